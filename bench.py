@@ -17,9 +17,18 @@ steps / max-over-ranks time (strong scaling: total work fixed).
 ``--workload C3`` at N = 1 is the unsharded 1-GPU reference point of that
 curve; ``--workload C2`` at N > 1 runs independent replicas (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-``roofline`` for the dominant kernel (HIP events on the session stream) and
-``cpu_baseline`` (the reference-like NumPy/SciPy loop on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps and prints the headline (``value``, ``ms_per_step``) with the run's
+counts.  ``--full`` adds everything that takes runs of its own: ``roofline``
+for the dominant kernel (HIP events on the session stream, one extra run with
+every kernel timed), ``fast_mode`` / ``mask_flips_vs_exact`` (the other fit
+mode on the same archive), ``per_rank`` on several GPUs, and ``cpu_baseline``
+(the reference-like NumPy/SciPy loop on a bounded sample).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step
+computed as ``DIR/<name>.npy`` (dump_outputs below).  The archive is generated
+from fixed seeds, so two builds run with the same arguments can be compared
+array for array.
 """
 from __future__ import annotations
 
@@ -366,6 +375,71 @@ def per_rank_report(ktimes, exch, rank, world, dev, wall_ms):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 * 10 ** 6   # --dump-outputs writes at most this much per rank
+DUMP_PROFILE_BYTES = 8 + 4 + 4 + 8 + 4 + 4   # test f64 + its code f32, weights f32, amp f64 + code, info as f32
+
+
+def sample_profiles(P, budget=DUMP_BUDGET_BYTES):
+    """The profiles --dump-outputs keeps of an archive of P: None (all) when
+    they fit the budget, else a fixed seeded sample of flat profile indices,
+    sorted, the same for every run on that shape."""
+    if P * DUMP_PROFILE_BYTES <= budget:
+        return None
+    keep = budget // (DUMP_PROFILE_BYTES + 8)   # + the sample's own index, written as f64
+    return np.sort(np.random.default_rng(1152000).choice(P, size=keep, replace=False))
+
+
+def finite_pair(a):
+    """A float array as two finite ones: the values with every non-finite entry
+    set to 0, and an f32 code per entry (0 finite, 1 NaN, 2 +inf, 3 -inf).  The
+    loop's outputs hold NaN and inf by design (numpy.ma's results on dead
+    channels); the files written are all finite, and nothing is lost."""
+    code = np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0))).astype(np.float32)
+    return np.where(code == 0, a, 0).astype(a.dtype), code
+
+
+def dump_outputs(sess, last, outdir, suffix=""):
+    """--dump-outputs: what the last timed step computed, as the arrays a
+    caller of the session receives, one ``<name><suffix>.npy`` each, f32 or f64,
+    every value finite (test, amp and template as finite_pair's values, with
+    their codes in <name>_nonfinite):
+      test, weights   run()'s avg_test_results (f64) and zap weights (f32), [P]
+      amp, info       the last iteration's fit amplitude (f64) and status (as f32), [P]
+      template        the last iteration's template (f32), [nbin]
+      loops           [loops, n_iter, converged] (f64)
+      changed, nzero, bad_fits   per iteration (f64)
+      sample_index    only for an archive over the budget: the flat profile
+                      indices (f64) the [P] arrays were sampled at
+    The timed steps leave test and weights on the GPU (run(fetch=False)) and the
+    library hands them out only from a run.  So the fit and the template are
+    read back first (they are the last timed step's own), then one more untimed
+    run of the same session fetches test and weights; that run must repeat the
+    last timed step - its counts and its fit amplitudes are compared bit for
+    bit, and a difference is an error."""
+    amp, info = sess.fit()
+    template = sess.template()
+    again = sess.run()
+    same = all(again[k] == last[k] for k in ("loops", "n_iter", "converged")) and \
+        all(np.array_equal(again[k], last[k]) for k in ("changed", "nzero", "bad_fits"))
+    if not same or sess.fit()[0].tobytes() != amp.tobytes():
+        raise SystemExit("bench.py: the run that fetches the outputs did not repeat the last timed step")
+    out = {"weights": again["weights"].ravel(), "info": info.ravel().astype(np.float32)}
+    out["test"], out["test_nonfinite"] = finite_pair(again["test"].ravel())
+    out["amp"], out["amp_nonfinite"] = finite_pair(amp.ravel())
+    idx = sample_profiles(amp.size)
+    if idx is not None:
+        out = {k: v[idx] for k, v in out.items()}
+        out["sample_index"] = idx.astype(np.float64)
+    out["template"], out["template_nonfinite"] = finite_pair(template)
+    out["loops"] = np.array([last["loops"], last["n_iter"], last["converged"]], np.float64)
+    for k in ("changed", "nzero", "bad_fits"):
+        out[k] = np.asarray(last[k], np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in out.items():
+        assert arr.dtype in (np.float32, np.float64) and np.isfinite(arr).all(), name
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.ascontiguousarray(arr))
+
+
 def batch_main(a, workload, rank, world, local, dev):
     """C4: every rank cleans `--batch` archives per step from page-locked host
     memory through the batch pipeline (iterative_cleaner_amd/batch.py); three
@@ -438,18 +512,112 @@ def batch_main(a, workload, rank, world, local, dev):
         dist.destroy_process_group()
 
 
-def main():
+def roofline_record(ktimes, dom, shape, run_counts, steps, exact_mode, fft, wl_key):
+    """--full: the ``roofline`` record of the line.  `ktimes`: {kernel: {ms,
+    launches}} over the timed steps (`dom`, the dominant kernel, timed there;
+    the others scaled from the breakdown run); `shape`: this rank's (nsub,
+    nchan, nbin); `wl_key`: the key of the committed PMC summaries."""
+    nsub, lnchan, nbin = shape
+    n_iter = run_counts["n_iter"]
+    kernels = {k: v for k, v in ktimes.items() if k.startswith("k_")}
+    total_k = sum(v["ms"] for v in kernels.values())
+    dk = kernels[dom]
+    avg_s = dk["ms"] / 1000.0 / max(1, dk["launches"])
+    # implementation bytes (every sweep the kernel makes) and SURVEY §8(d) bytes
+    total_bytes = algorithmic_bytes(dom, nsub, lnchan, nbin, dk["launches"], run_counts, steps, exact_mode, fft)
+    sweep_launch = total_bytes / max(1, dk["launches"]) if total_bytes else None
+    s8d_total = s8d_bytes(dom, nsub, lnchan, nbin, dk["launches"], n_iter, steps)
+    s8d_launch = s8d_total / max(1, dk["launches"]) if s8d_total else None
+    hbm_s8d = s8d_launch / avg_s / 1e9 if s8d_launch else None
+    sweep_gbs = sweep_launch / avg_s / 1e9 if sweep_launch else None
+    per_kernel = {}
+    for kname, kv in ktimes.items():
+        if kv["launches"] == 0:
+            continue
+        tb = algorithmic_bytes(kname, nsub, lnchan, nbin, kv["launches"], run_counts, steps, exact_mode, fft)
+        pk = {"ms_per_step": round(kv["ms"] / steps, 3), "launches_per_step": kv["launches"] // steps,
+              "sweep_gbs": round(tb / (kv["ms"] / 1000.0) / 1e9, 1) if tb else None}
+        sb = s8d_bytes(kname, nsub, lnchan, nbin, kv["launches"], n_iter, steps)
+        if sb:
+            pk["s8d_gbs"] = round(sb / (kv["ms"] / 1000.0) / 1e9, 1)
+        per_kernel[kname] = pk
+    traffic, src = pmc_traffic(wl_key, dom)
+    valu, vsrc = pmc_valu(wl_key)
+    hbm = {"achieved": round(hbm_s8d, 1) if hbm_s8d else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+           "frac": round(hbm_s8d / HBM_PEAK_GBS, 4) if hbm_s8d else None,
+           "algorithmic_bytes_per_launch": int(s8d_launch) if s8d_launch else None,
+           "definition": "SURVEY §8(d) bytes: one 4N cube read per iteration for the fit (+ diagnostics) "
+                         "and one for the template, divided over the kernel's launches"}
+    roof = {"bound": "hbm", "kernel": dom, "achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": hbm["frac"], "traffic": traffic,
+            "traffic_source": src if traffic else "no PMC summary for these HIP sources",
+            "avg_launch_ms": round(1000 * avg_s, 3), "kernel_share": round(dk["ms"] / total_k, 3),
+            "hbm_frac_s8d": hbm["frac"], "hbm_s8d": hbm,
+            "sweep_bytes": {"per_launch": int(sweep_launch) if sweep_launch else None,
+                            "gbs": round(sweep_gbs, 1) if sweep_gbs else None,
+                            "definition": "every data sweep the kernel makes (lmdif re-sweeps included)"}}
+    if valu:
+        for kname, pk in per_kernel.items():
+            v = valu.get(kname)
+            kv = ktimes[kname]
+            if v and v["launches"] and kv["launches"]:
+                g = v["valu_insts_per_launch"] / (kv["ms"] / kv["launches"] / 1000.0) / 1e9
+                pk["valu_frac"] = round(g / VALU_PEAK_G, 3)
+        v = valu.get(dom)
+        if v:
+            g = v["valu_insts_per_launch"] / avg_s / 1e9
+            roof["valu"] = {"achieved": round(g, 1), "peak": VALU_PEAK_G, "unit": "G wave64 VALU inst/s",
+                            "frac": round(g / VALU_PEAK_G, 4), "insts_per_launch": v["valu_insts_per_launch"],
+                            "f64_share": v["f64_share_of_valu"], "source": vsrc}
+    if traffic:
+        # measured HBM bytes (PMC) per launch over the launch time: what the
+        # kernel actually moves, re-sweeps and refetches included
+        tg = traffic / avg_s / 1e9
+        roof["traffic_gbs"] = round(tg, 1)
+        roof["traffic_frac"] = round(tg / HBM_PEAK_GBS, 4)
+    # the roof that binds is the larger measured fraction: PMC traffic
+    # against HBM peak, or VALU issue against its peak (DESIGN.md)
+    vf = roof.get("valu", {}).get("frac")
+    if vf is not None and vf > roof.get("traffic_frac", 0.0):
+        vv = roof["valu"]
+        roof.update({"bound": "valu", "achieved": vv["achieved"], "peak": vv["peak"], "unit": vv["unit"],
+                     "frac": vv["frac"]})
+        roof["bound_note"] = ("VALU issue (%.2f of peak) exceeds measured HBM traffic (%s of peak); the HBM "
+                              "fraction in SURVEY §8(d) bytes is hbm_frac_s8d" % (vf, roof.get("traffic_frac")))
+    elif "traffic_frac" in roof:
+        roof["bound_note"] = ("measured HBM traffic %.2f of peak (re-sweeps included); frac/achieved use "
+                              "SURVEY §8(d) algorithmic bytes" % roof["traffic_frac"])
+    roof["per_kernel"] = per_kernel
+    over, resident = check_kernel_rates(per_kernel, 4 * nsub * lnchan * nbin)
+    if over:
+        raise SystemExit("bench.py: per-kernel rates above the HBM peak (%s GB/s) on a %d-MB cube: the byte "
+                         "model is wrong: %s" % (HBM_PEAK_GBS, 4 * nsub * lnchan * nbin // 2 ** 20, over))
+    if resident:
+        roof["cache_resident_above_hbm_peak"] = resident
+    roof["timing"] = ("%s: HIP events on the session stream over the timed region (only this kernel timed "
+                      "there); per_kernel: one extra run with every kernel timed, scaled to the steps" % dom)
+    return roof
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: C2 on one GPU, C3 channel-sharded on several")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel breakdown and roofline "
+                         "(one extra run, HIP events on the dominant kernel in the timed steps), the other fit "
+                         "mode on the same archive, per-rank times on several GPUs, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                         "(f32 / f64; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--untimed-kernels", action="store_true",
-                    help="A/B only: no per-kernel HIP events in the timed region (the line then has no roofline)")
+                    help="--full, A/B only: no per-kernel HIP events in the timed region (the line then has no roofline)")
     ap.add_argument("--cpu-budget", type=float, default=30.0)
-    ap.add_argument("--kernel-report", action="store_true", help="print per-kernel times to stderr")
+    ap.add_argument("--kernel-report", action="store_true", help="--full: print per-kernel times to stderr")
     ap.add_argument("--batch", type=int, default=0,
                     help="batch mode (config C4): clean this many archives per step per GPU from "
                          "page-locked host memory, each upload overlapped with the previous cleaning "
@@ -463,9 +631,9 @@ def main():
                          "closed: the closed-form amplitude fused with the diagnostics (fit_mode 1, fast mode; "
                          "also reports the zap-mask flips against the exact mode on the same archive)")
     ap.add_argument("--no-fast-summary", action="store_true",
-                    help="exact mode at N=1: skip the closed-form (fit_mode 1) summary added to the line")
+                    help="--full, exact mode at N=1: skip the closed-form (fit_mode 1) summary added to the line")
     ap.add_argument("--no-flip-check", action="store_true",
-                    help="closed mode: skip the (untimed) exact run that counts zap-mask flips "
+                    help="--full, closed mode: skip the (untimed) exact run that counts zap-mask flips "
                          "(profiling passes, whose kernel tallies it would mix in)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="a session schedule option (_native.OPTIONS; same bits under every setting), repeatable")
@@ -473,7 +641,11 @@ def main():
                     help="shift: integer dedispersion shifts (default); fft: fractional delays, dedispersed by "
                          "psrchive's FFT phase rotation (dedisp_mode IC_DEDISP_FFT); fft_pp: the same with one "
                          "delay per profile (psrchive's per-Integration folding period, ic_set_delays2)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.batch and a.dump_outputs:
+        ap.error("--dump-outputs is not available with --batch (the batch pipeline hands out no arrays here)")
 
     import torch
     import torch.distributed as dist
@@ -570,11 +742,11 @@ def main():
     torch.cuda.synchronize()
     sess.upload_device(cube.data_ptr(), w0.data_ptr(), shift.data_ptr())
     fast = None
-    if fit_mode == _native.FIT_EXACT and not sharded and world == 1 and not a.no_fast_summary:
+    if a.full and fit_mode == _native.FIT_EXACT and not sharded and world == 1 and not a.no_fast_summary:
         # the north star's fast mode on the same archive, beside the exact line
         fast = fast_mode_summary(_native, cube, w0, shift, (nsub, nchan, nbin), local, a.steps, torch, delay)
     flips = None
-    if fit_mode == _native.FIT_CLOSED and not sharded and not a.no_flip_check:
+    if a.full and fit_mode == _native.FIT_CLOSED and not sharded and not a.no_flip_check:
         # zap-mask flips of the fast mode against the exact fit on this archive (untimed)
         fres = sess.run()
         with _native.GpuSession(nsub, nchan, nbin, max_iter=5, device=local, delay=delay) as ex:
@@ -593,7 +765,7 @@ def main():
     ktimes_all = {}
     dom = None
     rank_report = None
-    if not a.untimed_kernels:
+    if a.full and not a.untimed_kernels:
         sess.set_timing(True)
         if sharded:
             comm.timing = True
@@ -638,10 +810,12 @@ def main():
     stats = sess.run_stats()
     n_iter = out["n_iter"]
     run_counts = dict(stats, n_iter=n_iter, changed=[int(c) for c in out["changed"]])
+    if a.dump_outputs:
+        dump_outputs(sess, out, a.dump_outputs, "_rank%d" % rank if world > 1 else "")
     exact_weights = sess.run()["weights"] if fast is not None else None
     sess.close()
 
-    if rank == 0 and a.untimed_kernels:
+    if rank == 0 and a.full and a.untimed_kernels:
         print(json.dumps({"metric": "profiles cleaned/sec (whole node)", "value": round(a.steps * P_total / elapsed, 1),
                           "ms_per_step": round(1000.0 * elapsed / a.steps, 3), "untimed_kernels": True}))
         return
@@ -649,94 +823,8 @@ def main():
         lnchan = sess.shape[1]                 # this rank's channels (kernel byte counts)
         ms_step = 1000.0 * elapsed / a.steps
         value = a.steps * P_total / elapsed
-        kernels = {k: v for k, v in ktimes.items() if k.startswith("k_")}
-        total_k = sum(v["ms"] for v in kernels.values())
-        dk = kernels[dom]
-        avg_s = dk["ms"] / 1000.0 / max(1, dk["launches"])
-        # implementation bytes (every sweep the kernel makes) and SURVEY §8(d) bytes
-        exact_mode = fit_mode == _native.FIT_EXACT
-        total_bytes = algorithmic_bytes(dom, nsub, lnchan, nbin, dk["launches"], run_counts, a.steps, exact_mode,
-                                        delay is not None)
-        sweep_launch = total_bytes / max(1, dk["launches"]) if total_bytes else None
-        s8d_total = s8d_bytes(dom, nsub, lnchan, nbin, dk["launches"], n_iter, a.steps)
-        s8d_launch = s8d_total / max(1, dk["launches"]) if s8d_total else None
-        hbm_s8d = s8d_launch / avg_s / 1e9 if s8d_launch else None
-        sweep_gbs = sweep_launch / avg_s / 1e9 if sweep_launch else None
-        per_kernel = {}
-        for kname, kv in ktimes.items():
-            if kv["launches"] == 0:
-                continue
-            tb = algorithmic_bytes(kname, nsub, lnchan, nbin, kv["launches"], run_counts, a.steps, exact_mode,
-                                   delay is not None)
-            pk = {"ms_per_step": round(kv["ms"] / a.steps, 3), "launches_per_step": kv["launches"] // a.steps,
-                  "sweep_gbs": round(tb / (kv["ms"] / 1000.0) / 1e9, 1) if tb else None}
-            sb = s8d_bytes(kname, nsub, lnchan, nbin, kv["launches"], n_iter, a.steps)
-            if sb:
-                pk["s8d_gbs"] = round(sb / (kv["ms"] / 1000.0) / 1e9, 1)
-            per_kernel[kname] = pk
-        wl_key = workload if not sharded else "%s/%d" % (workload, world)
-        if fit_mode == _native.FIT_CLOSED:
-            wl_key += "/closed"
-        if delay is not None:
-            wl_key += "/" + a.dedisp
-        traffic, src = pmc_traffic(wl_key, dom)
-        valu, vsrc = pmc_valu(wl_key)
-        hbm = {"achieved": round(hbm_s8d, 1) if hbm_s8d else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-               "frac": round(hbm_s8d / HBM_PEAK_GBS, 4) if hbm_s8d else None,
-               "algorithmic_bytes_per_launch": int(s8d_launch) if s8d_launch else None,
-               "definition": "SURVEY §8(d) bytes: one 4N cube read per iteration for the fit (+ diagnostics) "
-                             "and one for the template, divided over the kernel's launches"}
-        roof = {"bound": "hbm", "kernel": dom, "achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": hbm["frac"], "traffic": traffic,
-                "traffic_source": src if traffic else "no PMC summary for these HIP sources",
-                "avg_launch_ms": round(1000 * avg_s, 3), "kernel_share": round(dk["ms"] / total_k, 3),
-                "hbm_frac_s8d": hbm["frac"], "hbm_s8d": hbm,
-                "sweep_bytes": {"per_launch": int(sweep_launch) if sweep_launch else None,
-                                "gbs": round(sweep_gbs, 1) if sweep_gbs else None,
-                                "definition": "every data sweep the kernel makes (lmdif re-sweeps included)"}}
-        if valu:
-            for kname, pk in per_kernel.items():
-                v = valu.get(kname)
-                kv = ktimes[kname]
-                if v and v["launches"] and kv["launches"]:
-                    g = v["valu_insts_per_launch"] / (kv["ms"] / kv["launches"] / 1000.0) / 1e9
-                    pk["valu_frac"] = round(g / VALU_PEAK_G, 3)
-            v = valu.get(dom)
-            if v:
-                g = v["valu_insts_per_launch"] / avg_s / 1e9
-                roof["valu"] = {"achieved": round(g, 1), "peak": VALU_PEAK_G, "unit": "G wave64 VALU inst/s",
-                                "frac": round(g / VALU_PEAK_G, 4), "insts_per_launch": v["valu_insts_per_launch"],
-                                "f64_share": v["f64_share_of_valu"], "source": vsrc}
-        if traffic:
-            # measured HBM bytes (PMC) per launch over the launch time: what the
-            # kernel actually moves, re-sweeps and refetches included
-            tg = traffic / avg_s / 1e9
-            roof["traffic_gbs"] = round(tg, 1)
-            roof["traffic_frac"] = round(tg / HBM_PEAK_GBS, 4)
-        # the roof that binds is the larger measured fraction: PMC traffic
-        # against HBM peak, or VALU issue against its peak
-        vf = roof.get("valu", {}).get("frac")
-        if vf is not None and vf > roof.get("traffic_frac", 0.0):
-            vv = roof["valu"]
-            roof.update({"bound": "valu", "achieved": vv["achieved"], "peak": vv["peak"], "unit": vv["unit"],
-                         "frac": vv["frac"]})
-            roof["bound_note"] = ("VALU issue (%.2f of peak) exceeds measured HBM traffic (%s of peak); the HBM "
-                                  "fraction in SURVEY §8(d) bytes is hbm_frac_s8d" % (vf, roof.get("traffic_frac")))
-        elif "traffic_frac" in roof:
-            roof["bound_note"] = ("measured HBM traffic %.2f of peak (re-sweeps included); frac/achieved use "
-                                  "SURVEY §8(d) algorithmic bytes" % roof["traffic_frac"])
-        roof["per_kernel"] = per_kernel
-        over, resident = check_kernel_rates(per_kernel, 4 * nsub * lnchan * nbin)
-        if over:
-            raise SystemExit("bench.py: per-kernel rates above the HBM peak (%s GB/s) on a %d-MB cube: the byte "
-                             "model is wrong: %s" % (HBM_PEAK_GBS, 4 * nsub * lnchan * nbin // 2 ** 20, over))
-        if resident:
-            roof["cache_resident_above_hbm_peak"] = resident
-        roof["timing"] = ("%s: HIP events on the session stream over the timed region (only this kernel timed "
-                          "there); per_kernel: one extra run with every kernel timed, scaled to the steps" % dom)
         iter_bytes = 8 * per_rank_P * nbin + 64 * per_rank_P    # SURVEY §8(d) B_iter, one GPU's share
         loop_gbs = iter_bytes * n_iter / (elapsed / a.steps) / 1e9
-        roof["loop_hbm_frac"] = round(loop_gbs / HBM_PEAK_GBS, 4)
         if sharded:
             parallelism = "channel-sharded x%d (RCCL per iteration: 3 all-to-alls to row owners, " \
                           "3 all-gathers of owner results, 1 all-reduce; %s)" % (
@@ -770,8 +858,17 @@ def main():
                        "parallelism": parallelism,
                        "loop_hbm_gbs_per_gpu": round(loop_gbs, 1),
                        "loop_hbm_frac": round(loop_gbs / HBM_PEAK_GBS, 4)},
-            "roofline": roof,
         }
+        if a.full:
+            wl_key = workload if not sharded else "%s/%d" % (workload, world)
+            if fit_mode == _native.FIT_CLOSED:
+                wl_key += "/closed"
+            if delay is not None:
+                wl_key += "/" + a.dedisp
+            roof = roofline_record(ktimes, dom, (nsub, lnchan, nbin), run_counts, a.steps,
+                                   fit_mode == _native.FIT_EXACT, delay is not None, wl_key)
+            roof["loop_hbm_frac"] = round(loop_gbs / HBM_PEAK_GBS, 4)
+            rec["roofline"] = roof
         if flips is not None:
             rec["config"]["mask_flips_vs_exact"] = flips
         if fast is not None:
@@ -781,7 +878,7 @@ def main():
             rec["config"]["exchange_ms_per_step"] = round(ktimes["exchange"]["ms"] / a.steps, 3)
         if rank_report is not None:
             rec["config"]["per_rank"] = rank_report
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 rec["cpu_baseline"] = cpu_baseline(nchan, nbin, seed, rfi, a.cpu_budget)
             except Exception as e:  # pragma: no cover

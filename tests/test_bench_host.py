@@ -8,6 +8,8 @@ tests keep the committed summaries in step with the sources.
 import os
 import sys
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
@@ -82,3 +84,21 @@ def test_rotation_bytes():
     assert bench.algorithmic_bytes("k_rotate", nsub, nchan, nbin, 7, run, 2) == \
         2 * (8 * N * (2 + 3) + 8 * nchan * nbin * 5)
     assert bench.s8d_bytes("k_rotate", nsub, nchan, nbin, 7, 3, 2) == 8 * N * 3 * 2
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    nsub, nchan = bench.WORKLOADS["C2"][:2]
+    assert bench.sample_profiles(nsub * nchan) is None          # the flagship archive is written whole
+    nsub, nchan = bench.WORKLOADS["C3"][:2]
+    idx = bench.sample_profiles(nsub * nchan)
+    assert idx.size * (bench.DUMP_PROFILE_BYTES + 8) <= bench.DUMP_BUDGET_BYTES < 64 * 10 ** 6
+    assert idx[0] >= 0 and idx[-1] < nsub * nchan and (idx[1:] > idx[:-1]).all()
+    assert (bench.sample_profiles(nsub * nchan) == idx).all()
+
+
+def test_finite_pair_keeps_every_kind_of_value():
+    a = np.array([1.5, np.nan, -0.0, np.inf, -np.inf, 3.0])
+    vals, code = bench.finite_pair(a)
+    assert vals.dtype == a.dtype and np.isfinite(vals).all()
+    assert vals.tolist() == [1.5, 0.0, -0.0, 0.0, 0.0, 3.0] and np.signbit(vals[2])
+    assert code.dtype == np.float32 and code.tolist() == [0, 1, 0, 2, 3, 0]

@@ -13,7 +13,7 @@ mkdir -p $OUT
 for r in $(seq 1 $R); do
   for i in "${!VARS[@]}"; do
     v=${VARS[$i]}; [ "$v" = "-" ] && v=""
-    timeout -k 10 200 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-fast-summary $v "$@" \
+    timeout -k 10 200 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-fast-summary $v "$@" \
         > $OUT/${i}_$r.json 2> $OUT/${i}_$r.err || exit 1
     echo "[$i] $v round $r: $(python3 -c "import json,sys; print(json.loads(open('$OUT/${i}_$r.json').read().splitlines()[-1])['ms_per_step'])")"
   done

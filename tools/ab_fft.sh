@@ -8,7 +8,7 @@ mkdir -p gpurun_out/abfft
 for r in $(seq 1 $R); do
   for v in $VARS; do
     f=gpurun_out/abfft/${v}_$r
-    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --workload $WL --dedisp fft --steps 5 --warmup 1 \
+    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --full --workload $WL --dedisp fft --steps 5 --warmup 1 \
         --no-cpu-baseline --no-flip-check --no-fast-summary > $f.json 2> $f.err || exit 1
     python3 -c "
 import json; d=json.loads(open('$f.json').read().splitlines()[-1]); pk=d['roofline']['per_kernel']

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/abl
 for r in $(seq 1 $R); do
   for v in $VARS; do
     f=gpurun_out/abl/${v}_$r
-    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline \
+    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline \
         --no-flip-check --no-fast-summary "$@" > $f.json 2> $f.err || exit 1
     python3 -c "
 import json; d=json.loads(open('$f.json').read().splitlines()[-1]); pk=d['roofline']['per_kernel']

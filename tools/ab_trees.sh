@@ -10,7 +10,7 @@ for r in $(seq 1 $R); do
   for d in $DIRS; do
     n=$(basename $(cd $d && pwd)); [ "$d" = "." ] && n=head
     f=$root/gpurun_out/abt/${n}_${WL}_$r
-    (cd $d && timeout -k 10 300 python bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline \
+    (cd $d && timeout -k 10 300 python bench.py --full --workload $WL --steps 5 --warmup 2 --no-cpu-baseline \
         --no-flip-check --no-fast-summary "$@" > $f.json 2> $f.err) || { tail -5 $f.err; exit 1; }
     python3 -c "
 import json; d=json.loads(open('$f.json').read().splitlines()[-1])

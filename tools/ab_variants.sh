@@ -6,7 +6,7 @@ VARS=${1:?variants}; R=${2:-2}; shift 2
 mkdir -p gpurun_out/ab
 for r in $(seq 1 $R); do
   for v in $VARS; do
-    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --steps 10 --warmup 2 --no-cpu-baseline \
+    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline \
         --no-flip-check --no-fast-summary "$@" > gpurun_out/ab/${v}_$r.json 2> gpurun_out/ab/${v}_$r.err || exit 1
     echo "$v $r done"
   done

@@ -9,7 +9,7 @@ for wl in $WLS; do
  for r in $(seq 1 $R); do
   for v in $VARS; do
     f=gpurun_out/abwl/${wl}_${v}_$r
-    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --workload $wl --steps 10 --warmup 2 \
+    IC_LIBRARY=ab/libicgpu_$v.so timeout -k 10 200 python bench.py --full --workload $wl --steps 10 --warmup 2 \
         --no-cpu-baseline --no-flip-check --no-fast-summary > $f.json 2> $f.err || exit 1
     python3 -c "
 import json; d=json.loads(open('$f.json').read().splitlines()[-1]); pk=d['roofline']['per_kernel']

@@ -19,6 +19,6 @@ cp gpurun_out/prof_${TAG}_$lc/pmc_traffic.json profiles/${RND}_${lc}_pmc_traffic
 cp gpurun_out/valu_${TAG}_$lc/pmc_valu.json profiles/${RND}_${lc}_pmc_valu_$TAG.json
 cp gpurun_out/prof_${TAG}_$lc/kernel_stats.csv $OUT/kernel_stats_$lc.csv
 cp gpurun_out/valu_${TAG}_$lc/summary.txt $OUT/pmc_valu_summary_$lc.txt
-timeout -k 10 400 python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD "$@" > $OUT/$lc.json 2> $OUT/$lc.err \
+timeout -k 10 400 python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD "$@" > $OUT/$lc.json 2> $OUT/$lc.err \
     || { tail -5 $OUT/$lc.err; exit 1; }
 echo "evidence $WL $FM $DD done"

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 run() {  # name counters...
     local name=$1; shift
     timeout -s KILL 120 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- \
-        python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/$name.log 2>&1 \
+        python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/$name.log 2>&1 \
         || { tail -20 $OUT/$name.log; return 1; }
     python3 tools/pmc_summary.py $(find $OUT/$name -name '*counter_collection.csv' | head -1) > $OUT/$name.txt \
         && rm -rf $OUT/$name

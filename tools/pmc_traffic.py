@@ -2,7 +2,7 @@
 """Summarise rocprofv3 FETCH_SIZE / WRITE_SIZE passes into per-kernel HBM traffic.
 
 Usage (after two separate ``rocprofv3 --pmc FETCH_SIZE`` / ``--pmc WRITE_SIZE``
-runs of ``bench.py --steps 1 --warmup 0 --no-cpu-baseline``):
+runs of ``bench.py --full --steps 1 --warmup 0 --no-cpu-baseline``):
 
     python tools/pmc_traffic.py --fetch gpurun_out/pmcF/pmc_counter_collection.csv \
         --write gpurun_out/pmcW/pmc_counter_collection.csv --workload C2 \
@@ -86,7 +86,7 @@ def main():
             "traffic_bytes_per_launch": int((fetch_b + write_b) / max(1, launches)),
         }
     rec = {"workload": a.workload, "source_sha": source_sha(),
-           "command": "bench.py --workload %s --steps 1 --warmup 0 --no-cpu-baseline" % a.workload,
+           "command": "bench.py --full --workload %s --steps 1 --warmup 0 --no-cpu-baseline" % a.workload,
            "correction": "FETCH_SIZE x2 (gfx950 wide-stream tally), KiB -> bytes",
            "kernels": kernels}
     with open(a.out, "w") as f:

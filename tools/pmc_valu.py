@@ -43,7 +43,7 @@ def main():
             "f64_share_of_valu": round(f64 / tot["SQ_INSTS_VALU"], 3) if tot["SQ_INSTS_VALU"] else None,
         }
     rec = {"workload": a.workload, "source_sha": source_sha(),
-           "command": "bench.py --workload %s --steps 1 --warmup 0 --no-cpu-baseline" % a.workload,
+           "command": "bench.py --full --workload %s --steps 1 --warmup 0 --no-cpu-baseline" % a.workload,
            "definition": "valu_insts = SQ_INSTS_VALU (wave64 instructions, 4 SIMD cycles each); "
                          "f64 lane-ops = 64 x (ADD+MUL+FMA+TRANS)_F64",
            "kernels": kernels}

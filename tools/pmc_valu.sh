@@ -16,7 +16,7 @@ export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 \
     SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVES \
     --output-format csv -d $OUT/pmc -o run -- \
-    python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmc.log 2>&1 \
+    python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmc.log 2>&1 \
     || { tail -20 $OUT/pmc.log; exit 1; }
 C=$(find $OUT/pmc -name '*counter_collection.csv' | head -1)
 python3 tools/pmc_summary.py "$C" > $OUT/summary.txt || exit 1

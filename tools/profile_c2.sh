@@ -16,14 +16,14 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 show() { echo "---- $1"; tail -20 "$1"; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- \
-    python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD --steps 5 --warmup 1 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/bench_stats.log 2>&1 \
+    python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD --steps 5 --warmup 1 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/bench_stats.log 2>&1 \
     || { show $OUT/bench_stats.log; exit 1; }
 find $OUT/stats -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmcF -o run -- \
-    python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmcF.log 2>&1 \
+    python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmcF.log 2>&1 \
     || { show $OUT/pmcF.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmcW -o run -- \
-    python3 bench.py --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmcW.log 2>&1 \
+    python3 bench.py --full --workload $WL --fit-mode $FM --dedisp $DD --steps 1 --warmup 0 --no-cpu-baseline --no-flip-check --no-fast-summary > $OUT/pmcW.log 2>&1 \
     || { show $OUT/pmcW.log; exit 1; }
 F=$(find $OUT/pmcF -name '*counter_collection.csv' | head -1)
 W=$(find $OUT/pmcW -name '*counter_collection.csv' | head -1)

@@ -9,6 +9,7 @@
 #   tools/rehearse_native_rccl.sh N [bench args...] -> gpurun_out/rehearse_N.json
 set -o pipefail
 N=${1:?ranks}; shift
+set -- --full "$@"   # the whole line: per_rank and the roofline beside the headline
 mkdir -p gpurun_out
 IC_BENCH_BACKEND=gloo IC_BENCH_RCCL_LIBRARY=$PWD/tests/stub_rccl/libstubrccl.so IC_STUB_RCCL_OUTBOX_MB=${IC_STUB_RCCL_OUTBOX_MB:-512} \
     timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define IC_ABI_VERSION 8
+#define IC_ABI_VERSION 9
 
 #define IC_OK 0
 #define IC_EINVAL -1   /* bad argument / shape                         */
@@ -144,6 +144,43 @@ int ic_upload_device(void *session, const float *d_cube, const float *d_w0,
 int ic_upload_async(void *session, const float *cube, const float *w0, const int32_t *shift);
 int ic_host_alloc(size_t bytes, void **ptr);
 void ic_host_free(void *ptr);
+
+/* Quantised uploads: the samples as a fold-mode PSRFITS archive stores them,
+ * decoded on the device, so that 2 bytes per sample cross the bus instead of 4.
+ *   q     [nsub][npol][nchan][nbin] int16, the DATA column (host byte order, or
+ *         with IC_Q_BIG_ENDIAN in flags the FITS order: each sample's two bytes
+ *         are then swapped on the device)
+ *   scl,
+ *   offs  [nsub][npol][nchan] f32, DAT_SCL / DAT_OFFS
+ *   nsum  1: the cube is polarisation 0 (Intensity; Stokes, I = pol 0);
+ *         2: pol 0 + pol 1 (AA+BB: PPQQ, Coherence); nsum <= npol
+ * Only the first nsum polarisations of each subint are copied (strided copies,
+ * as ic_upload_pols).  The session's cube becomes, sample for sample,
+ *   d_p = f32(f32(q_p) * scl_p + offs_p)          (psrfits.py decode)
+ *   nsum 1: d_0        nsum 2: f32(d_0 + d_1)     (archive.py pscrunch)
+ * with the multiply, the add and the polarisation add each rounded to IEEE f32
+ * on its own (no fused multiply-add): bit-identical to decoding and
+ * pscrunching on the host and calling ic_upload.  w0 and shift as ic_upload; on
+ * a shard session nchan is the shard's slice.  The first quantised upload into
+ * an input slot allocates its staging on the device (nsum * (2 nbin + 8) bytes
+ * per profile), kept for reuse until the session is destroyed; IC_ENOMEM if
+ * that fails.  IC_EINVAL: a null pointer, npol < 1, nsum not 1 or 2,
+ * nsum > npol, unknown flag bits, a shift outside [0, nbin).
+ *
+ * ic_upload_quantised is synchronous (IC_ESTATE while asynchronous uploads are
+ * pending).  ic_upload_quantised_async follows ic_upload_async's rules (two
+ * slots, first in first out, the page-locked host arrays untouched until the
+ * consuming ic_run returns) and may be mixed with it in one queue; the decode
+ * runs on the copy stream behind its copy, so it overlaps the cleaning of the
+ * archive before it. */
+#define IC_Q_BIG_ENDIAN 1
+int ic_upload_quantised(void *session, const int16_t *q, const float *scl, const float *offs, int npol, int nsum,
+                        int flags, const float *w0, const int32_t *shift);
+int ic_upload_quantised_async(void *session, const int16_t *q, const float *scl, const float *offs, int npol,
+                              int nsum, int flags, const float *w0, const int32_t *shift);
+/* The same decode alone: out [nsub][nchan][nbin] f32 on the host.  Synchronous. */
+int ic_decode_profiles(int device, int nsub, int npol, int nsum, int nchan, int nbin, const int16_t *q,
+                       const float *scl, const float *offs, int flags, float *out);
 
 /* Run the cleaning loop to convergence or max_iter (iterative_cleaner.py:83-146).
  * Outputs (host, any may be NULL):

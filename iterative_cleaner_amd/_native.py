@@ -13,7 +13,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # IC_LIBRARY: an alternative build of the same library (A/B measurements)
 LIB_PATH = os.environ.get("IC_LIBRARY") or os.path.join(HERE, "libicgpu.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # symbols exported by libicgpu.so, as declared in include/iterative_cleaner.h
 EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session_destroy",
@@ -26,7 +26,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_fit_profiles", "ic_get_diagnostics_f64", "ic_set_delays", "ic_rotate_profiles",
            "ic_set_timing_kernel", "ic_set_option", "ic_get_option", "ic_comprehensive_stats_rowstat",
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
-           "ic_set_delays2", "ic_rotate_profiles2")
+           "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
+           "ic_decode_profiles")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -34,6 +35,8 @@ OPTIONS = {"fit_tail": 1, "diag_fork": 2, "fork_delay": 3, "template_incr": 4, "
            "rowstat_waves": 6, "rowstat_minlen": 7, "diag_chain": 8, "sync_timeout_ms": 9,
            "fit_schedule": 10, "tail_split": 13, "rot_stats": 14}
 FIT_ROUNDS = 0   # IC_FIT_ROUNDS: sweep / state rounds (k_fit_pass, k_fit_state, k_fit_tail); the only schedule
+
+Q_BIG_ENDIAN = 1   # IC_Q_BIG_ENDIAN: int16 samples in the FITS byte order
 
 FIT_EXACT = 0    # IC_FIT_EXACT: scipy leastsq emulated bit for bit (the reference's arithmetic)
 FIT_CLOSED = 1   # IC_FIT_CLOSED: closed-form amplitude fused with the diagnostics (fast mode)
@@ -140,6 +143,9 @@ def load_library(path: str = LIB_PATH):
     lib.ic_get_option.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     lib.ic_upload_async.argtypes = [vp, vp, vp, vp]
     lib.ic_upload_pols.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.ic_upload_quantised.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.ic_upload_quantised_async.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.ic_decode_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.ic_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     lib.ic_host_free.argtypes = [vp]
     lib.ic_host_free.restype = None
@@ -293,6 +299,47 @@ class GpuSession:
                 raise ValueError("upload_async needs C-contiguous %s %s arrays" % (dt.__name__, shape))
         self._check(self.lib.ic_upload_async(self.h, _ptr(cube), _ptr(w0), _ptr(shift)), "ic_upload_async")
 
+    def upload_quantised(self, q, scl, offs, w0, shift, nsum):
+        """PSRFITS samples as stored, decoded on the GPU (ic_upload_quantised):
+        q int16 (nsub, npol, nchan, nbin) or (nsub, nchan, nbin) for one
+        polarisation - dtype '>i2' is sent as it is and byte-swapped on the
+        device - with scl / offs f32 (nsub, npol, nchan); the cube becomes
+        pol 0 (nsum 1) or pol 0 + pol 1 (nsum 2) of psrfits.decode(q, scl, offs)."""
+        nsub, nchan, nbin = self.shape
+        q, flags = _quantised_samples(q)
+        if q.ndim == 3:
+            q = q.reshape(q.shape[0], 1, q.shape[1], q.shape[2])
+        q = np.ascontiguousarray(q)
+        if q.ndim != 4 or q.shape[0] != nsub or q.shape[2:] != (nchan, nbin):
+            raise ValueError("upload_quantised: q shape %s != (%d, npol, %d, %d)" % (q.shape, nsub, nchan, nbin))
+        npol = int(q.shape[1])
+        scl = np.ascontiguousarray(scl, dtype=np.float32).reshape(nsub, npol, nchan)
+        offs = np.ascontiguousarray(offs, dtype=np.float32).reshape(nsub, npol, nchan)
+        w0 = np.ascontiguousarray(w0, dtype=np.float32).reshape(nsub, nchan)
+        shift = np.ascontiguousarray(np.mod(shift, nbin), dtype=np.int32).reshape(nchan)
+        self._check(self.lib.ic_upload_quantised(self.h, _ptr(q), _ptr(scl), _ptr(offs), npol, int(nsum), flags,
+                                                 _ptr(w0), _ptr(shift)), "ic_upload_quantised")
+
+    def upload_quantised_async(self, q, scl, offs, w0, shift, nsum):
+        """Queue the copy and the decode of the next archive
+        (ic_upload_quantised_async); the arrays must stay alive and unmodified
+        until the run() that consumes them returns."""
+        nsub, nchan, nbin = self.shape
+        if q.dtype.kind != "i" or q.dtype.itemsize != 2:
+            raise ValueError("upload_quantised_async needs int16 samples (native or '>i2'), got %s" % q.dtype)
+        flags = 0 if q.dtype.isnative else Q_BIG_ENDIAN
+        npol = 1 if q.ndim == 3 else (q.shape[1] if q.ndim == 4 else -1)
+        qshape = (nsub, nchan, nbin) if q.ndim == 3 else (nsub, npol, nchan, nbin)
+        for a, shape, dt in ((q, qshape, q.dtype), (scl, (nsub, npol, nchan), np.dtype(np.float32)),
+                             (offs, (nsub, npol, nchan), np.dtype(np.float32)),
+                             (w0, (nsub, nchan), np.dtype(np.float32)), (shift, (nchan,), np.dtype(np.int32))):
+            # a 1-pol archive's scales may come as (nsub, nchan)
+            ok = a.shape == shape or (npol == 1 and shape[1:2] == (1,) and a.shape == (nsub, nchan))
+            if a.dtype != dt or not ok or not a.flags.c_contiguous:
+                raise ValueError("upload_quantised_async needs C-contiguous %s %s arrays" % (dt, shape))
+        self._check(self.lib.ic_upload_quantised_async(self.h, _ptr(q), _ptr(scl), _ptr(offs), npol, int(nsum),
+                                                       flags, _ptr(w0), _ptr(shift)), "ic_upload_quantised_async")
+
     def upload_device(self, cube_ptr: int, w0_ptr: int, shift_ptr: int):
         """Device pointers (e.g. torch tensor .data_ptr()) on this session's GPU."""
         self._check(self.lib.ic_upload_device(self.h, C.c_void_p(cube_ptr), C.c_void_p(w0_ptr),
@@ -410,6 +457,36 @@ def fit_profiles(profiles, template, fit_mode=FIT_EXACT, device=0):
     if rc != 0:
         raise NativeError("ic_fit_profiles: %s (rc=%d)" % (_err(lib), rc))
     return amp, info, R
+
+
+def _quantised_samples(q):
+    """(array, flags): int16 samples as they are - '>i2' keeps the FITS byte
+    order and sets IC_Q_BIG_ENDIAN - anything else converted to native int16."""
+    q = np.asarray(q)
+    if q.dtype.kind == "i" and q.dtype.itemsize == 2:
+        return q, (0 if q.dtype.isnative else Q_BIG_ENDIAN)
+    return q.astype(np.int16), 0
+
+
+def decode_profiles(q, scl, offs, nsum, device=0):
+    """PSRFITS decode and polarisation sum on the GPU (ic_decode_profiles):
+    q int16 (nsub, npol, nchan, nbin) (dtype '>i2': byte-swapped on the
+    device), scl / offs f32 (nsub, npol, nchan) -> (nsub, nchan, nbin) f32,
+    pol 0 (nsum 1) or pol 0 + pol 1 (nsum 2) of psrfits.decode(q, scl, offs)."""
+    lib = load_library()
+    q, flags = _quantised_samples(q)
+    q = np.ascontiguousarray(q)
+    if q.ndim != 4:
+        raise ValueError("decode_profiles: q must be (nsub, npol, nchan, nbin)")
+    nsub, npol, nchan, nbin = q.shape
+    scl = np.ascontiguousarray(scl, dtype=np.float32).reshape(nsub, npol, nchan)
+    offs = np.ascontiguousarray(offs, dtype=np.float32).reshape(nsub, npol, nchan)
+    out = np.empty((nsub, nchan, nbin), np.float32)
+    rc = lib.ic_decode_profiles(int(device), nsub, npol, int(nsum), nchan, nbin, _ptr(q), _ptr(scl), _ptr(offs),
+                                flags, _ptr(out))
+    if rc != 0:
+        raise NativeError("ic_decode_profiles: %s (rc=%d)" % (_err(lib), rc))
+    return out
 
 
 def rotate_profiles(cube, delay, sign=1, device=0):

@@ -123,6 +123,7 @@ class Profile:
         self._ar, self._isub, self._ipol, self._ichan = ar, isub, ipol, ichan
 
     def get_amps(self) -> np.ndarray:
+        self._ar._q_exact = False    # the caller may write through the view
         return self._ar._data[self._isub, self._ipol, self._ichan]
 
     def get_weight(self) -> float:
@@ -185,6 +186,29 @@ class Archive:
         self._cfreq = float(centre_frequency)
         self._mjd = (float(mjd_start), float(mjd_end))
         self._duty = float(baseline_duty)
+
+    # the samples; any assignment ends their being exactly decode(*_psrfits_q)
+    @property
+    def _data(self) -> np.ndarray:
+        return self._samples
+
+    @_data.setter
+    def _data(self, value) -> None:
+        self._samples = value
+        self._q_exact = False
+
+    def get_quantised(self):
+        """(q, scl, offs) of the PSRFITS file this archive was loaded from -
+        int16 (nsub, npol, nchan, nbin) and f32 (nsub, npol, nchan) - while the
+        samples are still exactly ``psrfits.decode(q, scl, offs)``; None once a
+        transform replaced them (pscrunch of several polarisations, a
+        dedisperse / dededisperse that moved data, remove_baseline, fscrunch,
+        tscrunch), once ``Profile.get_amps`` handed out its writable view, and
+        for an archive from anywhere else."""
+        return self._psrfits_q if self._q_exact else None
+
+    _psrfits_q = None
+    _q_exact = False
 
     # ---------------------------------------------------------------- shape
     def get_nsubint(self): return self._data.shape[0]

@@ -5,7 +5,9 @@ The reference cleans its archive list one after the other, reloading and
 re-processing each (iterative_cleaner.py:59-62).  Here one session is reused
 for every archive of a shape, and the host->device copy of archive k+1 runs on
 the session's copy stream while archive k is cleaned (ic_upload_async, two
-device input slots).  Host staging goes through a ring of page-locked buffers
+device input slots).  Archives may also go up as the int16 samples PSRFITS
+stores (ic_upload_quantised_async), decoded on the copy stream: half the bytes
+per archive.  Host staging goes through a ring of page-locked buffers
 filled by a loader thread, so reading/decoding archive k+2 overlaps too.
 
 A C4 archive (128 x 1024 x 512) is too small to fill an MI355X on its own:
@@ -36,18 +38,30 @@ JOIN_TIMEOUT_S = 600.0
 _LEAKED = []
 
 
-def pipeline(session, items, fetch=True):
-    """Clean every (cube, w0, shift) of `items` on `session`, overlapping each
-    archive's upload with the previous archive's cleaning.  The arrays must stay
-    valid until their result is yielded (page-locked for the copies to overlap).
-    Yields the ic_run dicts in order."""
+def _queue_upload(session, arrays, nsum):
+    """Queue one item's upload: (cube, w0, shift) f32, or the PSRFITS samples
+    (q, scl, offs, w0, shift), decoded on the GPU."""
+    if len(arrays) == 5:
+        session.upload_quantised_async(*arrays, nsum)
+    else:
+        session.upload_async(*arrays)
+
+
+def pipeline(session, items, fetch=True, nsum=1):
+    """Clean every item of `items` on `session`, overlapping each archive's
+    upload with the previous archive's cleaning.  An item is (cube, w0, shift),
+    or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
+    offsets (GpuSession.upload_quantised_async; `nsum` polarisations summed);
+    both kinds may alternate.  The arrays must stay valid until their result is
+    yielded (page-locked for the copies to overlap).  Yields the ic_run dicts in
+    order."""
     it = iter(items)
     first = next(it, None)
     if first is None:
         return
-    session.upload_async(*first)
+    _queue_upload(session, first, nsum)
     for nxt in it:
-        session.upload_async(*nxt)
+        _queue_upload(session, nxt, nsum)
         yield session.run(fetch)
     yield session.run(fetch)
 
@@ -55,8 +69,9 @@ def pipeline(session, items, fetch=True):
 _EXITED = -2   # a worker's last message (run_lanes)
 
 
-def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None):
-    """Clean every (cube, w0, shift) of `items` on `len(sessions)` sessions of one
+def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1):
+    """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
+    as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
     session overlaps its next upload with its current run).  The arrays must
     stay valid until their result is yielded.  Yields the ic_run dicts in input
@@ -72,7 +87,7 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None):
     destroys it under the running call) and, with the arrays it was handed,
     kept in _LEAKED."""
     if len(sessions) == 1:
-        yield from pipeline(sessions[0], items, fetch)
+        yield from pipeline(sessions[0], items, fetch, nsum)
         return
     stop = stop if stop is not None else threading.Event()
     work = queue.Queue(maxsize=2 * len(sessions))
@@ -97,7 +112,7 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None):
                 idx, arrays = item
                 held[lane].append(arrays)
                 del held[lane][:-3]             # an upload is consumed by the second run after it
-                sess.upload_async(*arrays)
+                _queue_upload(sess, arrays, nsum)
                 if pending is not None:
                     done.put((pending, sess.run(fetch)))
                 pending = idx
@@ -192,12 +207,18 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None):
 
 
 class _Ring:
-    """`n` page-locked (cube, w0, shift) slots."""
+    """`n` page-locked (cube, w0, shift) slots, or with `q_spec` = (npol, dtype)
+    (q, scl, offs, w0, shift) slots of int16 samples in that byte order."""
 
-    def __init__(self, n, nsub, nchan, nbin):
-        self.slots = [(_native.PinnedArray((nsub, nchan, nbin), np.float32),
-                       _native.PinnedArray((nsub, nchan), np.float32),
-                       _native.PinnedArray((nchan,), np.int32)) for _ in range(n)]
+    def __init__(self, n, nsub, nchan, nbin, q_spec=None):
+        if q_spec is None:
+            spec = [((nsub, nchan, nbin), np.float32)]
+        else:
+            npol, dtype = q_spec
+            spec = [((nsub, npol, nchan, nbin), dtype), ((nsub, npol, nchan), np.float32),
+                    ((nsub, npol, nchan), np.float32)]
+        spec += [((nsub, nchan), np.float32), ((nchan,), np.int32)]
+        self.slots = [tuple(_native.PinnedArray(shape, dt) for shape, dt in spec) for _ in range(n)]
 
     def arrays(self, i):
         return tuple(p.array for p in self.slots[i])
@@ -209,12 +230,24 @@ class _Ring:
 
 
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
-                pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None):
+                pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
     pipeline overlaps each upload with the previous cleaning, on `lanes`
-    concurrent sessions.  Yields one ic_run dict per archive, in order."""
+    concurrent sessions.  Yields one ic_run dict per archive, in order.
+
+    quantised=True: the loader yields (q, scl, offs, w0, shift) instead, the
+    int16 samples (nsub, npol, nchan, nbin) of a fold-mode PSRFITS archive with
+    their scales and offsets (nsub, npol, nchan) (psrfits.load_quantised); the
+    cleaned cube is polarisation 0 (nsum 1) or pol 0 + pol 1 (nsum 2) of their
+    decode, made on the GPU.  The ring then holds the first `nsum`
+    polarisations as page-locked int16 in the byte order of the loader's first
+    item ('>i2' as stored, or native): half the bytes of an f32 cube cross the
+    bus, and none of the polarisations the loop never reads."""
+    nsum = int(nsum)
+    if quantised and nsum not in (1, 2):
+        raise ValueError("nsum must be 1 or 2")
     nsub, nchan, nbin = (int(x) for x in shape)
     lanes = int(lanes)
     if lanes < 1:
@@ -227,18 +260,39 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     full = queue.Queue(maxsize=ring)
     stop = threading.Event()
     error = []
-    rg = _Ring(ring, nsub, nchan, nbin)
+    rings = [] if quantised else [_Ring(ring, nsub, nchan, nbin)]   # quantised: made for the first item's byte order
     for i in range(ring):
         free.put(i)
 
+    def stage_quantised(i, q, scl, offs):
+        q = np.asarray(q)
+        if q.ndim == 3:
+            q = q.reshape(nsub, 1, nchan, nbin)
+        if q.dtype.kind != "i" or q.dtype.itemsize != 2:
+            raise ValueError("quantised samples must be int16 (native or '>i2'), got %s" % q.dtype)
+        if q.ndim != 4 or q.shape[0] != nsub or q.shape[2:] != (nchan, nbin) or q.shape[1] < nsum:
+            raise ValueError("quantised samples %s != (%d, npol >= %d, %d, %d)" % (q.shape, nsub, nsum, nchan, nbin))
+        if not rings:
+            rings.append(_Ring(ring, nsub, nchan, nbin, (nsum, q.dtype)))
+        dq, dscl, doffs = rings[0].arrays(i)[:3]
+        np.copyto(dq, q[:, :nsum])   # (a later item in the other byte order is converted to the ring's)
+        npol = q.shape[1]
+        np.copyto(dscl, np.asarray(scl, np.float32).reshape(nsub, npol, nchan)[:, :nsum])
+        np.copyto(doffs, np.asarray(offs, np.float32).reshape(nsub, npol, nchan)[:, :nsum])
+
     def load():
         try:
-            for cube, w0, shift in loader:
+            for item in loader:
                 i = free.get()
                 if stop.is_set():
                     return
-                c, w, s = rg.arrays(i)
-                np.copyto(c, np.asarray(cube, np.float32).reshape(nsub, nchan, nbin))
+                if quantised:
+                    q, scl, offs, w0, shift = item
+                    stage_quantised(i, q, scl, offs)
+                else:
+                    cube, w0, shift = item
+                    np.copyto(rings[0].arrays(i)[0], np.asarray(cube, np.float32).reshape(nsub, nchan, nbin))
+                w, s = rings[0].arrays(i)[-2:]
                 np.copyto(w, np.asarray(w0, np.float32).reshape(nsub, nchan))
                 np.copyto(s, np.mod(np.asarray(shift), nbin).astype(np.int32).reshape(nchan))
                 full.put(i)
@@ -256,7 +310,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             if i is None:
                 return
             order.append(i)
-            yield rg.arrays(i)
+            yield rings[0].arrays(i)
 
     order = []
     sessions = []
@@ -265,7 +319,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
         for _ in range(lanes):
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
                                                pulse_region, baseline_duty, device=device))
-        lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout)
+        lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
             yield out
@@ -281,6 +335,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
         for sess in sessions:
             sess.close()
         if any(getattr(sess, "_ic_leaked", False) for sess in sessions):
-            _LEAKED.append(rg)          # a leaked lane's copies may still read the page-locked ring
+            _LEAKED.extend(rings)       # a leaked lane's copies may still read the page-locked ring
         else:
-            rg.close()
+            for rg in rings:
+                rg.close()

@@ -175,6 +175,21 @@ def _loop_input(ar) -> np.ndarray:
     return cube
 
 
+def _quantised_input(ar):
+    """(q, scl, offs, nsum) when the archive still holds exactly the decoded
+    int16 samples of its PSRFITS file (Archive.get_quantised): the loop's input
+    is then uploaded as stored and decoded on the GPU (ic_upload_quantised),
+    nsum by _loop_input's rule - pol 0 for one polarisation or Stokes data,
+    else pol 0 + pol 1.  None for every other archive."""
+    get = getattr(ar, "get_quantised", None)
+    quant = get() if get is not None else None
+    if quant is None:
+        return None
+    q, scl, offs = quant
+    nsum = 1 if q.shape[1] == 1 or _state(ar) == "Stokes" else 2
+    return q, scl, offs, nsum
+
+
 def _data_f64(ar) -> bool:
     """True when the archive binding's get_data returns f64 (a psrchive build;
     the masked statistics then run in f64: ic_params.data_f64)."""
@@ -192,19 +207,25 @@ def _device() -> int:
 
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
-             data_f64=False, delay=None, input_dedispersed=False):
+             data_f64=False, delay=None, input_dedispersed=False, quantised=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
-    (+ ``residual`` when requested).  Under channel sharding (dist.channel_sharding)
+    (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
+    ``cube`` None: the PSRFITS int16 samples (nsub, npol, nchan, nbin) and their
+    scales / offsets, decoded and pscrunched on the GPU (unsharded runs only).  Under channel sharding (dist.channel_sharding)
     every rank runs its channel shard and gets the merged result: `cube` is then
     either the whole archive (sliced here) or, with ``nchan_total`` set, already
     this rank's channel slice (read slice-only from the file).  ``delay``:
     fractional delays, (nchan,) or (nsub, nchan) (dedispersion by FFT phase
     rotation); ``input_dedispersed``: the cube is stored dedispersed (FFT
     dedispersion only)."""
+    from .dist import channel_sharding
+    if quantised is not None:
+        if cube is not None or channel_sharding():
+            raise ValueError("quantised input takes no f32 cube and no channel sharding")
+        cube = quantised[0]
     pols = cube.ndim == 4
     nsub, nchan, nbin = (cube.shape[0], cube.shape[2], cube.shape[3]) if pols else cube.shape
-    from .dist import channel_sharding
     if channel_sharding():
         import torch
 
@@ -231,7 +252,9 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
                             args.pulse_region, baseline_duty,
                             device=_device() if device is None else device, data_f64=data_f64, delay=delay,
                             input_dedispersed=input_dedispersed) as s:
-        if pols:
+        if quantised is not None:
+            s.upload_quantised(quantised[0], quantised[1], quantised[2], w0, shift, quantised[3])
+        elif pols:
             s.upload_pols(cube, w0, shift)
         else:
             s.upload(cube, w0, shift)
@@ -315,15 +338,24 @@ def clean(ar, args, arch):
     if not args.quiet:
         print("Total number of profiles: %s" % size)
 
-    cube = _loop_input(ar)
     shift, delay = _dedispersion(ar)
     stored_ded = _stored_dedispersed(ar)
-    if stored_ded and delay is None:
-        cube = _to_dispersed(cube, shift)
+    f64 = _data_f64(ar)
+    # the int16 samples of a PSRFITS archive go to the GPU as stored; not f64
+    # data, not a channel shard, and not an archive stored dedispersed with
+    # integer shifts (the host rolls that one back to the dispersed frame)
+    quant = None
+    if not f64 and not sharding and not chan_slice and not (stored_ded and delay is None):
+        quant = _quantised_input(ar)
+    cube = None
+    if quant is None:
+        cube = _loop_input(ar)
+        if stored_ded and delay is None:
+            cube = _to_dispersed(cube, shift)
     duty = ar.get_baseline_duty() if hasattr(ar, "get_baseline_duty") else 0.15
     out = run_loop(cube, orig_weights, shift, args, want_residual=args.unload_res, baseline_duty=duty,
-                   nchan_total=nchan_total, data_f64=_data_f64(ar), delay=delay,
-                   input_dedispersed=stored_ded and delay is not None)
+                   nchan_total=nchan_total, data_f64=f64, delay=delay,
+                   input_dedispersed=stored_ded and delay is not None, quantised=quant)
     del cube
 
     x = 0

@@ -172,6 +172,12 @@ hipError_t launch_base(hipStream_t st, const float *raw, const int32_t *shift, c
                        const int32_t *flags, int nsub, int nchan, int nbin, int width, float *base);
 // total intensity in place: raw[i] = f32(raw[i] + pol1[i])  (archive.py pscrunch)
 hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n);
+// PSRFITS int16 samples q [nsub][nsum][nchan][nbin] (big_endian: as FITS stores
+// them) with scl / offs [nsub][nsum][nchan] -> raw [nsub][nchan][nbin]:
+// f32(f32(q) * scl + offs), the two polarisations added for nsum 2 (psrfits.py
+// decode, archive.py pscrunch)
+hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, const float *offs, int nsub, int nchan,
+                           int nbin, int nsum, bool big_endian, float *raw);
 // num (s, leaf, i) = part[s*ss + leaf*sl + i], weight (s, leaf) = wpart[s*wss + leaf*wsl]
 hipError_t launch_fscrunch(hipStream_t st, const double *part, long ss, long sl, const double *wpart, long wss,
                            long wsl, const SbPlan &plan, int nsub, int nbin, float *F, float *wf);

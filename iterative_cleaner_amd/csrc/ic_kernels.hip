@@ -656,6 +656,88 @@ __global__ __launch_bounds__(256) void k_pscrunch(float *__restrict__ raw, const
         raw[i] = raw[i] + pol1[i];
 }
 
+// PSRFITS fold-mode decode on the device (psrfits.py decode + archive.py
+// pscrunch): q [nsub][nsum][nchan][nbin] int16, scl / offs [nsub][nsum][nchan],
+// raw [nsub][nchan][nbin] = f32(f32(q0) * scl0 + offs0) (nsum 1) or the f32 sum
+// of the two polarisations' decoded values (nsum 2).  Multiply, add and
+// polarisation add are three separate IEEE roundings whatever -ffp-contract says.
+__device__ __forceinline__ float q_decode(int q, float scl, float offs)
+{
+    return __fadd_rn(__fmul_rn((float)q, scl), offs);
+}
+
+// two samples of one 32-bit word (the first in the low half), native order
+template <bool BE>
+__device__ __forceinline__ void q_pair(uint32_t w, int &lo, int &hi)
+{
+    if (BE) w = ((w & 0x00ff00ffu) << 8) | ((w >> 8) & 0x00ff00ffu);
+    lo = (int)(int16_t)(w & 0xffffu);
+    hi = (int)(int16_t)(w >> 16);
+}
+
+template <bool BE>
+__device__ __forceinline__ void q_decode8(const uint4 v, float scl, float offs, float *o)
+{
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int lo, hi;
+        q_pair<BE>(w[j], lo, hi);
+        o[2 * j] = q_decode(lo, scl, offs);
+        o[2 * j + 1] = q_decode(hi, scl, offs);
+    }
+}
+
+// nbin % 8 == 0: a lane takes 8 consecutive samples of one profile (one 16-byte
+// load per polarisation, two 16-byte stores); gpp = nbin / 8 groups per
+// profile, I wide enough for NSUM * ngroups
+template <bool BE, int NSUM, typename I>
+__global__ __launch_bounds__(256) void k_decode_q(const int16_t *__restrict__ q, const float *__restrict__ scl,
+                                                  const float *__restrict__ offs, float *__restrict__ raw, I ngroups,
+                                                  I gpp, I nchan)
+{
+    const uint4 *q4 = (const uint4 *)q;
+    float4 *r4 = (float4 *)raw;
+    for (I g = (I)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (I)gridDim.x * 256) {
+        const I p = g / gpp;                                         // output profile s * nchan + c
+        const I pq = NSUM == 2 ? p + (p / nchan) * nchan : p;        // (s, pol 0, c) in q's profile order
+        const I gq = pq * gpp + (g - p * gpp);
+        float a[8];
+        q_decode8<BE>(q4[gq], scl[pq], offs[pq], a);
+        if (NSUM == 2) {
+            float b[8];
+            q_decode8<BE>(q4[gq + nchan * gpp], scl[pq + nchan], offs[pq + nchan], b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a[j] = __fadd_rn(a[j], b[j]);
+        }
+        r4[2 * (size_t)g] = make_float4(a[0], a[1], a[2], a[3]);
+        r4[2 * (size_t)g + 1] = make_float4(a[4], a[5], a[6], a[7]);
+    }
+}
+
+// any nbin: one sample per lane and step, the profile index per sample
+template <bool BE, int NSUM>
+__global__ __launch_bounds__(256) void k_decode_q_scalar(const int16_t *__restrict__ q, const float *__restrict__ scl,
+                                                         const float *__restrict__ offs, float *__restrict__ raw,
+                                                         size_t n, size_t nbin, size_t nchan)
+{
+    const uint16_t *qu = (const uint16_t *)q;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t p = i / nbin;
+        const size_t pq = NSUM == 2 ? p + (p / nchan) * nchan : p;
+        const size_t iq = pq * nbin + (i - p * nbin);
+        float a = 0.0f;
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) {
+            uint32_t w = qu[iq + k * nchan * nbin];
+            if (BE) w = ((w & 0xffu) << 8) | (w >> 8);
+            const float d = q_decode((int)(int16_t)w, scl[pq + k * nchan], offs[pq + k * nchan]);
+            a = k == 0 ? d : __fadd_rn(a, d);
+        }
+        raw[i] = a;
+    }
+}
+
 // F[s][i] = f32(num/wsum) (0 if wsum == 0); wf[s] = f32(wsum); num and wsum
 // are the canonical trees over the leaves
 __global__ __launch_bounds__(256) void k_fscrunch(const double *__restrict__ part, long ss, long sl,
@@ -5170,6 +5252,44 @@ hipError_t launch_base(hipStream_t st, const float *raw, const int32_t *shift, c
 hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n)
 {
     IC_GGL(k_pscrunch, dim3(std::min<unsigned>(cdiv(n / 4 + 1, 256), 8192)), dim3(256), 0, st, raw, pol1, n);
+    return hipGetLastError();
+}
+
+namespace {
+template <bool BE, int NSUM>
+void decode_q_dispatch(hipStream_t st, const int16_t *q, const float *scl, const float *offs, size_t P, int nchan,
+                       int nbin, float *raw)
+{
+    const size_t n = P * (size_t)nbin;
+    if (nbin % 8 == 0 && (((uintptr_t)q | (uintptr_t)raw) & 15) == 0) {
+        const size_t ng = n / 8;
+        const dim3 grid((unsigned)std::min<size_t>(cdiv(ng, 256), 8192));
+        if (ng * NSUM < ((size_t)1 << 31))
+            IC_GGL((k_decode_q<BE, NSUM, uint32_t>), grid, dim3(256), 0, st, q, scl, offs, raw, (uint32_t)ng,
+                   (uint32_t)(nbin / 8), (uint32_t)nchan);
+        else
+            IC_GGL((k_decode_q<BE, NSUM, size_t>), grid, dim3(256), 0, st, q, scl, offs, raw, ng, (size_t)(nbin / 8),
+                   (size_t)nchan);
+    } else {
+        const dim3 grid((unsigned)std::min<size_t>(cdiv(n, 256), 65536));
+        IC_GGL((k_decode_q_scalar<BE, NSUM>), grid, dim3(256), 0, st, q, scl, offs, raw, n, (size_t)nbin,
+               (size_t)nchan);
+    }
+}
+}  // namespace
+
+hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, const float *offs, int nsub, int nchan,
+                           int nbin, int nsum, bool big_endian, float *raw)
+{
+    if (nsub < 1 || nchan < 1 || nbin < 1 || (nsum != 1 && nsum != 2)) return hipErrorInvalidValue;
+    const size_t P = (size_t)nsub * nchan;
+    if (nsum == 2) {
+        if (big_endian) decode_q_dispatch<true, 2>(st, q, scl, offs, P, nchan, nbin, raw);
+        else decode_q_dispatch<false, 2>(st, q, scl, offs, P, nchan, nbin, raw);
+    } else {
+        if (big_endian) decode_q_dispatch<true, 1>(st, q, scl, offs, P, nchan, nbin, raw);
+        else decode_q_dispatch<false, 1>(st, q, scl, offs, P, nchan, nbin, raw);
+    }
     return hipGetLastError();
 }
 

@@ -109,6 +109,13 @@ struct Session {
     float *slot_raw[2] = {nullptr, nullptr}, *slot_w0[2] = {nullptr, nullptr};
     int32_t *slot_shift[2] = {nullptr, nullptr};
     hipEvent_t slot_ev[2] = {nullptr, nullptr};
+    // quantised uploads (ic_upload_quantised*): per input slot the int16 samples
+    // [nsub][nsum][nchan][nbin] and scl then offs [nsub][nsum][nchan] each, decoded
+    // into slot_raw; allocated by the first such upload into the slot for its nsum
+    // (slot_qsum), regrown for a larger one
+    int16_t *slot_q[2] = {nullptr, nullptr};
+    float *slot_so[2] = {nullptr, nullptr};
+    int slot_qsum[2] = {0, 0};
     hipStream_t copy_stream = nullptr;
     int cur = 0, fifo[2] = {0, 0}, fifo_n = 0;
     bool ever_uploaded = false;
@@ -400,7 +407,7 @@ int collect_timing(Session *s)
 void free_all(Session *s)
 {
     for (int q = 0; q < 2; ++q) {
-        void *sb[] = {s->slot_raw[q], s->slot_w0[q], s->slot_shift[q]};
+        void *sb[] = {s->slot_raw[q], s->slot_w0[q], s->slot_shift[q], s->slot_q[q], s->slot_so[q]};
         for (void *b : sb)
             if (b) (void)hipFree(b);
         if (s->slot_ev[q]) (void)hipEventDestroy(s->slot_ev[q]);
@@ -1442,6 +1449,147 @@ int ic_upload_async(void *session, const float *cube, const float *w0, const int
     CK(hipEventRecord(s->slot_ev[target], s->copy_stream));
     s->fifo[s->fifo_n++] = target;
     s->ever_uploaded = true;
+    return IC_OK;
+}
+
+// arguments shared by the quantised entry points
+static int q_check_args(const void *q, const float *scl, const float *offs, int npol, int nsum, int flags)
+{
+    if (!q || !scl || !offs) return fail(IC_EINVAL, "null argument");
+    if (npol < 1) return fail(IC_EINVAL, "npol=%d", npol);
+    if (nsum != 1 && nsum != 2) return fail(IC_EINVAL, "nsum=%d (1: pol 0, 2: pol 0 + pol 1)", nsum);
+    if (nsum > npol) return fail(IC_EINVAL, "nsum=%d > npol=%d", nsum, npol);
+    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    return IC_OK;
+}
+
+// the first nsum polarisations of every subint of host[nsub][npol][row bytes]
+// -> dev[nsub][nsum][row bytes]
+static hipError_t q_copy_pols(void *dev, const void *host, size_t row, int nsub, int npol, int nsum, hipStream_t st)
+{
+    if (nsum == npol) return hipMemcpyAsync(dev, host, row * nsum * nsub, hipMemcpyHostToDevice, st);
+    return hipMemcpy2DAsync(dev, row * nsum, host, row * npol, row * nsum, nsub, hipMemcpyHostToDevice, st);
+}
+
+// staging of one slot for nsum polarisations.  A slot being (re)allocated holds
+// no pending upload and the decode of any earlier one has been waited for by
+// the ic_run that consumed it, so freeing the smaller staging is safe.
+static int q_stage(Session *s, int slot, int nsum)
+{
+    if (s->slot_qsum[slot] >= nsum) return IC_OK;
+    if (s->slot_q[slot]) (void)hipFree(s->slot_q[slot]);
+    if (s->slot_so[slot]) (void)hipFree(s->slot_so[slot]);
+    s->slot_q[slot] = nullptr;
+    s->slot_so[slot] = nullptr;
+    s->slot_qsum[slot] = 0;
+    if (dalloc(&s->slot_q[slot], s->N * nsum) != hipSuccess || dalloc(&s->slot_so[slot], s->P * 2 * nsum) != hipSuccess) {
+        if (s->slot_q[slot]) (void)hipFree(s->slot_q[slot]);
+        s->slot_q[slot] = nullptr;
+        s->slot_so[slot] = nullptr;
+        return fail(IC_ENOMEM, "quantised staging (%zu bytes) failed",
+                    (size_t)nsum * (sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P));
+    }
+    s->slot_qsum[slot] = nsum;
+    return IC_OK;
+}
+
+// copies and decode of one quantised archive into input slot `slot`, on `st`
+static int q_enqueue(Session *s, int slot, hipStream_t st, const int16_t *q, const float *scl, const float *offs,
+                     int npol, int nsum, int flags, const float *w0, const int32_t *shift)
+{
+    const int nsub = s->p.nsub, nchan = s->nchan, nbin = s->p.nbin;
+    float *dscl = s->slot_so[slot], *doffs = dscl + s->P * nsum;
+    CK(q_copy_pols(s->slot_q[slot], q, sizeof(int16_t) * (size_t)nchan * nbin, nsub, npol, nsum, st));
+    CK(q_copy_pols(dscl, scl, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st));
+    CK(q_copy_pols(doffs, offs, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st));
+    CK(launch_decode_q(st, s->slot_q[slot], dscl, doffs, nsub, nchan, nbin, nsum, (flags & IC_Q_BIG_ENDIAN) != 0,
+                       s->slot_raw[slot]));
+    CK(hipMemcpyAsync(s->slot_w0[slot], w0, sizeof(float) * s->P, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(s->slot_shift[slot], shift, sizeof(int32_t) * nchan, hipMemcpyHostToDevice, st));
+    return IC_OK;
+}
+
+int ic_upload_quantised(void *session, const int16_t *q, const float *scl, const float *offs, int npol, int nsum,
+                        int flags, const float *w0, const int32_t *shift)
+{
+    Session *s = (Session *)session;
+    if (!s || !w0 || !shift) return fail(IC_EINVAL, "null argument");
+    if (int rc = q_check_args(q, scl, offs, npol, nsum, flags)) return rc;
+    if (s->failed) return failed_session();
+    if (s->fifo_n) return fail(IC_ESTATE, "ic_upload_quantised with %d asynchronous upload(s) pending", s->fifo_n);
+    CK(hipSetDevice(s->device));
+    for (int c = 0; c < s->nchan; ++c)
+        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = q_stage(s, s->cur, nsum)) return rc;
+    s->ever_uploaded = true;
+    if (int rc = q_enqueue(s, s->cur, s->stream, q, scl, offs, npol, nsum, flags, w0, shift)) return rc;
+    CK(hipStreamSynchronize(s->stream));
+    s->uploaded = true;
+    s->ran = false;
+    return IC_OK;
+}
+
+int ic_upload_quantised_async(void *session, const int16_t *q, const float *scl, const float *offs, int npol, int nsum,
+                              int flags, const float *w0, const int32_t *shift)
+{
+    Session *s = (Session *)session;
+    if (!s || !w0 || !shift) return fail(IC_EINVAL, "null argument");
+    if (int rc = q_check_args(q, scl, offs, npol, nsum, flags)) return rc;
+    if (s->failed) return failed_session();
+    if (s->fifo_n == 2) return fail(IC_ESTATE, "two asynchronous uploads already pending (run one first)");
+    for (int c = 0; c < s->nchan; ++c)
+        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    CK(hipSetDevice(s->device));
+    // the slot rule of ic_upload_async
+    const int target = s->fifo_n ? 1 - s->fifo[s->fifo_n - 1] : (s->ever_uploaded ? 1 - s->cur : s->cur);
+    if (!s->slot_raw[target]) {
+        if (dalloc(&s->slot_raw[target], s->N) != hipSuccess || dalloc(&s->slot_w0[target], s->P) != hipSuccess ||
+            dalloc(&s->slot_shift[target], (size_t)s->nchan) != hipSuccess)
+            return fail(IC_ENOMEM, "second input slot (%zu bytes) failed", sizeof(float) * (s->N + s->P));
+    }
+    if (int rc = q_stage(s, target, nsum)) return rc;
+    if (!s->copy_stream) CK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    if (!s->slot_ev[target]) CK(hipEventCreateWithFlags(&s->slot_ev[target], hipEventDisableTiming));
+    // the decode runs on the copy stream behind its copies and slot_ev follows
+    // it: ic_run waits for a decoded cube as it waits for an f32 copy
+    if (int rc = q_enqueue(s, target, s->copy_stream, q, scl, offs, npol, nsum, flags, w0, shift)) return rc;
+    CK(hipEventRecord(s->slot_ev[target], s->copy_stream));
+    s->fifo[s->fifo_n++] = target;
+    s->ever_uploaded = true;
+    return IC_OK;
+}
+
+int ic_decode_profiles(int device, int nsub, int npol, int nsum, int nchan, int nbin, const int16_t *q,
+                       const float *scl, const float *offs, int flags, float *out)
+{
+    if (!out) return fail(IC_EINVAL, "null argument");
+    if (int rc = q_check_args(q, scl, offs, npol, nsum, flags)) return rc;
+    if (nsub <= 0 || nchan <= 0 || nbin <= 0) return fail(IC_EINVAL, "bad shape (%d, %d, %d)", nsub, nchan, nbin);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    CK(hipSetDevice(device));
+    const size_t P = (size_t)nsub * nchan, N = P * nbin;
+    int16_t *dq = nullptr;
+    float *dso = nullptr, *d = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&dq, sizeof(int16_t) * N * nsum);
+    if (e == hipSuccess) e = hipMalloc((void **)&dso, sizeof(float) * P * 2 * nsum);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, sizeof(float) * N);
+    if (e == hipSuccess) e = q_copy_pols(dq, q, sizeof(int16_t) * (size_t)nchan * nbin, nsub, npol, nsum, st);
+    if (e == hipSuccess) e = q_copy_pols(dso, scl, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st);
+    if (e == hipSuccess) e = q_copy_pols(dso + P * nsum, offs, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st);
+    if (e == hipSuccess)
+        e = launch_decode_q(st, dq, dso, dso + P * nsum, nsub, nchan, nbin, nsum, (flags & IC_Q_BIG_ENDIAN) != 0, d);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(float) * N, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (dq) (void)hipFree(dq);
+    if (dso) (void)hipFree(dso);
+    if (d) (void)hipFree(d);
+    if (st) (void)hipStreamDestroy(st);
+    if (e == hipErrorOutOfMemory) return fail(IC_ENOMEM, "ic_decode_profiles: device allocation failed");
+    if (e != hipSuccess) return fail(IC_EHIP, "ic_decode_profiles: %s", hipGetErrorString(e));
     return IC_OK;
 }
 

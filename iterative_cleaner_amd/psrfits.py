@@ -250,11 +250,9 @@ def probe_shape(path: str):
             fh.seek(n + (-n % BLOCK), 1)
 
 
-def load(path: str, channels=None):
-    """Read a fold-mode PSRFITS archive.  channels = (c0, c1): only those
-    channels; the SUBINT table is memory-mapped, so the other channels' samples
-    are never read (channel-sharded cleaning)."""
-    from .archive import Archive
+def _read_subint(path: str, channels, native: bool) -> dict:
+    """The SUBINT table's columns and keywords as load() and load_quantised()
+    use them; native: the int16 samples in host byte order (else as stored)."""
     with open(path, "rb") as fh:
         primary = _read_header(fh)
         if not primary or primary.get("SIMPLE") is not True:
@@ -279,7 +277,7 @@ def load(path: str, channels=None):
     if not 0 <= c0 < c1 <= nchan_total:
         raise ValueError("%s: channel range %s outside [0, %d)" % (path, (c0, c1), nchan_total))
     nchan = c1 - c0
-    q = np.array(rows["DATA"].reshape(nsub, npol, nchan_total, nbin)[:, :, c0:c1], np.int16)
+    q = np.array(rows["DATA"].reshape(nsub, npol, nchan_total, nbin)[:, :, c0:c1], np.int16 if native else None)
     scl = np.array(rows["DAT_SCL"].reshape(nsub, npol, nchan_total)[:, :, c0:c1], np.float32)
     offs = np.array(rows["DAT_OFFS"].reshape(nsub, npol, nchan_total)[:, :, c0:c1], np.float32)
     weights = np.array(rows["DAT_WTS"].reshape(nsub, nchan_total)[:, c0:c1], np.float32)
@@ -312,17 +310,51 @@ def load(path: str, channels=None):
     if state is not None and (state == "Intensity") != (npol == 1):
         state = None          # inconsistent header: fall back on the npol default
     del rows
-    ar = Archive(decode(q, scl, offs), weights, shift, dedispersed=bool(hdr.get("IC_DEDSP", False)),
+    return dict(q=q, scl=scl, offs=offs, weights=weights, shift=shift, frac=frac, freqs=freqs, period=period,
+                cfreq=cfreq, dm=dm, mjd0=mjd0, state=state, primary=primary, hdr=hdr, c0=c0, c1=c1,
+                nchan_total=nchan_total)
+
+
+def load(path: str, channels=None):
+    """Read a fold-mode PSRFITS archive.  channels = (c0, c1): only those
+    channels; the SUBINT table is memory-mapped, so the other channels' samples
+    are never read (channel-sharded cleaning)."""
+    from .archive import Archive
+    t = _read_subint(path, channels, True)
+    q, scl, offs, primary, hdr, mjd0, period = (t[k] for k in ("q", "scl", "offs", "primary", "hdr", "mjd0", "period"))
+    ar = Archive(decode(q, scl, offs), t["weights"], t["shift"], dedispersed=bool(hdr.get("IC_DEDSP", False)),
                  filename=path, source=str(primary.get("SRC_NAME", "J0000+0000")),
-                 centre_frequency=cfreq, mjd_start=mjd0,
+                 centre_frequency=t["cfreq"], mjd_start=mjd0,
                  mjd_end=float(hdr.get("IC_MJDE", mjd0 + 0.01)),
-                 baseline_duty=float(hdr.get("IC_DUTY", 0.15)), state=state, dm_delay=frac)
+                 baseline_duty=float(hdr.get("IC_DUTY", 0.15)), state=t["state"], dm_delay=t["frac"])
     if channels is not None:
-        ar._chan_range = (c0, c1)
-        ar._nchan_total = nchan_total
+        ar._chan_range = (t["c0"], t["c1"])
+        ar._nchan_total = t["nchan_total"]
     ar._psrfits_q = (q, scl, offs)
+    ar._q_exact = True       # Archive.get_quantised: the samples are decode(q, scl, offs)
     ar._format = "PSRFITS"
-    ar._chan_freqs = freqs
+    ar._chan_freqs = t["freqs"]
     ar._period = period if np.any(period != period[:1]) else float(period[0])
-    ar._dm = dm
+    ar._dm = t["dm"]
     return ar
+
+
+def load_quantised(path: str, channels=None):
+    """The samples of a fold-mode PSRFITS archive as the file stores them, for
+    GpuSession.upload_quantised[_async] and batch loaders: the f32 cube is never
+    formed.  Returns (q, scl, offs, weights, shift, meta): q int16 (nsub, npol,
+    nchan, nbin) in the FITS (big-endian) byte order, dtype '>i2'; scl / offs
+    f32 (nsub, npol, nchan); weights f32 (nsub, nchan) and shift int64 (nchan,),
+    the values load() gives its archive; meta: the state ('Intensity', 'PPQQ',
+    'Coherence' or 'Stokes'), dedispersed, baseline_duty, delay (the
+    fractional delays or None), npol and source."""
+    t = _read_subint(path, channels, False)
+    q = t["q"]
+    nsub, npol, nchan, nbin = q.shape
+    hdr = t["hdr"]
+    from .archive import default_state
+    meta = dict(state=t["state"] or default_state(npol), dedispersed=bool(hdr.get("IC_DEDSP", False)),
+                baseline_duty=float(hdr.get("IC_DUTY", 0.15)), delay=t["frac"], npol=npol,
+                source=str(t["primary"].get("SRC_NAME", "J0000+0000")))
+    return (q, t["scl"], t["offs"], t["weights"],
+            np.mod(np.asarray(t["shift"], dtype=np.int64), nbin).reshape(nchan), meta)

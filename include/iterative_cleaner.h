@@ -309,6 +309,11 @@ int ic_get_run_stats(void *session, ic_run_stats *out);
  *                          same kernel (the rotated residual never goes to
  *                          HBM), 0 = it writes them and a statistics pass reads
  *                          them back; 1
+ *   IC_OPT_GRID_CAP        a test and tuning knob: the most blocks a kernel
+ *                          that walks its profiles (or samples) in a grid-stride
+ *                          loop is launched with, 1..65536, 0 = the launchers'
+ *                          own grids; 0.  A small cap makes a small archive take
+ *                          every such loop through many trips per block.
  *   IC_OPT_SYNC_TIMEOUT_MS longest host wait for the GPU, >= 1 ms; 600000.  A
  *                          wait that runs out fails its call with IC_EHIP and
  *                          marks the session failed: every later call on it
@@ -329,6 +334,7 @@ int ic_get_run_stats(void *session, ic_run_stats *out);
  * with the lanes schedule) */
 #define IC_OPT_TAIL_SPLIT 13
 #define IC_OPT_ROT_STATS 14
+#define IC_OPT_GRID_CAP 15
 #define IC_TAIL_SPLIT_OFF 0
 #define IC_TAIL_SPLIT_ON 1
 #define IC_TAIL_SPLIT_AUTO 2

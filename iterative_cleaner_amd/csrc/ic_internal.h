@@ -140,6 +140,15 @@ struct LineStatsArgs {
     int grp_waves = 8, grp_minlen = 1024;
 };
 
+// Grid cap (session option IC_OPT_GRID_CAP): the launchers whose grid is
+// min(blocks the work needs, a constant) launch min(that, grid_cap) blocks when
+// grid_cap > 0, so that a small archive drives every grid-stride loop through
+// many trips.  0 = the grids as they are.
+inline unsigned cap_grid(size_t grid, int grid_cap)
+{
+    return (unsigned)(grid_cap > 0 && grid > (size_t)grid_cap ? (size_t)grid_cap : grid);
+}
+
 // ---- launch wrappers (ic_kernels.hip); all asynchronous on `st` ----
 // mode 0: part = sum W*ded; 1: part2 = sum W*f32(ded-base) + wpart; 2: both;
 // 3: mode 1 + the fit cube D[k][i] = f32(ded-base) (row stride ldD).
@@ -169,15 +178,15 @@ hipError_t launch_window(hipStream_t st, const double *part, long ss, long sl, c
 size_t window_lds_bytes(int nbin);
 // flags != nullptr: only subints with flags[s] != 0
 hipError_t launch_base(hipStream_t st, const float *raw, const int32_t *shift, const int32_t *win,
-                       const int32_t *flags, int nsub, int nchan, int nbin, int width, float *base);
+                       const int32_t *flags, int nsub, int nchan, int nbin, int width, float *base, int grid_cap = 0);
 // total intensity in place: raw[i] = f32(raw[i] + pol1[i])  (archive.py pscrunch)
-hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n);
+hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n, int grid_cap = 0);
 // PSRFITS int16 samples q [nsub][nsum][nchan][nbin] (big_endian: as FITS stores
 // them) with scl / offs [nsub][nsum][nchan] -> raw [nsub][nchan][nbin]:
 // f32(f32(q) * scl + offs), the two polarisations added for nsum 2 (psrfits.py
 // decode, archive.py pscrunch)
 hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, const float *offs, int nsub, int nchan,
-                           int nbin, int nsum, bool big_endian, float *raw);
+                           int nbin, int nsum, bool big_endian, float *raw, int grid_cap = 0);
 // num (s, leaf, i) = part[s*ss + leaf*sl + i], weight (s, leaf) = wpart[s*wss + leaf*wsl]
 hipError_t launch_fscrunch(hipStream_t st, const double *part, long ss, long sl, const double *wpart, long wss,
                            long wsl, const SbPlan &plan, int nsub, int nbin, float *F, float *wf);
@@ -195,10 +204,10 @@ hipError_t launch_unpack_fscrunch(hipStream_t st, const ShardGeom &g, int rows_p
 // (valid == true: the single u8 field `valid` instead)
 hipError_t launch_pack_rows(hipStream_t st, const ShardGeom &g, int nchan_loc, const double *std_d,
                             const double *mean_d, const double *fft_d, const double *ptp_d, const uint8_t *valid,
-                            unsigned char *send);
+                            unsigned char *send, int grid_cap = 0);
 // per-source blocks -> owned rows [rows_own][nchan_g] of each field
 hipError_t launch_assemble_rows(hipStream_t st, const ShardGeom &g, const unsigned char *recv, double *std_r,
-                                double *mean_r, double *fft_r, double *ptp_r, uint8_t *valid_r);
+                                double *mean_r, double *fft_r, double *ptp_r, uint8_t *valid_r, int grid_cap = 0);
 // gathered [world][8 * rows_pad] (rank p: med [4][rows_p], mad [4][rows_p]) -> row_med/row_mad [4][nsub]
 hipError_t launch_unpack_rowstats(hipStream_t st, const ShardGeom &g, int rows_pad, const double *recv,
                                   double *row_med, double *row_mad);
@@ -239,7 +248,8 @@ hipError_t launch_fit_state(hipStream_t st, const FitStateArrays &S, long P, con
                             uint8_t *late = nullptr);
 hipError_t launch_fit_tail(hipStream_t st, const float *D, const double *T64, long P, int nbin, int ldD,
                            int dtiled, const int32_t *list, const unsigned long long *nctr, long bound,
-                           const FitStateArrays &S, double *amp, int32_t *info, unsigned long long *sweeps);
+                           const FitStateArrays &S, double *amp, int32_t *info, unsigned long long *sweeps,
+                           int grid_cap = 0);
 // Diagnostics kernels (k_diag_p2<N> for power-of-two nbin 64..4096, k_diag
 // otherwise).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
 // the fit cube D (row stride ldD); DIAG_CLOSED = fit_mode 1, the closed-form
@@ -276,6 +286,7 @@ struct DiagArgs {
     const unsigned long long *nctr = nullptr;
     const uint8_t *skip = nullptr;   // != nullptr: profiles with skip[k] != 0 are left out
     int chain = 1;   // 0: the row-layout k_diag_p2 at nbin 1024/2048/4096 too (IC_OPT_DIAG_CHAIN)
+    int grid_cap = 0;   // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
 };
 hipError_t launch_diag(hipStream_t st, const DiagArgs &a);
 // the diagnostics kernel launch_diag picks for `a` takes a profile list
@@ -297,7 +308,7 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
                           const double *fft_d, const double *col_med, const double *col_mad,
                           const double *row_med, const double *row_mad, double chanthresh,
                           double subintthresh, double *test, float *W, float *hist, int iter,
-                          int32_t *counters);
+                          int32_t *counters, int grid_cap = 0);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
 // bins, n a power of two (<= 8192): the phase rotation's multiplier
 // (phase_rotation.py phasors; oracle orc_phasor).  One fixed sequence of
@@ -415,6 +426,7 @@ struct RotateArgs {
     const float *w0;
     const double2 *tw_p2;       // k_diag_p2's twiddle table (p2_twiddles)
     double *std_o, *mean_o, *ptp_o, *fft_o;
+    int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
 };
 hipError_t launch_rotate(hipStream_t st, const RotateArgs &a);
 bool rotate_supported(int nbin);
@@ -425,6 +437,6 @@ bool rotate_stats_supported(int nbin, bool data_f64);
 hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, const float *base, const double *T64,
                            const double *amp, const int32_t *info, const int32_t *shift, int nsub, int nchan,
                            int nbin, int ldD, int dtiled, int pr_on, double pr_factor, int pr_start, int pr_end,
-                           float *R);
+                           float *R, int grid_cap = 0);
 
 }  // namespace icgpu

@@ -5238,10 +5238,10 @@ hipError_t launch_window(hipStream_t st, const double *part, long ss, long sl, c
 }
 
 hipError_t launch_base(hipStream_t st, const float *raw, const int32_t *shift, const int32_t *win, const int32_t *flags,
-                       int nsub, int nchan, int nbin, int width, float *base)
+                       int nsub, int nchan, int nbin, int width, float *base, int grid_cap)
 {
     const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = (unsigned)std::min<size_t>(cdiv(P, 16), 16384);
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 16), 16384), grid_cap);
     if (nbin % 4 == 0 && ((uintptr_t)raw & 15) == 0 && width <= nbin)
         IC_GGL(k_base<true>, dim3(grid), dim3(256), 0, st, raw, shift, win, flags, nsub, nchan, nbin, width, base);
     else
@@ -5249,21 +5249,22 @@ hipError_t launch_base(hipStream_t st, const float *raw, const int32_t *shift, c
     return hipGetLastError();
 }
 
-hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n)
+hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t n, int grid_cap)
 {
-    IC_GGL(k_pscrunch, dim3(std::min<unsigned>(cdiv(n / 4 + 1, 256), 8192)), dim3(256), 0, st, raw, pol1, n);
+    const unsigned grid = cap_grid(std::min<unsigned>(cdiv(n / 4 + 1, 256), 8192), grid_cap);
+    IC_GGL(k_pscrunch, dim3(grid), dim3(256), 0, st, raw, pol1, n);
     return hipGetLastError();
 }
 
 namespace {
 template <bool BE, int NSUM>
 void decode_q_dispatch(hipStream_t st, const int16_t *q, const float *scl, const float *offs, size_t P, int nchan,
-                       int nbin, float *raw)
+                       int nbin, float *raw, int grid_cap)
 {
     const size_t n = P * (size_t)nbin;
     if (nbin % 8 == 0 && (((uintptr_t)q | (uintptr_t)raw) & 15) == 0) {
         const size_t ng = n / 8;
-        const dim3 grid((unsigned)std::min<size_t>(cdiv(ng, 256), 8192));
+        const dim3 grid(cap_grid(std::min<size_t>(cdiv(ng, 256), 8192), grid_cap));
         if (ng * NSUM < ((size_t)1 << 31))
             IC_GGL((k_decode_q<BE, NSUM, uint32_t>), grid, dim3(256), 0, st, q, scl, offs, raw, (uint32_t)ng,
                    (uint32_t)(nbin / 8), (uint32_t)nchan);
@@ -5271,7 +5272,7 @@ void decode_q_dispatch(hipStream_t st, const int16_t *q, const float *scl, const
             IC_GGL((k_decode_q<BE, NSUM, size_t>), grid, dim3(256), 0, st, q, scl, offs, raw, ng, (size_t)(nbin / 8),
                    (size_t)nchan);
     } else {
-        const dim3 grid((unsigned)std::min<size_t>(cdiv(n, 256), 65536));
+        const dim3 grid(cap_grid(std::min<size_t>(cdiv(n, 256), 65536), grid_cap));
         IC_GGL((k_decode_q_scalar<BE, NSUM>), grid, dim3(256), 0, st, q, scl, offs, raw, n, (size_t)nbin,
                (size_t)nchan);
     }
@@ -5279,16 +5280,16 @@ void decode_q_dispatch(hipStream_t st, const int16_t *q, const float *scl, const
 }  // namespace
 
 hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, const float *offs, int nsub, int nchan,
-                           int nbin, int nsum, bool big_endian, float *raw)
+                           int nbin, int nsum, bool big_endian, float *raw, int grid_cap)
 {
     if (nsub < 1 || nchan < 1 || nbin < 1 || (nsum != 1 && nsum != 2)) return hipErrorInvalidValue;
     const size_t P = (size_t)nsub * nchan;
     if (nsum == 2) {
-        if (big_endian) decode_q_dispatch<true, 2>(st, q, scl, offs, P, nchan, nbin, raw);
-        else decode_q_dispatch<false, 2>(st, q, scl, offs, P, nchan, nbin, raw);
+        if (big_endian) decode_q_dispatch<true, 2>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
+        else decode_q_dispatch<false, 2>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
     } else {
-        if (big_endian) decode_q_dispatch<true, 1>(st, q, scl, offs, P, nchan, nbin, raw);
-        else decode_q_dispatch<false, 1>(st, q, scl, offs, P, nchan, nbin, raw);
+        if (big_endian) decode_q_dispatch<true, 1>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
+        else decode_q_dispatch<false, 1>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
     }
     return hipGetLastError();
 }
@@ -5331,22 +5332,22 @@ hipError_t launch_unpack_fscrunch(hipStream_t st, const ShardGeom &g, int rows_p
 
 hipError_t launch_pack_rows(hipStream_t st, const ShardGeom &g, int nchan_loc, const double *std_d,
                             const double *mean_d, const double *fft_d, const double *ptp_d, const uint8_t *valid,
-                            unsigned char *send)
+                            unsigned char *send, int grid_cap)
 {
     const size_t P = (size_t)g.nsub * nchan_loc;
     if (P == 0) return hipSuccess;
-    IC_GGL(k_pack_rows, dim3(std::min<unsigned>(cdiv(P, 256), 4096)), dim3(256), 0, st, g, nchan_loc,
-                       std_d, mean_d, fft_d, ptp_d, valid, send);
+    const unsigned grid = cap_grid(std::min<unsigned>(cdiv(P, 256), 4096), grid_cap);
+    IC_GGL(k_pack_rows, dim3(grid), dim3(256), 0, st, g, nchan_loc, std_d, mean_d, fft_d, ptp_d, valid, send);
     return hipGetLastError();
 }
 
 hipError_t launch_assemble_rows(hipStream_t st, const ShardGeom &g, const unsigned char *recv, double *std_r,
-                                double *mean_r, double *fft_r, double *ptp_r, uint8_t *valid_r)
+                                double *mean_r, double *fft_r, double *ptp_r, uint8_t *valid_r, int grid_cap)
 {
     const size_t n = (size_t)(g.row0[g.rank + 1] - g.row0[g.rank]) * g.nchan_g;
     if (n == 0) return hipSuccess;
-    IC_GGL(k_assemble_rows, dim3(std::min<unsigned>(cdiv(n, 256), 4096)), dim3(256), 0, st, g, recv,
-                       std_r, mean_r, fft_r, ptp_r, valid_r);
+    const unsigned grid = cap_grid(std::min<unsigned>(cdiv(n, 256), 4096), grid_cap);
+    IC_GGL(k_assemble_rows, dim3(grid), dim3(256), 0, st, g, recv, std_r, mean_r, fft_r, ptp_r, valid_r);
     return hipGetLastError();
 }
 
@@ -5431,11 +5432,12 @@ hipError_t launch_fit_state(hipStream_t st, const FitStateArrays &S, long P, con
 
 hipError_t launch_fit_tail(hipStream_t st, const float *D, const double *T64, long P, int nbin, int ldD,
                            int dtiled, const int32_t *list, const unsigned long long *nctr, long bound,
-                           const FitStateArrays &S, double *amp, int32_t *info, unsigned long long *sweeps)
+                           const FitStateArrays &S, double *amp, int32_t *info, unsigned long long *sweeps,
+                           int grid_cap)
 {
     const long n = list ? bound : P;
     if (n <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<long>(cdiv(n, TAIL_WAVES), 65536);
+    const unsigned grid = cap_grid((size_t)std::min<long>(cdiv(n, TAIL_WAVES), 65536), grid_cap);
     IC_GGL(k_fit_tail, dim3(grid), dim3(64 * TAIL_WAVES), 0, st, D, T64, P, nbin, ldD, dtiled, list, nctr,
                        S, amp, info, sweeps);
     return hipGetLastError();
@@ -5449,7 +5451,7 @@ static hipError_t launch_p2(hipStream_t st, const DiagArgs &a, size_t P)
     int gpb = C::WPP > 1 ? 1 : 8;
     while (gpb > 1 && fixed + gpb * (size_t)C::GROUP_BYTES > 150 * 1024) --gpb;
     const size_t shm = fixed + gpb * (size_t)C::GROUP_BYTES;
-    const unsigned grid = (unsigned)std::min<size_t>((P + gpb - 1) / gpb, 4096);
+    const unsigned grid = cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap);
     if (a.mode == DIAG_EXACT)
         IC_GGL((k_diag_p2<NN, DIAG_EXACT, D64>), dim3(grid), dim3(C::TPP * gpb), shm, st, a);
     else if (a.mode == DIAG_CLOSED)
@@ -5467,7 +5469,7 @@ static hipError_t launch_cl(hipStream_t st, const DiagArgs &a, size_t P)
     using C = CLay<NN>;
     const int gpb = C::GPB;
     const size_t shm = (size_t)C::TW_LDS * 16 + gpb * (size_t)C::GROUP_BYTES;
-    const unsigned grid = (unsigned)std::min<size_t>((P + gpb - 1) / gpb, 4096);
+    const unsigned grid = cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap);
     if (a.mode == DIAG_EXACT)
         IC_GGL((k_diag_cl<NN, DIAG_EXACT>), dim3(grid), dim3(C::L * gpb), shm, st, a);
     else if (a.mode == DIAG_STATS)
@@ -5527,7 +5529,7 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
     while (wpb > 1 && fixed + wpb * lay.per_wave > 150 * 1024) --wpb;
     const size_t shm = fixed + wpb * lay.per_wave;
     if (shm > 160 * 1024) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)std::min<size_t>((P + wpb - 1) / wpb, 8192);
+    const unsigned grid = cap_grid(std::min<size_t>((P + wpb - 1) / wpb, 8192), a.grid_cap);
     IC_GGL(k_diag, dim3(grid), dim3(64 * wpb), shm, st, a);
     return hipGetLastError();
 }
@@ -5596,10 +5598,10 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
                           const double *fft_d, const double *col_med, const double *col_mad,
                           const double *row_med, const double *row_mad, double chanthresh,
                           double subintthresh, double *test, float *W, float *hist, int iter,
-                          int32_t *counters)
+                          int32_t *counters, int grid_cap)
 {
     const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = (unsigned)std::min<size_t>(cdiv(P, 256), 1024);
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
     IC_GGL(k_combine, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d,
                        mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh,
                        test, W, hist, iter, counters);
@@ -5609,11 +5611,11 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
 hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, const float *base, const double *T64,
                            const double *amp, const int32_t *info, const int32_t *shift, int nsub, int nchan,
                            int nbin, int ldD, int dtiled, int pr_on, double pr_factor, int pr_start, int pr_end,
-                           float *R)
+                           float *R, int grid_cap)
 {
     const size_t P = (size_t)nsub * nchan;
     if (!D && (!raw || !base)) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)std::min<size_t>(cdiv(P, 4), 16384);
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 4), 16384), grid_cap);
     IC_GGL(k_residual, dim3(grid), dim3(256), 0, st, D, raw, base, T64, amp, info, shift, P, nchan, nbin,
                        ldD, dtiled, pr_on, pr_factor, pr_start, pr_end, R);
     return hipGetLastError();
@@ -5664,22 +5666,23 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
         (a.identity && (a.amp || a.late || a.list)) || (a.list && !a.nctr))
         return hipErrorInvalidValue;
     if (a.identity) {
-        IC_GGL(k_rotate_identity, dim3((unsigned)std::min<size_t>(cdiv(P, 4), 16384)), dim3(256), 0, st, a);
+        const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 4), 16384), a.grid_cap);
+        IC_GGL(k_rotate_identity, dim3(grid), dim3(256), 0, st, a);
         return hipGetLastError();
     }
 #define IC_ROT(NN)                                                                                 \
     case NN:                                                                                       \
         if (a.delay2)                                                                              \
             IC_GGL((k_rotate<NN, true>),                                                           \
-                   dim3((unsigned)std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB)), \
+                   dim3(cap_grid(std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB), a.grid_cap)), \
                    dim3(RotCfg<NN>::TB * RotCfg<NN>::WPB), 0, st, a);                              \
         else                                                                                       \
             IC_GGL((k_rotate<NN, false>),                                                          \
-                   dim3((unsigned)std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB)), \
+                   dim3(cap_grid(std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB), a.grid_cap)), \
                    dim3(RotCfg<NN>::TB * RotCfg<NN>::WPB), 0, st, a);                              \
         break;
     if (stats) {   // nbin 1024 (rotate_stats_supported)
-        const dim3 grid((unsigned)std::min<size_t>(cdiv(P, RotCfg<1024>::WPB), 16384 / RotCfg<1024>::WPB));
+        const dim3 grid(cap_grid(std::min<size_t>(cdiv(P, RotCfg<1024>::WPB), 16384 / RotCfg<1024>::WPB), a.grid_cap));
         const dim3 block(RotCfg<1024>::TB * RotCfg<1024>::WPB);
         if (a.delay2) IC_GGL((k_rotate<1024, true, true>), grid, block, 0, st, a);
         else IC_GGL((k_rotate<1024, false, true>), grid, block, 0, st, a);

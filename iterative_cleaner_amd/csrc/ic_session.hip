@@ -141,6 +141,7 @@ struct Session {
     LineStatsArgs ls_knobs;     // row-median form (IC_OPT_ROWSTAT_*)
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
+    int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
     double sync_timeout_s = 600.0;   // IC_OPT_SYNC_TIMEOUT_MS
     // a host wait timed out with kernels of this session possibly still in
     // flight: every later call but ic_session_destroy fails (IC_ESTATE), and
@@ -609,6 +610,7 @@ RotateArgs rotate_args(Session *s, const float *in, const float *base, int sign,
     a.nbin = s->p.nbin;
     a.out = out;
     a.ldo = ldo;
+    a.grid_cap = s->grid_cap;
     return a;
 }
 
@@ -658,10 +660,12 @@ int prepare(Session *s)
     CK(hipGetLastError());
     if (s->comm) {
         LAUNCH(s, K_SHARD_PACK,
-               launch_pack_rows(s->stream, s->geom, nchan, nullptr, nullptr, nullptr, nullptr, s->valid, s->xd_send));
+               launch_pack_rows(s->stream, s->geom, nchan, nullptr, nullptr, nullptr, nullptr, s->valid, s->xd_send,
+                                s->grid_cap));
         CM(s, s->comm->alltoallv(s->xd_send, s->vsb.data(), s->xd_recv, s->vrb.data(), s->stream), "valid rows");
         LAUNCH(s, K_SHARD_PACK,
-               launch_assemble_rows(s->stream, s->geom, s->xd_recv, nullptr, nullptr, nullptr, nullptr, s->valid_r));
+               launch_assemble_rows(s->stream, s->geom, s->xd_recv, nullptr, nullptr, nullptr, nullptr, s->valid_r,
+                                    s->grid_cap));
     }
     if (s->fftded) {
         // remove_baseline reads the dedispersed view rot(raw) (archive.py
@@ -673,7 +677,8 @@ int prepare(Session *s)
                                     s->part, nullptr, nullptr, nullptr, 0, 0, s->exA, nullptr));
         if (int rc = window_stage(s, nullptr)) return rc;
         LAUNCH(s, K_BASE,
-               launch_base(s->stream, s->dr, s->zshift, s->win, nullptr, nsub, nchan, nbin, s->width, s->base0));
+               launch_base(s->stream, s->dr, s->zshift, s->win, nullptr, nsub, nchan, nbin, s->width, s->base0,
+                           s->grid_cap));
         RotateArgs ra = rotate_args(s, s->raw, s->base0, +1, nullptr, s->Tc, nbin);
         ra.out2 = s->D;
         ra.ldo2 = s->ldD;
@@ -688,7 +693,8 @@ int prepare(Session *s)
                                 nullptr, nullptr, nullptr, 0, 0, s->exA, nullptr));
     if (int rc = window_stage(s, nullptr)) return rc;
     LAUNCH(s, K_BASE,
-           launch_base(s->stream, s->raw, s->shift, s->win, nullptr, nsub, nchan, nbin, s->width, s->base0));
+           launch_base(s->stream, s->raw, s->shift, s->win, nullptr, nsub, nchan, nbin, s->width, s->base0,
+                       s->grid_cap));
     // the fit cube D = f32(ded - base0) is written by iteration 1's template
     // pass (chan_partials mode 3), which reads the same values
     CK(hipMemcpyAsync(s->base, s->base0, sizeof(float) * s->P, hipMemcpyDeviceToDevice, s->stream));
@@ -728,7 +734,8 @@ int iteration_template(Session *s, int iter)
             }
             if (int rc = window_stage(s, s->wflag)) return rc;
             LAUNCH(s, K_BASE,
-                   launch_base(s->stream, s->dr, s->zshift, s->win, s->wflag, nsub, nchan, nbin, s->width, s->base));
+                   launch_base(s->stream, s->dr, s->zshift, s->win, s->wflag, nsub, nchan, nbin, s->width, s->base,
+                               s->grid_cap));
             LAUNCH(s, K_ROTATE,
                    launch_rotate(s->stream, rotate_args(s, s->raw, s->base, +1, s->wflag, s->Tc, nbin)));
         }
@@ -755,7 +762,8 @@ int iteration_template(Session *s, int iter)
         }
         if (int rc = window_stage(s, s->wflag)) return rc;
         LAUNCH(s, K_BASE,
-               launch_base(s->stream, s->raw, s->shift, s->win, s->wflag, nsub, nchan, nbin, s->width, s->base));
+               launch_base(s->stream, s->raw, s->shift, s->win, s->wflag, nsub, nchan, nbin, s->width, s->base,
+                           s->grid_cap));
         LAUNCH(s, K_CHAN_PARTIALS,
                launch_chan_partials(s->stream, 1, s->raw, s->W, s->shift, s->base, s->wflag, nsub, nchan, nbin,
                                     nullptr, s->part2, s->wpart, nullptr, 0, 0, nullptr, s->exF));
@@ -769,10 +777,12 @@ int iteration_template(Session *s, int iter)
 int shard_rowstats(Session *s, const LineStatsArgs &la)
 {
     LAUNCH(s, K_SHARD_PACK,
-           launch_pack_rows(s->stream, s->geom, s->nchan, s->std_, s->mean, s->fft, s->ptp, nullptr, s->xd_send));
+           launch_pack_rows(s->stream, s->geom, s->nchan, s->std_, s->mean, s->fft, s->ptp, nullptr, s->xd_send,
+                            s->grid_cap));
     CM(s, s->comm->alltoallv(s->xd_send, s->dsb.data(), s->xd_recv, s->drb.data(), s->stream), "diagnostics rows");
     LAUNCH(s, K_SHARD_PACK,
-           launch_assemble_rows(s->stream, s->geom, s->xd_recv, s->std_r, s->mean_r, s->fft_r, s->ptp_r, nullptr));
+           launch_assemble_rows(s->stream, s->geom, s->xd_recv, s->std_r, s->mean_r, s->fft_r, s->ptp_r, nullptr,
+                                s->grid_cap));
     LineStatsArgs lr;
     lr.nsub = s->rows_own;
     lr.nchan = s->geom.nchan_g;
@@ -862,7 +872,7 @@ int run_fit(Session *s, const DiagArgs *fork)
                 s->tail_bound = bound;
             }
             LAUNCH(s, K_FIT_TAIL, launch_fit_tail(s->stream, s->D, s->T64, P, nbin, s->ldD, s->dtiled, cur, cin, bound,
-                                                  s->fs, s->amp, s->info, tail_sweeps));
+                                                  s->fs, s->amp, s->info, tail_sweeps, s->grid_cap));
             tail = true;
             break;
         }
@@ -1390,7 +1400,7 @@ int ic_upload_pols(void *session, const float *data, int npol, const float *w0, 
             return fail(IC_ENOMEM, "hipMalloc(pol1 scratch, %zu floats) failed", s->N);
         hipError_t e = hipMemcpy2DAsync(pol1, row, (const char *)data + row, row * npol, row, s->p.nsub,
                                         hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) e = launch_pscrunch(s->stream, s->raw, pol1, s->N);
+        if (e == hipSuccess) e = launch_pscrunch(s->stream, s->raw, pol1, s->N, s->grid_cap);
         if (e == hipSuccess && s->D)
             e = hipMemsetAsync(s->D, 0, sizeof(float) * s->Ppad * (size_t)s->ldD, s->stream);
         if (!s->D) {
@@ -1503,7 +1513,7 @@ static int q_enqueue(Session *s, int slot, hipStream_t st, const int16_t *q, con
     CK(q_copy_pols(dscl, scl, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st));
     CK(q_copy_pols(doffs, offs, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st));
     CK(launch_decode_q(st, s->slot_q[slot], dscl, doffs, nsub, nchan, nbin, nsum, (flags & IC_Q_BIG_ENDIAN) != 0,
-                       s->slot_raw[slot]));
+                       s->slot_raw[slot], s->grid_cap));
     CK(hipMemcpyAsync(s->slot_w0[slot], w0, sizeof(float) * s->P, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(s->slot_shift[slot], shift, sizeof(int32_t) * nchan, hipMemcpyHostToDevice, st));
     return IC_OK;
@@ -1687,6 +1697,7 @@ DiagArgs diag_args(Session *s, int pr_start, int pr_end)
     a.ptp_o = s->ptp;
     a.data_f64 = p.data_f64 != 0;
     a.chain = s->diag_chain ? 1 : 0;
+    a.grid_cap = s->grid_cap;
     return a;
 }
 
@@ -1829,7 +1840,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
                launch_combine(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp, la.ptp_f32,
                               s->fft,
                               la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh, p.subintthresh,
-                              s->test, s->W, s->hist, n_iter, s->counters));
+                              s->test, s->W, s->hist, n_iter, s->counters, s->grid_cap));
         if (s->comm)
             CM(s, s->comm->allreduce_sum_i32(s->counters, (size_t)(n_iter + 4), s->stream), "convergence counters");
         CK(hipMemcpyAsync(cnt, s->counters, sizeof(int32_t) * (n_iter + 4), hipMemcpyDeviceToHost,
@@ -1906,7 +1917,7 @@ int ic_get_residual(void *session, float *out)
         e = launch_rotate(s->stream, ra);
     } else {
         e = launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub, s->nchan,
-                            p.nbin, s->ldD, s->dtiled, p.pr_on, p.pr_factor, pr_start, pr_end, R);
+                            p.nbin, s->ldD, s->dtiled, p.pr_on, p.pr_factor, pr_start, pr_end, R, s->grid_cap);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, R, sizeof(float) * s->N, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
@@ -2114,6 +2125,10 @@ int ic_set_option(void *session, int option, int64_t v)
         if (v < 0 || v > 2) return fail(IC_EINVAL, "IC_OPT_TAIL_SPLIT=%lld (0, 1 or 2)", (long long)v);
         s->tail_split_mode = (int)v;
         return IC_OK;
+    case IC_OPT_GRID_CAP:
+        if (v < 0 || v > 65536) return fail(IC_EINVAL, "IC_OPT_GRID_CAP=%lld outside 0..65536", (long long)v);
+        s->grid_cap = (int)v;
+        return IC_OK;
     case IC_OPT_ROT_STATS:
         if (v != 0 && v != 1) return fail(IC_EINVAL, "IC_OPT_ROT_STATS=%lld (0 or 1)", (long long)v);
         s->rot_stats = v != 0;
@@ -2140,6 +2155,7 @@ int ic_get_option(void *session, int option, int64_t *out)
     case IC_OPT_FIT_SCHEDULE: *out = IC_FIT_ROUNDS; return IC_OK;
     case IC_OPT_TAIL_SPLIT: *out = s->tail_split_mode; return IC_OK;
     case IC_OPT_ROT_STATS: *out = s->rot_stats ? 1 : 0; return IC_OK;
+    case IC_OPT_GRID_CAP: *out = s->grid_cap; return IC_OK;
     default: return fail(IC_EINVAL, "unknown option %d", option);
     }
 }
@@ -2369,7 +2385,7 @@ int ic_fit_profiles(int device, int nprof, int nbin, const float *T, const float
         float *R = nullptr;
         CK(hipMalloc((void **)&R, sizeof(float) * s->N));
         hipError_t e = launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub,
-                                       s->nchan, nbin, s->ldD, s->dtiled, 0, 1.0, 0, 0, R);
+                                       s->nchan, nbin, s->ldD, s->dtiled, 0, 1.0, 0, 0, R, s->grid_cap);
         if (e == hipSuccess) e = hipMemcpyAsync(resid_out, R, row * nprof, hipMemcpyDeviceToHost, s->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
         (void)hipFree(R);

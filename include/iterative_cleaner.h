@@ -43,7 +43,12 @@ extern "C" {
 #define IC_ESTATE -4   /* call out of order (e.g. run before upload)   */
 #define IC_ECOMM -5    /* a shard exchange failed (or a peer aborted)  */
 
-/* Loop parameters: args Namespace of iterative_cleaner.py:16-42. */
+/* Loop parameters: args Namespace of iterative_cleaner.py:16-42.
+ * nbin: a power of two in 64..8192 runs the templated diagnostics kernels
+ * (k_diag_p2 / k_diag_cl; at 8192 a profile is shared by eight waves), any
+ * other length the generic k_diag, as far as its per-profile LDS need allows
+ * (ic_session_create says how many bytes a refused length would take: every
+ * power of two above 8192 is refused that way).  nsub, nchan <= 16384. */
 typedef struct {
     int32_t nsub, nchan, nbin;
     int32_t max_iter;          /* -m                                          */
@@ -102,7 +107,8 @@ typedef struct {
  *                    epsilons of the profile's largest |sample| of numpy's f64
  *                    irfft(rfft(x) * phasor); parity with real psrchive
  *                    unpinned).  nbin must be a power of
- *                    two in 64..4096 (either fit_mode); the shift arrays of the
+ *                    two in 64..8192 (either fit_mode, f32 or f64 data,
+ *                    per-channel or per-profile delays); the shift arrays of the
  *                    uploads are then unused (pass zeros). */
 #define IC_DEDISP_SHIFT 0
 #define IC_DEDISP_FFT 1
@@ -294,7 +300,8 @@ int ic_get_run_stats(void *session, ic_run_stats *out);
  *   IC_OPT_ROWSTAT_WAVES   waves per row median/MAD line: 0 (one wave), 4 or 8; 8
  *   IC_OPT_ROWSTAT_MINLEN  shortest row that takes them, 1..16384; 1024
  *   IC_OPT_DIAG_CHAIN      1 = chain-layout diagnostics kernel at nbin 1024,
- *                          2048, 4096; 0 = the row-layout kernel; 1
+ *                          2048, 4096; 0 = the row-layout kernel (which every
+ *                          other power of two in 64..8192 takes either way); 1
  *   IC_OPT_FIT_SCHEDULE    how the exact fit is scheduled: IC_FIT_ROUNDS (the
  *                          only value since round 5) = rounds of a sweep kernel
  *                          over every profile with a pending data request and a

@@ -250,7 +250,24 @@ hipError_t launch_fit_tail(hipStream_t st, const float *D, const double *T64, lo
                            int dtiled, const int32_t *list, const unsigned long long *nctr, long bound,
                            const FitStateArrays &S, double *amp, int32_t *info, unsigned long long *sweeps,
                            int grid_cap = 0);
-// Diagnostics kernels (k_diag_p2<N> for power-of-two nbin 64..4096, k_diag
+// The power-of-two profile lengths with a templated diagnostics kernel
+// (k_diag_p2<N>) and a rotation (k_rotate<N>).  This list is the one place the
+// range lives: the launchers' dispatch, the host checks and the error texts
+// derive from it, so a further length is an entry here plus whatever its
+// instantiation needs (group_tree's wave count, RotCfg).
+#define IC_P2_SIZES(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096) X(8192)
+#define IC_P2_ENTRY(N) N,
+constexpr int kP2Sizes[] = {IC_P2_SIZES(IC_P2_ENTRY)};   // ascending
+#undef IC_P2_ENTRY
+constexpr int kP2Min = kP2Sizes[0], kP2Max = kP2Sizes[sizeof(kP2Sizes) / sizeof(kP2Sizes[0]) - 1];
+inline bool p2_supported(int nbin)
+{
+    for (int n : kP2Sizes)
+        if (n == nbin) return true;
+    return false;
+}
+
+// Diagnostics kernels (k_diag_p2<N> for the power-of-two nbin above, k_diag
 // otherwise).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
 // the fit cube D (row stride ldD); DIAG_CLOSED = fit_mode 1, the closed-form
 // amplitude sum(T*p)/TT from raw + base (written to amp/info), then the same
@@ -386,7 +403,7 @@ __host__ __device__ inline double2 ic_phasor(int k, double d, int n)
 // (in_tiled / out2_tiled: d_ofs, strides multiples of 32); flags: only subints
 // with flags[s] != 0; late: only profiles with (late[p] != 0) == late_sel (the
 // diagnostics fork's two passes).  in may equal out (each row is read whole
-// before it is written).  nbin a power of two, 64 .. 4096.
+// before it is written).  nbin a power of two, 64 .. 8192 (IC_P2_SIZES).
 struct RotateArgs {
     const float *in;
     long ld_in;

@@ -2622,11 +2622,13 @@ __global__ __launch_bounds__(256) void k_diag(DiagArgs a)
 }
 
 // ---------------------------------------------------------------------------
-// k_diag_p2<N>: the same diagnostics for power-of-two nbin = N (64..4096).
-// A profile group of TPP = 64*WPP threads cleans one profile: one wave for
-// N <= 1024, N/1024 waves for N = 2048/4096, so every thread holds the same
-// 16 samples and one pairwise chain at every N >= 1024 (at N = 4096 one wave
-// per profile needed a 32-KiB work array per wave: 1.25 waves/SIMD).
+// k_diag_p2<N>: the same diagnostics for power-of-two nbin = N (IC_P2_SIZES:
+// 64..8192).  A profile group of TPP = 64*WPP threads cleans one profile: one
+// wave for N <= 1024, N/1024 waves for N = 2048/4096/8192, so every thread holds
+// the same 16 samples and one pairwise chain at every N >= 1024 (at N = 4096 one
+// wave per profile needed a 32-KiB work array per wave: 1.25 waves/SIMD).  At
+// N = 8192 the group is 8 waves (512 threads) around a 64-KiB work array (68 KiB
+// for f64 data): two groups per CU, 4 waves per SIMD, and four radix-8 stages.
 // numpy's pairwise sum for N = 2^k is a balanced tree over leaves of
 // min(N,128) samples, each leaf 8 strided chains of min(N,128)/8 samples:
 // chain c = (leaf c/8, accumulator c%8) lives in thread c%TPP, slot c/TPP, and
@@ -2718,8 +2720,10 @@ __device__ __forceinline__ T tree_slots(const T (&v)[CPL])
 
 // Group-uniform reduction of a per-thread value: the wave tree over its WACT
 // active lanes, then (WPP > 1) a balanced tree over the group's waves through
-// `red` (WPP slots of 8 B, one slot array per call site; both barriers keep the
-// slots reusable on the next profile).
+// `red` (WPP <= 8 slots of 8 B, one slot array per call site; both barriers keep
+// the slots reusable on the next profile).  With the wave tree this is numpy's
+// pairwise order: wave w holds leaves 8w .. 8w + 7, so waves pair up as the
+// leaves' blocks of 8 do.
 template <int WPP, int WACT, typename T, typename Op>
 __device__ __forceinline__ T group_tree(T v, Op op, T *red, int wave, int lane)
 {
@@ -2730,8 +2734,10 @@ __device__ __forceinline__ T group_tree(T v, Op op, T *red, int wave, int lane)
         if (lane == 0) red[wave] = w;
         __syncthreads();
         T r;
+        static_assert(WPP == 2 || WPP == 4 || WPP == 8, "the balanced tree is spelled out for 2, 4 and 8 waves");
         if constexpr (WPP == 2) r = op(red[0], red[1]);
-        else r = op(op(red[0], red[1]), op(red[2], red[3]));   // WPP == 4
+        else if constexpr (WPP == 4) r = op(op(red[0], red[1]), op(red[2], red[3]));
+        else r = op(op(op(red[0], red[1]), op(red[2], red[3])), op(op(red[4], red[5]), op(red[6], red[7])));
         __syncthreads();
         return r;
     }
@@ -2849,7 +2855,8 @@ __device__ __forceinline__ void p2_fft(double2 *C, const XT *X, double mu, const
 }
 
 // occupancy floors (waves per SIMD, <= 128 VGPRs): 4 for the multi-wave groups
-// (the LDS allows 4 blocks of 4096 per CU) and for N = 1024 (the LDS allows 4
+// (the LDS allows 4 blocks of 4096 per CU and 2 of 8192, 16 waves either way)
+// and for N = 1024 (the LDS allows 4
 // waves/SIMD with 8-wave blocks), where the template is then read from L1
 // instead of being held in 32 VGPRs.  Measured on C2 (k_diag ms per clean):
 // 3 waves + template in registers 8.63, 4 waves + registers 8.10 (spills),
@@ -3134,7 +3141,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
                     }
             }
             mx = group_tree<WPP, 64>(mx, OpMaxF(), (XT *)(red + 32), wave, lane);
-            mn = group_tree<WPP, 64>(mn, OpMinF(), (XT *)(red + 36), wave, lane);
+            mn = group_tree<WPP, 64>(mn, OpMinF(), (XT *)(red + 40), wave, lane);
             // a NaN sample makes the pairwise sum s32 NaN; a NaN s32 without one
             // (inf - inf) is rare, and only then are the samples checked one by one
             int nan = 0;
@@ -3145,7 +3152,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
 #pragma unroll
                         for (int q = 0; q < C::CL; ++q) nan |= isnan(v[sl][q]);
                 }
-                nan = group_tree<WPP, 64>(nan, OpOr(), (int *)(red + 40), wave, lane);
+                nan = group_tree<WPP, 64>(nan, OpOr(), (int *)(red + 48), wave, lane);
             }
             ptp = nan ? (double)NAN : (double)(XT)(mx - mn);
             // rFFT of f64(X) - mean: N/2-point complex Stockham, in place
@@ -3187,14 +3194,14 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
                 if (kk <= H) post(Cb[cidx(kk)], Cb[cidx(kk == 0 ? 0 : C::M - kk)], tw[kk]);
             }
             int nanf = isnan(nsum);
-            best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 44, wave, lane);
-            nanf = group_tree<WPP, 64>(nanf, OpOr(), (int *)(red + 48), wave, lane);
+            best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 52, wave, lane);
+            nanf = group_tree<WPP, 64>(nanf, OpOr(), (int *)(red + 60), wave, lane);
             fftv = nanf ? NAN : 0.5 * sqrt(best2);
         } else {
             // invalid: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
             int nanx = 0;
             for (int i = t; i < N; i += TPP) nanx |= isnan(X[xaddr(i)]);
-            nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 52), wave, lane);
+            nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 48), wave, lane);
             fftv = nanx ? NAN : 0.0;
         }
         if (t == 0) {
@@ -3620,19 +3627,29 @@ __global__ __launch_bounds__(256) void k_residual(const float *__restrict__ D, c
 // (-ffp-contract=off), at half the f64 instruction count.
 typedef float rc2 __attribute__((ext_vector_type(2)));
 
+#ifndef IC_ROT_TW_LDS_MAX
+#define IC_ROT_TW_LDS_MAX 4096   // the longest nbin whose rotation stages its twiddle table in LDS
+#endif
+
 template <int N>
 struct RotCfg {
     static constexpr int M = N / 2, H = M / 2;
-    static constexpr int LG = N == 64 ? 5 : N == 128 ? 6 : N == 256 ? 7 : N == 512 ? 8 : N == 1024 ? 9
-                                                                              : N == 2048 ? 10 : 11;   // log2 M
+    static constexpr int LG = __builtin_ctz(M);   // log2 M
     static constexpr int TB = M / 8 < 64 ? 64 : (M / 8 > 256 ? 256 : M / 8);
     // one-wave profiles run four to a block, which stages the twiddle table in
-    // LDS once for all four; the one-block profiles of N >= 2048 stage it too,
+    // LDS once for all four; the one-block profiles of N = 2048 / 4096 stage it too,
     // once per block of the grid-stride loop (16 profiles per block at C5:
     // 62.7-63.1 -> 58.0-58.2 ms per C5 clean in the FFT mode, against f64
     // entries through L1/L2 rounded at each use)
     static constexpr int WPB = TB == 64 ? 4 : 1;
-    static constexpr bool TW_LDS = true;
+    // N = 8192: the f32 table (64 KiB) beside the 36 KiB of points would leave
+    // one block (one wave per SIMD) per CU; its entries are read as f64 through
+    // L1/L2 and rounded at the use (TwGlobal): the LDS then allows 4 blocks per
+    // CU and the 251-256 VGPRs two (2 waves per SIMD).  Measured on a 64 x 512
+    // x 8192 archive, alternating: 33.0-33.2 ms per clean with per-profile
+    // delays and 33.9-34.1 per channel, against 38.5-38.6 and 40.3-40.5 staged
+    // (-DIC_ROT_TW_LDS_MAX=8192 builds the staged form, tools/build_variant.sh)
+    static constexpr bool TW_LDS = N <= IC_ROT_TW_LDS_MAX;
 };
 
 // LDS slot of complex point i: one pad slot after every 8 points.  With 8-byte
@@ -3716,7 +3733,7 @@ __device__ __forceinline__ rc2 rot_ld2(__amdgpu_buffer_rsrc_t r, unsigned voff, 
 // rounded to f32.  Staged in LDS as f32 (TwLds32; with the statistics, whose
 // FFT needs the f64 table in LDS too, the f32 stage tables only: TwLdsSt), or
 // read as f64 through L1/L2 and rounded at the use (TwGlobal, one-block
-// profiles N >= 2048).
+// profiles N = 8192, whose f32 table would take 64 KiB).
 template <int N>
 struct TwGlobal {
     static constexpr bool ASM_ROWS = false;
@@ -5494,7 +5511,7 @@ bool diag_list_supported(const DiagArgs &a)
 {
     const int n = a.nbin;
     return uses_cl(a) ||
-           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && n >= 64 && n <= 4096 && (n & (n - 1)) == 0);
+           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && p2_supported(n));
 }
 
 hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
@@ -5518,7 +5535,7 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
         if (a.data_f64 && a.mode != DIAG_FIT) return launch_p2<NN, true>(st, a, P);                \
         return launch_p2<NN, false>(st, a, P);                                                     \
     }
-    IC_P2(64) IC_P2(128) IC_P2(256) IC_P2(512) IC_P2(1024) IC_P2(2048) IC_P2(4096)
+    IC_P2_SIZES(IC_P2)
 #undef IC_P2
     if (a.mode == DIAG_FIT) return hipErrorInvalidValue;   // power-of-two nbin only
     // nleaf/nops upper bound from nbin: leaves >= 64 samples except tiny n
@@ -5536,10 +5553,7 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
 
 size_t diag_lds_bytes(int nbin)
 {
-    switch (nbin) {
-    case 64: case 128: case 256: case 512: case 1024: case 2048: case 4096: return 0;
-    default: break;
-    }
+    if (p2_supported(nbin)) return 0;
     const int nleaf_ub = nbin <= 128 ? 1 : (nbin / 64 + 1);
     const DiagLayout lay = diag_layout(nbin, nleaf_ub, nleaf_ub);
     return (size_t)lay.ntw * 16 + lay.per_wave;
@@ -5621,13 +5635,7 @@ hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, con
     return hipGetLastError();
 }
 
-bool rotate_supported(int nbin)
-{
-    switch (nbin) {
-    case 64: case 128: case 256: case 512: case 1024: case 2048: case 4096: return true;
-    default: return false;
-    }
-}
+bool rotate_supported(int nbin) { return p2_supported(nbin); }
 
 bool rotate_stats_supported(int nbin, bool data_f64) { return nbin == 1024 && !data_f64; }
 
@@ -5689,7 +5697,7 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
         return hipGetLastError();
     }
     switch (a.nbin) {
-        IC_ROT(64) IC_ROT(128) IC_ROT(256) IC_ROT(512) IC_ROT(1024) IC_ROT(2048) IC_ROT(4096)
+        IC_P2_SIZES(IC_ROT)
     default: return hipErrorInvalidValue;
     }
 #undef IC_ROT

@@ -996,7 +996,8 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     if (p.input_dedispersed != 0 && (p.input_dedispersed != 1 || p.dedisp_mode != IC_DEDISP_FFT))
         return fail(IC_EINVAL, "input_dedispersed=%d needs dedisp_mode IC_DEDISP_FFT (0 or 1)", p.input_dedispersed);
     if (p.dedisp_mode == IC_DEDISP_FFT && !rotate_supported(p.nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in 64..4096 (nbin=%d)", p.nbin);
+        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in %d..%d (nbin=%d)", kP2Min, kP2Max,
+                    p.nbin);
     if (diag_lds_bytes(p.nbin) > 160 * 1024)
         return fail(IC_EINVAL, "nbin=%d needs %zu bytes of LDS for the diagnostics (> 160 KiB)", p.nbin,
                     diag_lds_bytes(p.nbin));
@@ -1979,7 +1980,8 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
 {
     if (!in || !delay_bins || !out || nsub <= 0 || nchan <= 0) return fail(IC_EINVAL, "bad argument");
     if (!rotate_supported(nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in 64..4096 (nbin=%d)", nbin);
+        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in %d..%d (nbin=%d)", kP2Min, kP2Max,
+                    nbin);
     if (sign != 1 && sign != -1) return fail(IC_EINVAL, "sign must be +1 or -1");
     const size_t nd = per_profile ? (size_t)nsub * nchan : (size_t)nchan;
     for (size_t c = 0; c < nd; ++c)

@@ -21,7 +21,7 @@ Mode selection (:func:`plan`):
     a whole number of bins is;
   * otherwise             -> psrchive's fractional FFT rotation (IC_DEDISP_FFT):
     one delay per channel when every subint has the same row, else one per
-    profile (ic_set_delays2).  nbin must then be a power of two in 64..4096;
+    profile (ic_set_delays2).  nbin must then be a power of two in 64..8192;
     any other nbin raises (the rotation kernels do not serve it, and rounding
     the delays would silently change which profiles get zapped).
 """
@@ -34,9 +34,12 @@ DISPERSION_CONSTANT = 1.0 / 2.41e-4    # s MHz^2 cm^3 / pc (psrchive, dspsr, tem
 __all__ = ["DISPERSION_CONSTANT", "delays_from_dm", "plan", "archive_delays", "fft_supported"]
 
 
+FFT_NBIN_MIN, FFT_NBIN_MAX = 64, 8192    # the library's IC_P2_SIZES (csrc/ic_internal.h)
+
+
 def fft_supported(nbin: int) -> bool:
-    """nbin the rotation kernels serve: a power of two in 64..4096."""
-    return 64 <= nbin <= 4096 and (nbin & (nbin - 1)) == 0
+    """nbin the rotation kernels serve: a power of two in 64..8192."""
+    return FFT_NBIN_MIN <= nbin <= FFT_NBIN_MAX and (nbin & (nbin - 1)) == 0
 
 
 def delays_from_dm(dm, freqs, fref, periods, nbin) -> np.ndarray:
@@ -66,8 +69,9 @@ def plan(delay, nbin: int, what: str = "archive"):
         # integral, but a channel's shift differs between subints: the shift
         # arrays are per channel, so these go through the per-profile rotation
     if not fft_supported(nbin):
-        raise ValueError("%s: fractional dedispersion delays need a power-of-two nbin in 64..4096 for the "
-                         "FFT phase rotation (nbin=%d); the delays are not rounded" % (what, nbin))
+        raise ValueError("%s: fractional dedispersion delays need a power-of-two nbin in %d..%d for the "
+                         "FFT phase rotation (nbin=%d); the delays are not rounded"
+                         % (what, FFT_NBIN_MIN, FFT_NBIN_MAX, nbin))
     zeros = np.zeros(nchan, np.int64)
     if np.all(d == d[:1]):
         return zeros, np.ascontiguousarray(d[0])

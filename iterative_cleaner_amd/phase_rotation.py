@@ -69,7 +69,7 @@ PI_L = np.longdouble("3.141592653589793238462643383279502884")
 
 
 def is_supported(nbin: int) -> bool:
-    """The rotation needs a power-of-two nbin (the GPU kernel: 64 .. 4096)."""
+    """The rotation needs a power-of-two nbin (the GPU kernels: 64 .. 8192)."""
     return nbin >= 4 and (nbin & (nbin - 1)) == 0
 
 

@@ -214,6 +214,36 @@ int ic_set_delays(void *session, const double *delay_bins);
  * rows that are all equal give exactly ic_set_delays' results (and take its
  * table). */
 int ic_set_delays2(void *session, const double *delay_bins);
+/* Delays that travel with an asynchronous upload (batches of archives with
+ * fractional delays: every archive has its own).  Binds delay_bins to the
+ * NEWEST pending asynchronous upload, the last ic_upload_async or
+ * ic_upload_quantised_async: per_profile 0 takes delay_bins [nchan] f64,
+ * 1 takes [nsub*nchan] (a shard: its local channel counts), as ic_set_delays
+ * and ic_set_delays2.  When ic_run consumes that upload the delays become the
+ * session's, exactly as if ic_set_delays (per_profile 1: ic_set_delays2) had
+ * been called with them just before that ic_run: they stay in force for
+ * re-runs and synchronous uploads until a later upload with delays is consumed
+ * or ic_set_delays[2] is called; an upload without attached delays leaves the
+ * session's delays as they are.  Rows that are all equal give the bits of
+ * per_profile 0 with that row (and take its table).
+ *
+ * The work is queued on the session's copy stream behind that upload's copies:
+ * one host->device copy of the delays into a buffer of the upload's input slot
+ * and, for per-channel delays, the kernel that builds the slot's phasor table
+ * from them (the table ic_set_delays builds, by the same kernel); the upload
+ * counts as arrived only after both, so all of it overlaps the cleaning of the
+ * archive before.  delay_bins follows ic_upload_async's rule: untouched until
+ * the consuming ic_run returns, page-locked for the copy to overlap.  The
+ * slot's buffers (the table, nchan * (nbin/2 + 1) * 2 floats, and nsub * nchan
+ * doubles) are allocated at first need and kept until ic_session_destroy.
+ *   IC_ESTATE  the session is not IC_DEDISP_FFT; no upload is pending; the
+ *              newest pending upload already has delays; the session has failed
+ *   IC_EINVAL  a null pointer; per_profile not 0 or 1; a delay that is not
+ *              finite (checked on the host, at the call): nothing is queued,
+ *              the upload stays pending without delays and takes them from a
+ *              later call
+ *   IC_ENOMEM  the slot's buffers cannot be allocated */
+int ic_upload_delays_async(void *session, const double *delay_bins, int per_profile);
 
 /* dedisperse (sign +1) or dededisperse (sign -1) a cube [nsub][nchan][nbin] f32
  * by the FFT phase rotation on the GPU (the operation IC_DEDISP_FFT applies at

@@ -27,7 +27,7 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_set_timing_kernel", "ic_set_option", "ic_get_option", "ic_comprehensive_stats_rowstat",
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
-           "ic_decode_profiles")
+           "ic_decode_profiles", "ic_upload_delays_async")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -164,6 +164,7 @@ def load_library(path: str = LIB_PATH):
     lib.ic_fit_profiles.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     lib.ic_set_delays.argtypes = [vp, vp]
     lib.ic_set_delays2.argtypes = [vp, vp]
+    lib.ic_upload_delays_async.argtypes = [vp, vp, C.c_int]
     lib.ic_rotate_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     lib.ic_rotate_profiles2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     lib.ic_comprehensive_stats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double,
@@ -205,7 +206,11 @@ class GpuSession:
 
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
-                 delay=None, options=None, input_dedispersed=False):
+                 delay=None, options=None, input_dedispersed=False, dedisp_fft=False):
+        """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
+        with these delays (set_delays).  dedisp_fft=True: the same mode without
+        delays yet: they come with set_delays, or with each archive
+        (upload_async / upload_quantised_async delay=)."""
         self.lib = load_library()
         self.shape = (int(nsub), int(nchan), int(nbin))
         self.max_iter = int(max_iter)
@@ -213,7 +218,7 @@ class GpuSession:
         on, fac, a, b = normalise_pulse_region(list(pulse_region), int(nbin))
         self.params = Params(int(nsub), int(nchan), int(nbin), int(max_iter), float(chanthresh),
                              float(subintthresh), on, fac, a, b, float(baseline_duty), self.fit_mode,
-                             1 if data_f64 else 0, DEDISP_SHIFT if delay is None else DEDISP_FFT,
+                             1 if data_f64 else 0, DEDISP_FFT if (delay is not None or dedisp_fft) else DEDISP_SHIFT,
                              1 if input_dedispersed else 0)
         self.data_f64 = bool(data_f64)
         h = C.c_void_p()
@@ -289,15 +294,37 @@ class GpuSession:
         self._check(self.lib.ic_upload_pols(self.h, _ptr(data), int(data.shape[1]), _ptr(w0), _ptr(shift)),
                     "ic_upload_pols")
 
-    def upload_async(self, cube, w0, shift):
+    def _check_delay(self, delay):
+        """The delays of an asynchronous upload are handed over as they are (not
+        copied): f64, C-contiguous, (nchan,) per channel or (nsub, nchan) per profile."""
+        nsub, nchan = self.shape[0], self.shape[1]
+        if (not isinstance(delay, np.ndarray) or delay.dtype != np.float64 or not delay.flags.c_contiguous
+                or delay.shape not in ((nchan,), (nsub, nchan))):
+            raise ValueError("delay must be a C-contiguous float64 array of shape (%d,) or (%d, %d)"
+                             % (nchan, nsub, nchan))
+
+    def _attach_delays(self, delay):
+        """ic_upload_delays_async for the upload queued last."""
+        self._check(self.lib.ic_upload_delays_async(self.h, _ptr(delay), 1 if delay.ndim == 2 else 0),
+                    "ic_upload_delays_async")
+
+    def upload_async(self, cube, w0, shift, delay=None):
         """Queue the copy of the next archive (see ic_upload_async); the arrays
-        must stay alive and unmodified until the run() that consumes them returns."""
+        must stay alive and unmodified until the run() that consumes them returns.
+        delay (an IC_DEDISP_FFT session): the archive's fractional delays, f64
+        (nchan,) or (nsub, nchan), attached to this upload
+        (ic_upload_delays_async): they become the session's delays when run()
+        consumes it.  Not copied: the same rule as the other arrays."""
         nsub, nchan, nbin = self.shape
         for a, shape, dt in ((cube, (nsub, nchan, nbin), np.float32), (w0, (nsub, nchan), np.float32),
                              (shift, (nchan,), np.int32)):
             if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
                 raise ValueError("upload_async needs C-contiguous %s %s arrays" % (dt.__name__, shape))
+        if delay is not None:
+            self._check_delay(delay)
         self._check(self.lib.ic_upload_async(self.h, _ptr(cube), _ptr(w0), _ptr(shift)), "ic_upload_async")
+        if delay is not None:
+            self._attach_delays(delay)
 
     def upload_quantised(self, q, scl, offs, w0, shift, nsum):
         """PSRFITS samples as stored, decoded on the GPU (ic_upload_quantised):
@@ -320,10 +347,10 @@ class GpuSession:
         self._check(self.lib.ic_upload_quantised(self.h, _ptr(q), _ptr(scl), _ptr(offs), npol, int(nsum), flags,
                                                  _ptr(w0), _ptr(shift)), "ic_upload_quantised")
 
-    def upload_quantised_async(self, q, scl, offs, w0, shift, nsum):
+    def upload_quantised_async(self, q, scl, offs, w0, shift, nsum, delay=None):
         """Queue the copy and the decode of the next archive
         (ic_upload_quantised_async); the arrays must stay alive and unmodified
-        until the run() that consumes them returns."""
+        until the run() that consumes them returns.  delay: as upload_async."""
         nsub, nchan, nbin = self.shape
         if q.dtype.kind != "i" or q.dtype.itemsize != 2:
             raise ValueError("upload_quantised_async needs int16 samples (native or '>i2'), got %s" % q.dtype)
@@ -337,8 +364,12 @@ class GpuSession:
             ok = a.shape == shape or (npol == 1 and shape[1:2] == (1,) and a.shape == (nsub, nchan))
             if a.dtype != dt or not ok or not a.flags.c_contiguous:
                 raise ValueError("upload_quantised_async needs C-contiguous %s %s arrays" % (dt, shape))
+        if delay is not None:
+            self._check_delay(delay)
         self._check(self.lib.ic_upload_quantised_async(self.h, _ptr(q), _ptr(scl), _ptr(offs), npol, int(nsum),
                                                        flags, _ptr(w0), _ptr(shift)), "ic_upload_quantised_async")
+        if delay is not None:
+            self._attach_delays(delay)
 
     def upload_device(self, cube_ptr: int, w0_ptr: int, shift_ptr: int):
         """Device pointers (e.g. torch tensor .data_ptr()) on this session's GPU."""

@@ -39,12 +39,20 @@ _LEAKED = []
 
 
 def _queue_upload(session, arrays, nsum):
-    """Queue one item's upload: (cube, w0, shift) f32, or the PSRFITS samples
-    (q, scl, offs, w0, shift), decoded on the GPU."""
-    if len(arrays) == 5:
-        session.upload_quantised_async(*arrays, nsum)
+    """Queue one item's upload: (cube, w0, shift[, delay]) f32, or the PSRFITS
+    samples (q, scl, offs, w0, shift[, delay]), decoded on the GPU.  A trailing
+    delay (f64, per channel or per profile) goes up with the archive
+    (ic_upload_delays_async); it is passed on, by keyword, only when the item
+    has one."""
+    n = len(arrays)
+    if n not in (3, 4, 5, 6):
+        raise ValueError("a batch item holds 3 or 4 arrays (cube, w0, shift[, delay]) or 5 or 6 "
+                         "(q, scl, offs, w0, shift[, delay]), not %d" % n)
+    kw = {"delay": arrays[-1]} if n in (4, 6) else {}
+    if n >= 5:
+        session.upload_quantised_async(*arrays[:5], nsum, **kw)
     else:
-        session.upload_async(*arrays)
+        session.upload_async(*arrays[:3], **kw)
 
 
 def pipeline(session, items, fetch=True, nsum=1):
@@ -52,7 +60,12 @@ def pipeline(session, items, fetch=True, nsum=1):
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
     offsets (GpuSession.upload_quantised_async; `nsum` polarisations summed);
-    both kinds may alternate.  The arrays must stay valid until their result is
+    both kinds may alternate.  On a session of the FFT dedispersion
+    (GpuSession(dedisp_fft=True)) an item may end in its archive's fractional
+    delays, f64 (nchan,) or (nsub, nchan): (cube, w0, shift, delay) or (q, scl,
+    offs, w0, shift, delay); they are copied, and the channel phasor table built,
+    behind the archive's copy, and become the session's delays for that archive
+    and after it.  The arrays must stay valid until their result is
     yielded (page-locked for the copies to overlap).  Yields the ic_run dicts in
     order."""
     it = iter(items)
@@ -71,7 +84,7 @@ _EXITED = -2   # a worker's last message (run_lanes)
 
 def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1):
     """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
-    as `pipeline`) on `len(sessions)` sessions of one
+    each with or without trailing delays, as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
     session overlaps its next upload with its current run).  The arrays must
     stay valid until their result is yielded.  Yields the ic_run dicts in input
@@ -208,9 +221,11 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
 
 class _Ring:
     """`n` page-locked (cube, w0, shift) slots, or with `q_spec` = (npol, dtype)
-    (q, scl, offs, w0, shift) slots of int16 samples in that byte order."""
+    (q, scl, offs, w0, shift) slots of int16 samples in that byte order.
+    delays: each slot ends in an (nsub, nchan) f64 buffer for the archive's
+    fractional delays."""
 
-    def __init__(self, n, nsub, nchan, nbin, q_spec=None):
+    def __init__(self, n, nsub, nchan, nbin, q_spec=None, delays=False):
         if q_spec is None:
             spec = [((nsub, nchan, nbin), np.float32)]
         else:
@@ -218,6 +233,8 @@ class _Ring:
             spec = [((nsub, npol, nchan, nbin), dtype), ((nsub, npol, nchan), np.float32),
                     ((nsub, npol, nchan), np.float32)]
         spec += [((nsub, nchan), np.float32), ((nchan,), np.int32)]
+        if delays:
+            spec += [((nsub, nchan), np.float64)]
         self.slots = [tuple(_native.PinnedArray(shape, dt) for shape, dt in spec) for _ in range(n)]
 
     def arrays(self, i):
@@ -230,7 +247,8 @@ class _Ring:
 
 
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
-                pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1):
+                pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
+                dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -244,7 +262,20 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     decode, made on the GPU.  The ring then holds the first `nsum`
     polarisations as page-locked int16 in the byte order of the loader's first
     item ('>i2' as stored, or native): half the bytes of an f32 cube cross the
-    bus, and none of the polarisations the loop never reads."""
+    bus, and none of the polarisations the loop never reads.
+
+    dedisp="fft": the archives are dedispersed by the FFT phase rotation
+    (IC_DEDISP_FFT), each by its own fractional delays: every loader item ends
+    in them, (cube, w0, shift, delay) or (q, scl, offs, w0, shift, delay), f64
+    in bins, (nchan,) per channel or (nsub, nchan) per profile (both kinds may
+    alternate; psrfits_loader yields such items).  The delays are staged in the
+    ring and go up with their archive.  An item without delays raises
+    ValueError, as does one with delays when dedisp is "shift".
+    input_dedispersed, fit_mode and options (a dict of schedule options) are
+    handed to every lane's GpuSession."""
+    if dedisp not in ("shift", "fft"):
+        raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
+    fft = dedisp == "fft"
     nsum = int(nsum)
     if quantised and nsum not in (1, 2):
         raise ValueError("nsum must be 1 or 2")
@@ -260,7 +291,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     full = queue.Queue(maxsize=ring)
     stop = threading.Event()
     error = []
-    rings = [] if quantised else [_Ring(ring, nsub, nchan, nbin)]   # quantised: made for the first item's byte order
+    rings = [] if quantised else [_Ring(ring, nsub, nchan, nbin, delays=fft)]   # quantised: made for the first item's byte order
     for i in range(ring):
         free.put(i)
 
@@ -273,12 +304,40 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
         if q.ndim != 4 or q.shape[0] != nsub or q.shape[2:] != (nchan, nbin) or q.shape[1] < nsum:
             raise ValueError("quantised samples %s != (%d, npol >= %d, %d, %d)" % (q.shape, nsub, nsum, nchan, nbin))
         if not rings:
-            rings.append(_Ring(ring, nsub, nchan, nbin, (nsum, q.dtype)))
+            rings.append(_Ring(ring, nsub, nchan, nbin, (nsum, q.dtype), delays=fft))
         dq, dscl, doffs = rings[0].arrays(i)[:3]
         np.copyto(dq, q[:, :nsum])   # (a later item in the other byte order is converted to the ring's)
         npol = q.shape[1]
         np.copyto(dscl, np.asarray(scl, np.float32).reshape(nsub, npol, nchan)[:, :nsum])
         np.copyto(doffs, np.asarray(offs, np.float32).reshape(nsub, npol, nchan)[:, :nsum])
+
+    def split_delay(item):
+        """(the item without its delays, the delays or None)"""
+        item = tuple(item)
+        base = 5 if quantised else 3
+        if len(item) not in (base, base + 1):
+            raise ValueError("a loader item holds %d arrays, or %d with its delays, not %d"
+                             % (base, base + 1, len(item)))
+        delay = item[base] if len(item) > base else None
+        if fft and delay is None:
+            raise ValueError("dedisp='fft': every loader item ends in its archive's fractional delays")
+        if not fft and delay is not None:
+            raise ValueError("a loader item with delays needs dedisp='fft'")
+        return item[:base], delay
+
+    views = {}   # ring slot -> the delays of the archive staged in it, as handed to the session
+
+    def stage_delay(i, delay):
+        d = np.asarray(delay, np.float64)
+        buf = rings[0].arrays(i)[-1]
+        if d.shape == (nchan,):
+            np.copyto(buf[0], d)        # per channel: row 0
+            views[i] = buf[0]
+        elif d.shape == (nsub, nchan):
+            np.copyto(buf, d)
+            views[i] = buf
+        else:
+            raise ValueError("delays %s != (%d,) or (%d, %d)" % (d.shape, nchan, nsub, nchan))
 
     def load():
         try:
@@ -286,13 +345,16 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                 i = free.get()
                 if stop.is_set():
                     return
+                item, delay = split_delay(item)
                 if quantised:
                     q, scl, offs, w0, shift = item
                     stage_quantised(i, q, scl, offs)
                 else:
                     cube, w0, shift = item
                     np.copyto(rings[0].arrays(i)[0], np.asarray(cube, np.float32).reshape(nsub, nchan, nbin))
-                w, s = rings[0].arrays(i)[-2:]
+                if fft:
+                    stage_delay(i, delay)
+                w, s = rings[0].arrays(i)[-3:-1] if fft else rings[0].arrays(i)[-2:]
                 np.copyto(w, np.asarray(w0, np.float32).reshape(nsub, nchan))
                 np.copyto(s, np.mod(np.asarray(shift), nbin).astype(np.int32).reshape(nchan))
                 full.put(i)
@@ -310,7 +372,8 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             if i is None:
                 return
             order.append(i)
-            yield rings[0].arrays(i)
+            arrays = rings[0].arrays(i)
+            yield arrays[:-1] + (views[i],) if fft else arrays
 
     order = []
     sessions = []
@@ -318,7 +381,9 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     try:
         for _ in range(lanes):
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
-                                               pulse_region, baseline_duty, device=device))
+                                               pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
+                                               options=options, input_dedispersed=input_dedispersed,
+                                               dedisp_fft=fft))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
@@ -339,3 +404,29 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
         else:
             for rg in rings:
                 rg.close()
+
+
+def psrfits_loader(paths, dedisp="shift"):
+    """Loader for clean_batch(..., quantised=True, dedisp=dedisp) over fold-mode
+    PSRFITS files (psrfits.load_quantised): yields (q, scl, offs, w0, shift),
+    or with dedisp="fft" (q, scl, offs, w0, shift, delay), the delays the file's
+    DM, channel frequencies and folding periods give (per channel, or per
+    profile when the rows' periods differ).  Raises ValueError naming the file
+    whose dedispersion is not `dedisp`: one with integral delays in an "fft"
+    list, one with fractional delays in a "shift" list.  The delays are never
+    rounded, and integral ones never take the rotation, which is not exact."""
+    if dedisp not in ("shift", "fft"):
+        raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
+    from . import psrfits
+    for path in paths:
+        q, scl, offs, w0, shift, meta = psrfits.load_quantised(path)
+        delay = meta["delay"]
+        if (delay is not None) != (dedisp == "fft"):
+            raise ValueError("%s: the archive is dedispersed by %s, the batch by %s"
+                             % (path, "fractional delays (FFT rotation)" if delay is not None
+                                else "integer shifts", "the FFT rotation (dedisp='fft')" if dedisp == "fft"
+                                else "integer shifts (dedisp='shift')"))
+        if delay is None:
+            yield q, scl, offs, w0, shift
+        else:
+            yield q, scl, offs, w0, shift, np.ascontiguousarray(delay, dtype=np.float64)

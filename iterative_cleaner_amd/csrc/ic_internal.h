@@ -446,6 +446,10 @@ struct RotateArgs {
     int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
 };
 hipError_t launch_rotate(hipStream_t st, const RotateArgs &a);
+// RotateArgs.ph built on the device from delay [nchan] f64 (device memory):
+// ph[c][k] = f32(ic_phasor(k, delay[c], nbin)), k <= nbin/2
+hipError_t launch_phasor_table(hipStream_t st, const double *delay, int nchan, int nbin, float *ph,
+                               int grid_cap = 0);
 bool rotate_supported(int nbin);
 // the residual rotation can carry the statistics (RotateArgs.std_o): f32 rows
 // whose rotation keeps a profile in one wave's registers (nbin 1024)

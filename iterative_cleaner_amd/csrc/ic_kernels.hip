@@ -656,6 +656,25 @@ __global__ __launch_bounds__(256) void k_pscrunch(float *__restrict__ raw, const
         raw[i] = raw[i] + pol1[i];
 }
 
+// The channel phasor table of the FFT dedispersion (RotateArgs.ph) from the
+// channels' delays on the device: ph[c][k] = f32(ic_phasor(k, delay[c], nbin)),
+// k <= nbin/2.  One element per thread, k fastest (a wave stores 512
+// contiguous bytes), grid-stride.  ic_phasor is the function the host's table
+// (make_phasors) and k_rotate's per-profile path evaluate; with
+// -ffp-contract=off its separately rounded f64 operations give the same bits
+// here.  n < 2^31 (launch_phasor_table).
+__global__ __launch_bounds__(256) void k_phasor_table(const double *__restrict__ delay, float2 *__restrict__ ph,
+                                                      uint32_t n, uint32_t row, int nbin)
+{
+    const uint32_t step = gridDim.x * blockDim.x;
+    // i + step cannot wrap: n < 2^31 and step <= 65536 * 256
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint32_t c = i / row, k = i - c * row;
+        const double2 v = ic_phasor((int)k, delay[c], nbin);
+        ph[i] = make_float2((float)v.x, (float)v.y);
+    }
+}
+
 // PSRFITS fold-mode decode on the device (psrfits.py decode + archive.py
 // pscrunch): q [nsub][nsum][nchan][nbin] int16, scl / offs [nsub][nsum][nchan],
 // raw [nsub][nchan][nbin] = f32(f32(q0) * scl0 + offs0) (nsum 1) or the f32 sum
@@ -5270,6 +5289,16 @@ hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t
 {
     const unsigned grid = cap_grid(std::min<unsigned>(cdiv(n / 4 + 1, 256), 8192), grid_cap);
     IC_GGL(k_pscrunch, dim3(grid), dim3(256), 0, st, raw, pol1, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_phasor_table(hipStream_t st, const double *delay, int nchan, int nbin, float *ph, int grid_cap)
+{
+    if (nchan < 1 || nbin < 2 || !delay || !ph) return hipErrorInvalidValue;
+    const size_t row = (size_t)nbin / 2 + 1, n = (size_t)nchan * row;
+    if (n >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(n, 256), 65536), grid_cap);
+    IC_GGL(k_phasor_table, dim3(grid), dim3(256), 0, st, delay, (float2 *)ph, (uint32_t)n, (uint32_t)row, nbin);
     return hipGetLastError();
 }
 

@@ -191,7 +191,19 @@ struct Session {
     float *dr = nullptr, *Tc = nullptr, *R = nullptr, *zbase = nullptr;
     int32_t *zshift = nullptr;
     float *ph = nullptr;   // f32 pairs
-    double *delay2 = nullptr;        // [P] per-profile delays (ic_set_delays2), else nullptr
+    double *dly = nullptr;           // [P] the session's delays on the device (first need): the channel
+                                     // row k_phasor_table reads, or the per-profile delays
+    double *delay2 = nullptr;        // = dly while per-profile delays are in force, else nullptr
+    // delays attached to an asynchronous upload (ic_upload_delays_async), per
+    // input slot: the delays [P] as copied (slot_dly), the channel table built
+    // from them on the copy stream (slot_ph; slot_dmode 1) or nothing more
+    // (per profile; 2).  0: the slot's upload carries no delays.  Buffers at
+    // first need.  The ic_run that consumes the upload exchanges the slot's
+    // buffer with the session's (ph or dly): the delays stay the session's own
+    // when a later upload, attached or not, reuses the slot.
+    float *slot_ph[2] = {nullptr, nullptr};
+    double *slot_dly[2] = {nullptr, nullptr};
+    int slot_dmode[2] = {0, 0};
     // timing
     bool timing = false;
     int timing_only = -1;            // >= 0: time only this kernel id
@@ -408,7 +420,8 @@ int collect_timing(Session *s)
 void free_all(Session *s)
 {
     for (int q = 0; q < 2; ++q) {
-        void *sb[] = {s->slot_raw[q], s->slot_w0[q], s->slot_shift[q], s->slot_q[q], s->slot_so[q]};
+        void *sb[] = {s->slot_raw[q], s->slot_w0[q], s->slot_shift[q], s->slot_q[q], s->slot_so[q],
+                      s->slot_ph[q], s->slot_dly[q]};
         for (void *b : sb)
             if (b) (void)hipFree(b);
         if (s->slot_ev[q]) (void)hipEventDestroy(s->slot_ev[q]);
@@ -423,7 +436,7 @@ void free_all(Session *s)
                     s->part, s->wpart, s->T64,  s->amp, s->std_, s->mean, s->fft,  s->test,
                     s->lstat, s->tw,   s->plan, s->fs_block, s->lists, s->rcount, s->tw_p2, s->part2,
                     s->wflag, s->TT, s->dr, s->Tc, s->R, s->zbase, s->zshift, s->ph, s->T2, s->fs.U, s->tmark,
-                    s->delay2};
+                    s->dly};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     void *rbufs[] = {s->std_r, s->mean_r, s->fft_r, s->ptp_r, s->valid_r};
@@ -1717,6 +1730,17 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
         s->shift = s->slot_shift[slot];
         s->uploaded = true;
         s->ran = false;
+        // delays that came with the upload become the session's (slot_ev
+        // follows their copy and the table kernel)
+        if (s->slot_dmode[slot] == 1) {
+            std::swap(s->ph, s->slot_ph[slot]);
+            s->delay2 = nullptr;   // a per-channel archive after a per-profile one
+        } else if (s->slot_dmode[slot] == 2) {
+            std::swap(s->dly, s->slot_dly[slot]);
+            s->delay2 = s->dly;
+        }
+        if (s->slot_dmode[slot]) s->delays_set = true;
+        s->slot_dmode[slot] = 0;
     }
     if (!s->uploaded) return fail(IC_ESTATE, "ic_run before ic_upload");
     // timed launches of earlier runs: fold them into the totals so the event
@@ -1936,14 +1960,61 @@ int ic_set_delays(void *session, const double *delay_bins)
     for (int c = 0; c < s->nchan; ++c)
         if (!isfinite(delay_bins[c])) return fail(IC_EINVAL, "delay[%d] is not finite", c);
     CK(hipSetDevice(s->device));
-    const std::vector<float> ph = make_phasors(s->p.nbin, s->nchan, delay_bins);
-    CK(hipMemcpyAsync(s->ph, ph.data(), sizeof(float) * ph.size(), hipMemcpyHostToDevice, s->stream));
-    CK(hipStreamSynchronize(s->stream));
-    if (s->delay2) {
-        CK(hipFree(s->delay2));
-        s->delay2 = nullptr;
+    // the table is built on the device (k_phasor_table), as an attached
+    // upload's is: one code path
+    if (!s->dly && hipMalloc((void **)&s->dly, sizeof(double) * s->P) != hipSuccess) {
+        s->dly = nullptr;
+        return fail(IC_ENOMEM, "hipMalloc(delays) failed");
     }
+    s->delay2 = nullptr;   // dly holds the channel row from here on
+    s->delays_set = false;
+    CK(hipMemcpyAsync(s->dly, delay_bins, sizeof(double) * s->nchan, hipMemcpyHostToDevice, s->stream));
+    CK(launch_phasor_table(s->stream, s->dly, s->nchan, s->p.nbin, s->ph, s->grid_cap));
+    CK(hipStreamSynchronize(s->stream));
     s->delays_set = true;
+    return IC_OK;
+}
+
+int ic_upload_delays_async(void *session, const double *delay_bins, int per_profile)
+{
+    Session *s = (Session *)session;
+    if (!s || !delay_bins) return fail(IC_EINVAL, "null argument");
+    if (s->failed) return failed_session();
+    if (!s->fftded)
+        return fail(IC_ESTATE, "ic_upload_delays_async on a session with dedisp_mode %d", s->p.dedisp_mode);
+    if (per_profile != 0 && per_profile != 1) return fail(IC_EINVAL, "per_profile=%d (0 or 1)", per_profile);
+    if (!s->fifo_n) return fail(IC_ESTATE, "ic_upload_delays_async without a pending asynchronous upload");
+    const int slot = s->fifo[s->fifo_n - 1];
+    if (s->slot_dmode[slot]) return fail(IC_ESTATE, "the newest pending upload already has delays");
+    const int nsub = s->p.nsub, nchan = s->nchan;
+    const size_t nd = per_profile ? s->P : (size_t)nchan;
+    for (size_t k = 0; k < nd; ++k)
+        if (!isfinite(delay_bins[k])) return fail(IC_EINVAL, "delay[%zu] is not finite", k);
+    // equal rows take the channel table, as in ic_set_delays2
+    bool table = !per_profile;
+    if (per_profile) {
+        table = true;
+        for (int sb = 1; sb < nsub && table; ++sb)
+            table = memcmp(delay_bins, delay_bins + (size_t)sb * nchan, sizeof(double) * nchan) == 0;
+    }
+    CK(hipSetDevice(s->device));
+    if (!s->slot_dly[slot] && hipMalloc((void **)&s->slot_dly[slot], sizeof(double) * s->P) != hipSuccess) {
+        s->slot_dly[slot] = nullptr;
+        return fail(IC_ENOMEM, "hipMalloc(slot delays, %zu bytes) failed", sizeof(double) * s->P);
+    }
+    if (table && !s->slot_ph[slot] && dalloc(&s->slot_ph[slot], 2 * (size_t)nchan * (s->p.nbin / 2 + 1)) != hipSuccess) {
+        s->slot_ph[slot] = nullptr;
+        return fail(IC_ENOMEM, "hipMalloc(slot phasor table, %zu bytes) failed",
+                    sizeof(float) * 2 * (size_t)nchan * (s->p.nbin / 2 + 1));
+    }
+    // behind the upload's copies on the copy stream; the slot's event moves
+    // behind the delays' copy and the table kernel, so ic_run waits for both
+    CK(hipMemcpyAsync(s->slot_dly[slot], delay_bins, sizeof(double) * (table ? (size_t)nchan : s->P),
+                      hipMemcpyHostToDevice, s->copy_stream));
+    if (table)
+        CK(launch_phasor_table(s->copy_stream, s->slot_dly[slot], nchan, s->p.nbin, s->slot_ph[slot], s->grid_cap));
+    CK(hipEventRecord(s->slot_ev[slot], s->copy_stream));
+    s->slot_dmode[slot] = table ? 1 : 2;
     return IC_OK;
 }
 
@@ -1962,12 +2033,13 @@ int ic_set_delays2(void *session, const double *delay_bins)
         rows_equal = memcmp(delay_bins, delay_bins + (size_t)sb * nchan, sizeof(double) * nchan) == 0;
     if (rows_equal) return ic_set_delays(session, delay_bins);
     CK(hipSetDevice(s->device));
-    if (!s->delay2 && hipMalloc((void **)&s->delay2, sizeof(double) * s->P) != hipSuccess) {
-        s->delay2 = nullptr;
+    if (!s->dly && hipMalloc((void **)&s->dly, sizeof(double) * s->P) != hipSuccess) {
+        s->dly = nullptr;
         return fail(IC_ENOMEM, "hipMalloc(per-profile delays) failed");
     }
-    CK(hipMemcpyAsync(s->delay2, delay_bins, sizeof(double) * s->P, hipMemcpyHostToDevice, s->stream));
+    CK(hipMemcpyAsync(s->dly, delay_bins, sizeof(double) * s->P, hipMemcpyHostToDevice, s->stream));
     CK(hipStreamSynchronize(s->stream));
+    s->delay2 = s->dly;
     s->delays_set = true;
     return IC_OK;
 }

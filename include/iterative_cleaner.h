@@ -188,6 +188,41 @@ int ic_upload_quantised_async(void *session, const int16_t *q, const float *scl,
 int ic_decode_profiles(int device, int nsub, int npol, int nsum, int nchan, int nbin, const int16_t *q,
                        const float *scl, const float *offs, int flags, float *out);
 
+/* Quantised downloads: the reverse, PSRFITS int16 samples encoded on the
+ * device, so that 2 nbin + 8 bytes per profile leave the GPU instead of 4 nbin.
+ * Each profile of nbin f32 samples d is encoded on its own (psrfits.py quantise),
+ * every step a separate IEEE operation:
+ *   mn, mx = the profile's minimum and maximum, NaN if any sample is NaN (numpy)
+ *   offs   = f32(0.5 * (f64(mx) + f64(mn)))
+ *   scl    = f32((f64(mx) - f64(mn)) / 65534.0); 1.0f unless scl > 0 and finite
+ *   x      = (f64(d) - f64(offs)) / f64(scl)   an f64 subtraction and a true
+ *            division: no fused multiply-add, no reciprocal, no f32 shortcut
+ *   q      = int16(clamp(rint(x), -32767, 32767))   round half to even; a NaN x
+ *            gives 0, +-inf clamp like any large value; -32768 is never produced
+ * q, scl and offs carry the bits psrfits.quantise gives the same samples, with
+ * one exception: numpy does not fix the sign of the minimum / maximum of zeros
+ * of mixed sign, so for a profile that holds only such zeros the sign of the
+ * zero offs is not pinned (its q and scl are: 0 and 1).  A NaN scl / offs
+ * equals the host's as a NaN, not in sign or payload.
+ *   flags  0, or IC_Q_BIG_ENDIAN: each sample's two bytes swapped on the
+ *          device, the FITS order, ready for the DATA column
+ *   q      [nsub][nchan][nbin] int16;  scl, offs  [nsub][nchan] f32
+ * IC_EINVAL: a null pointer, unknown flag bits, a shape that is not positive
+ * (checked before any device is touched).
+ *
+ * ic_encode_profiles: the encode alone, in [nsub][nchan][nbin] f32 on the host.
+ * Synchronous.
+ * ic_get_residual_quantised: the last iteration's residual, the cube
+ * ic_get_residual returns (a shard: its channel slice), materialised on the
+ * device as there and encoded there; the f32 cube never reaches the host.
+ * IC_ESTATE before a completed iteration and on a failed session.  The first
+ * call allocates the int16 / scale / offset staging on the device (2 nbin + 8
+ * bytes per profile), kept until ic_session_destroy; IC_ENOMEM if that, or the
+ * call's f32 temporary, fails. */
+int ic_encode_profiles(int device, int nsub, int nchan, int nbin, const float *in, int flags, int16_t *q,
+                       float *scl, float *offs);
+int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, float *offs);
+
 /* Run the cleaning loop to convergence or max_iter (iterative_cleaner.py:83-146).
  * Outputs (host, any may be NULL):
  *   test_out        [nsub*nchan] f64 : avg_test_results of the last loop (:120)

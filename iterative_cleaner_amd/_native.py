@@ -27,7 +27,7 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_set_timing_kernel", "ic_set_option", "ic_get_option", "ic_comprehensive_stats_rowstat",
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
-           "ic_decode_profiles", "ic_upload_delays_async")
+           "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -146,6 +146,8 @@ def load_library(path: str = LIB_PATH):
     lib.ic_upload_quantised.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.ic_upload_quantised_async.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.ic_decode_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
+    lib.ic_encode_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.ic_get_residual_quantised.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.ic_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     lib.ic_host_free.argtypes = [vp]
     lib.ic_host_free.restype = None
@@ -400,6 +402,19 @@ class GpuSession:
         self._check(self.lib.ic_get_residual(self.h, _ptr(out)), "ic_get_residual")
         return out
 
+    def residual_quantised(self, big_endian=False):
+        """residual() encoded on the GPU as a PSRFITS file stores it
+        (ic_get_residual_quantised): (q int16 (nsub, nchan, nbin), scl, offs f32
+        (nsub, nchan)), the bits of psrfits.quantise(residual()); the f32 cube is
+        never downloaded.  big_endian: q in the FITS byte order, dtype '>i2'."""
+        nsub, nchan, _ = self.shape
+        q = np.empty(self.shape, ">i2" if big_endian else np.int16)
+        scl = np.empty((nsub, nchan), np.float32)
+        offs = np.empty((nsub, nchan), np.float32)
+        self._check(self.lib.ic_get_residual_quantised(self.h, Q_BIG_ENDIAN if big_endian else 0, _ptr(q), _ptr(scl),
+                                                       _ptr(offs)), "ic_get_residual_quantised")
+        return q, scl, offs
+
     def template(self):
         out = np.empty(self.shape[2], np.float32)
         self._check(self.lib.ic_get_template(self.h, _ptr(out)), "ic_get_template")
@@ -518,6 +533,25 @@ def decode_profiles(q, scl, offs, nsum, device=0):
     if rc != 0:
         raise NativeError("ic_decode_profiles: %s (rc=%d)" % (_err(lib), rc))
     return out
+
+
+def encode_profiles(cube, big_endian=False, device=0):
+    """PSRFITS encode on the GPU (ic_encode_profiles): (nsub, nchan, nbin) f32 ->
+    (q int16 (nsub, nchan, nbin), scl, offs f32 (nsub, nchan)), the bits of
+    psrfits.quantise; big_endian: q in the FITS byte order, dtype '>i2'."""
+    lib = load_library()
+    cube = np.ascontiguousarray(cube, dtype=np.float32)
+    if cube.ndim != 3:
+        raise ValueError("encode_profiles: cube must be (nsub, nchan, nbin)")
+    nsub, nchan, nbin = cube.shape
+    q = np.empty(cube.shape, ">i2" if big_endian else np.int16)
+    scl = np.empty((nsub, nchan), np.float32)
+    offs = np.empty((nsub, nchan), np.float32)
+    rc = lib.ic_encode_profiles(int(device), nsub, nchan, nbin, _ptr(cube), Q_BIG_ENDIAN if big_endian else 0,
+                                _ptr(q), _ptr(scl), _ptr(offs))
+    if rc != 0:
+        raise NativeError("ic_encode_profiles: %s (rc=%d)" % (_err(lib), rc))
+    return q, scl, offs
 
 
 def rotate_profiles(cube, delay, sign=1, device=0):

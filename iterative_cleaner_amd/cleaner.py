@@ -207,7 +207,7 @@ def _device() -> int:
 
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
-             data_f64=False, delay=None, input_dedispersed=False, quantised=None):
+             data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -218,7 +218,11 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     this rank's channel slice (read slice-only from the file).  ``delay``:
     fractional delays, (nchan,) or (nsub, nchan) (dedispersion by FFT phase
     rotation); ``input_dedispersed``: the cube is stored dedispersed (FFT
-    dedispersion only)."""
+    dedispersion only).  ``residual_quantised`` (with ``want_residual``): the
+    residual comes encoded on the GPU as a PSRFITS file stores it, as
+    ``residual_q`` = (q '>i2', scl, offs) instead of the f32 ``residual``
+    (GpuSession.residual_quantised; under channel sharding the merged f32
+    ``residual`` is returned as ever)."""
     from .dist import channel_sharding
     if quantised is not None:
         if cube is not None or channel_sharding():
@@ -260,7 +264,10 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
             s.upload(cube, w0, shift)
         out = s.run()
         if want_residual and out["n_iter"] > 0:
-            out["residual"] = s.residual()
+            if residual_quantised:
+                out["residual_q"] = s.residual_quantised(big_endian=True)
+            else:
+                out["residual"] = s.residual()
     return out
 
 
@@ -353,9 +360,13 @@ def clean(ar, args, arch):
         if stored_ded and delay is None:
             cube = _to_dispersed(cube, shift)
     duty = ar.get_baseline_duty() if hasattr(ar, "get_baseline_duty") else 0.15
+    # an archive loaded from PSRFITS unloads as PSRFITS (archive_io), its
+    # residual too: that one is encoded on the GPU and downloaded as int16
+    psrfits_res = args.unload_res and getattr(ar, "_format", "") == "PSRFITS"
     out = run_loop(cube, orig_weights, shift, args, want_residual=args.unload_res, baseline_duty=duty,
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
-                   input_dedispersed=stored_ded and delay is not None, quantised=quant)
+                   input_dedispersed=stored_ded and delay is not None, quantised=quant,
+                   residual_quantised=psrfits_res)
     del cube
 
     x = 0
@@ -402,8 +413,11 @@ def clean(ar, args, arch):
     if args.bad_chan != 1 or args.bad_subint != 1:
         ar = find_bad_parts(ar, args)
     if args.unload_res and _side_effects:
-        _residual_archive(ar, out["residual"], orig_weights, shift, backend, delay).unload(
-            "%s_residual_%s.ar" % (ar_name, loops))
+        res_name = "%s_residual_%s.ar" % (ar_name, loops)
+        if psrfits_res:
+            _unload_psrfits_residual(ar, out, orig_weights, res_name)
+        else:
+            _residual_archive(ar, out["residual"], orig_weights, shift, backend, delay).unload(res_name)
     if args.print_zap:
         _plot_zap(avg_test_results, ar_name, args)
     if not args.no_log:
@@ -419,6 +433,22 @@ def _residual_archive(ar, residual, weights, shift, backend, delay=None):
     return Archive(residual[:, None], weights, shift, dedispersed=False, dm_delay=delay,
                    filename="residual.ar",
                    source=ar.get_source() if hasattr(ar, "get_source") else "J0000+0000")
+
+
+def _unload_psrfits_residual(ar, out, weights, path):
+    """The residual of an archive loaded from PSRFITS, written as PSRFITS with
+    the archive's metadata (the reference's residual is patient.clone(),
+    ic.py:106-108: same format): total intensity, one polarisation, dispersed
+    frame, the weights before the cleaning.  Its samples are the int16 the GPU
+    encoded (``residual_q``); a run that could only return the merged f32
+    residual (channel shards) is encoded here by psrfits.quantise, which gives
+    the same bytes."""
+    from . import psrfits
+    rq = out.get("residual_q")
+    if rq is None:
+        rq = psrfits.quantise(out["residual"][:, None])
+    psrfits.save_quantised(path, *rq, **psrfits.archive_meta(ar, weights=weights, state="Intensity",
+                                                             dedispersed=False))
 
 
 if __name__ == "__main__":  # pragma: no cover

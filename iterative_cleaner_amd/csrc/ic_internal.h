@@ -187,6 +187,11 @@ hipError_t launch_pscrunch(hipStream_t st, float *raw, const float *pol1, size_t
 // decode, archive.py pscrunch)
 hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, const float *offs, int nsub, int nchan,
                            int nbin, int nsum, bool big_endian, float *raw, int grid_cap = 0);
+// the reverse: in [nprof][nbin] f32 -> PSRFITS int16 samples q [nprof][nbin]
+// (big_endian: as FITS stores them) with scl / offs [nprof], bit for bit
+// psrfits.py quantise (k_encode_q); nprof < 2^31, the sample index is a size_t
+hipError_t launch_encode_q(hipStream_t st, const float *in, int nprof, int nbin, bool big_endian, int16_t *q,
+                           float *scl, float *offs, int grid_cap = 0);
 // num (s, leaf, i) = part[s*ss + leaf*sl + i], weight (s, leaf) = wpart[s*wss + leaf*wsl]
 hipError_t launch_fscrunch(hipStream_t st, const double *part, long ss, long sl, const double *wpart, long wss,
                            long wsl, const SbPlan &plan, int nsub, int nbin, float *F, float *wf);

@@ -757,6 +757,125 @@ __global__ __launch_bounds__(256) void k_decode_q_scalar(const int16_t *__restri
     }
 }
 
+// PSRFITS fold-mode encode on the device (psrfits.py quantise), the decode in
+// reverse: in [nprof][nbin] f32 -> q [nprof][nbin] int16, scl / offs [nprof].
+// Per profile, with mn / mx its minimum and maximum (NaN if any sample is NaN,
+// numpy's rule):
+//   offs = f32(0.5 * (f64(mx) + f64(mn)))
+//   scl  = f32((f64(mx) - f64(mn)) / 65534), 1 unless scl > 0 and finite
+//   q    = clamp(rint((f64(d) - f64(offs)) / f64(scl)), -32767, 32767), NaN -> 0
+// every step its own IEEE operation (an f64 subtraction and a true division per
+// sample, round half to even), so the bits are the host's.  The comparisons
+// skip NaN samples and a flag carries them, because the hardware's min / max
+// return the other operand.
+__device__ __forceinline__ int q_encode(float d, double offs, double scl)
+{
+    const double x = __ddiv_rn(__dsub_rn((double)d, offs), scl);
+    if (x != x) return 0;
+    const double r = rint(x);          // +-inf clamp like any large value
+    return (int)(r < -32767.0 ? -32767.0 : (r > 32767.0 ? 32767.0 : r));
+}
+
+// two samples into one 32-bit word (the first in the low half), BE: each
+// sample's bytes swapped (q_pair in reverse)
+template <bool BE>
+__device__ __forceinline__ uint32_t q_pack(int lo, int hi)
+{
+    uint32_t w = ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+    if (BE) w = ((w & 0x00ff00ffu) << 8) | ((w >> 8) & 0x00ff00ffu);
+    return w;
+}
+
+__device__ __forceinline__ void q_minmax(float x, float &mn, float &mx, int &nan)
+{
+    nan |= x != x;
+    mn = x < mn ? x : mn;
+    mx = x > mx ? x : mx;
+}
+
+// One 256-lane block per profile, grid-stride over the profiles.  Pass 1: the
+// block's minimum and maximum (16-byte loads when V4: nbin % 4 == 0), reduced
+// in the wave by shuffles and across the four waves through LDS; every lane
+// then derives the same scl / offs and lane 0 stores them.  Pass 2 reads the
+// profile again (at most 32 KB, just read) and writes the samples, 8 per lane
+// in one 16-byte store when V8 (nbin % 8 == 0), else one by one.
+template <bool BE, bool V4, bool V8>
+__global__ __launch_bounds__(256) void k_encode_q(const float *__restrict__ in, int nprof, int nbin,
+                                                  int16_t *__restrict__ q, float *__restrict__ scl,
+                                                  float *__restrict__ offs)
+{
+    __shared__ float s_mn[4], s_mx[4];
+    __shared__ int s_nan[4];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int p = blockIdx.x; p < nprof; p += gridDim.x) {
+        const float *src = in + (size_t)p * nbin;
+        float mn = INFINITY, mx = -INFINITY;
+        int nan = 0;
+        if (V4) {
+            const float4 *s4 = (const float4 *)src;
+            for (int i = tid; i < nbin / 4; i += 256) {
+                const float4 v = s4[i];
+                q_minmax(v.x, mn, mx, nan);
+                q_minmax(v.y, mn, mx, nan);
+                q_minmax(v.z, mn, mx, nan);
+                q_minmax(v.w, mn, mx, nan);
+            }
+        } else {
+            for (int i = tid; i < nbin; i += 256) q_minmax(src[i], mn, mx, nan);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float a = __shfl_xor(mn, off), b = __shfl_xor(mx, off);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+            nan |= __shfl_xor(nan, off);
+        }
+        if ((tid & 63) == 0) {
+            s_mn[wave] = mn;
+            s_mx[wave] = mx;
+            s_nan[wave] = nan;
+        }
+        __syncthreads();
+        mn = s_mn[0];
+        mx = s_mx[0];
+        nan = s_nan[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            mn = s_mn[w] < mn ? s_mn[w] : mn;
+            mx = s_mx[w] > mx ? s_mx[w] : mx;
+            nan |= s_nan[w];
+        }
+        __syncthreads();               // the next profile writes s_* again
+        if (nan) mn = mx = NAN;
+        const float fo = (float)__dmul_rn(0.5, __dadd_rn((double)mx, (double)mn));
+        float fs = (float)__ddiv_rn(__dsub_rn((double)mx, (double)mn), 65534.0);
+        if (!(fs > 0.0f && isfinite(fs))) fs = 1.0f;
+        if (tid == 0) {
+            scl[p] = fs;
+            offs[p] = fo;
+        }
+        const double o = (double)fo, s = (double)fs;
+        if (V8) {
+            const float4 *s4 = (const float4 *)src;
+            uint4 *dst = (uint4 *)(q + (size_t)p * nbin);
+            for (int g = tid; g < nbin / 8; g += 256) {
+                const float4 a = s4[2 * g], b = s4[2 * g + 1];
+                dst[g] = make_uint4(q_pack<BE>(q_encode(a.x, o, s), q_encode(a.y, o, s)),
+                                    q_pack<BE>(q_encode(a.z, o, s), q_encode(a.w, o, s)),
+                                    q_pack<BE>(q_encode(b.x, o, s), q_encode(b.y, o, s)),
+                                    q_pack<BE>(q_encode(b.z, o, s), q_encode(b.w, o, s)));
+            }
+        } else {
+            uint16_t *dst = (uint16_t *)q + (size_t)p * nbin;
+            for (int i = tid; i < nbin; i += 256) {
+                uint32_t w = (uint32_t)q_encode(src[i], o, s) & 0xffffu;
+                if (BE) w = ((w & 0xffu) << 8) | (w >> 8);
+                dst[i] = (uint16_t)w;
+            }
+        }
+    }
+}
+
 // F[s][i] = f32(num/wsum) (0 if wsum == 0); wf[s] = f32(wsum); num and wsum
 // are the canonical trees over the leaves
 __global__ __launch_bounds__(256) void k_fscrunch(const double *__restrict__ part, long ss, long sl,
@@ -5337,6 +5456,30 @@ hipError_t launch_decode_q(hipStream_t st, const int16_t *q, const float *scl, c
         if (big_endian) decode_q_dispatch<true, 1>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
         else decode_q_dispatch<false, 1>(st, q, scl, offs, P, nchan, nbin, raw, grid_cap);
     }
+    return hipGetLastError();
+}
+
+namespace {
+template <bool BE>
+void encode_q_dispatch(hipStream_t st, const float *in, int nprof, int nbin, int16_t *q, float *scl, float *offs,
+                       int grid_cap)
+{
+    // a block per profile; 16384 blocks of four waves cover the 256 CUs many times
+    const dim3 grid(cap_grid(std::min<size_t>((size_t)nprof, 16384), grid_cap));
+    const bool v4 = nbin % 4 == 0 && ((uintptr_t)in & 15) == 0;
+    const bool v8 = v4 && nbin % 8 == 0 && ((uintptr_t)q & 15) == 0;
+    if (v8) IC_GGL((k_encode_q<BE, true, true>), grid, dim3(256), 0, st, in, nprof, nbin, q, scl, offs);
+    else if (v4) IC_GGL((k_encode_q<BE, true, false>), grid, dim3(256), 0, st, in, nprof, nbin, q, scl, offs);
+    else IC_GGL((k_encode_q<BE, false, false>), grid, dim3(256), 0, st, in, nprof, nbin, q, scl, offs);
+}
+}  // namespace
+
+hipError_t launch_encode_q(hipStream_t st, const float *in, int nprof, int nbin, bool big_endian, int16_t *q,
+                           float *scl, float *offs, int grid_cap)
+{
+    if (nprof < 1 || nbin < 1) return hipErrorInvalidValue;
+    if (big_endian) encode_q_dispatch<true>(st, in, nprof, nbin, q, scl, offs, grid_cap);
+    else encode_q_dispatch<false>(st, in, nprof, nbin, q, scl, offs, grid_cap);
     return hipGetLastError();
 }
 

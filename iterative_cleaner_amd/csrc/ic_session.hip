@@ -116,6 +116,10 @@ struct Session {
     int16_t *slot_q[2] = {nullptr, nullptr};
     float *slot_so[2] = {nullptr, nullptr};
     int slot_qsum[2] = {0, 0};
+    // quantised download (ic_get_residual_quantised): the encoded residual's
+    // int16 samples [N] and scl then offs [P] each; first use, kept
+    int16_t *res_q = nullptr;
+    float *res_so = nullptr;
     hipStream_t copy_stream = nullptr;
     int cur = 0, fifo[2] = {0, 0}, fifo_n = 0;
     bool ever_uploaded = false;
@@ -436,7 +440,7 @@ void free_all(Session *s)
                     s->part, s->wpart, s->T64,  s->amp, s->std_, s->mean, s->fft,  s->test,
                     s->lstat, s->tw,   s->plan, s->fs_block, s->lists, s->rcount, s->tw_p2, s->part2,
                     s->wflag, s->TT, s->dr, s->Tc, s->R, s->zbase, s->zshift, s->ph, s->T2, s->fs.U, s->tmark,
-                    s->dly};
+                    s->dly, s->res_q, s->res_so};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     void *rbufs[] = {s->std_r, s->mean_r, s->fft_r, s->ptp_r, s->valid_r};
@@ -1922,6 +1926,22 @@ int ic_run(void *session, double *test_out, float *weights_out, int32_t *loops_o
     return rc;
 }
 
+// the last iteration's residual cube, dispersed frame, into R [N] on the
+// session stream (ic_get_residual, ic_get_residual_quantised)
+static hipError_t launch_residual_cube(Session *s, float *R)
+{
+    const ic_params &p = s->p;
+    int pr_start = p.pr_start < 0 ? 0 : (p.pr_start > p.nbin ? p.nbin : p.pr_start);
+    int pr_end = p.pr_end < 0 ? 0 : (p.pr_end > p.nbin ? p.nbin : p.pr_end);
+    if (s->fftded) {   // residual + dededisperse (the inverse rotation) in one pass
+        RotateArgs ra = residual_rotate_args(s, pr_start, pr_end);
+        ra.out = R;
+        return launch_rotate(s->stream, ra);
+    }
+    return launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub, s->nchan,
+                           p.nbin, s->ldD, s->dtiled, p.pr_on, p.pr_factor, pr_start, pr_end, R, s->grid_cap);
+}
+
 int ic_get_residual(void *session, float *out)
 {
     Session *s = (Session *)session;
@@ -1929,25 +1949,84 @@ int ic_get_residual(void *session, float *out)
     if (s->failed) return failed_session();
     if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
     CK(hipSetDevice(s->device));
-    const ic_params &p = s->p;
-    int pr_start = p.pr_start < 0 ? 0 : (p.pr_start > p.nbin ? p.nbin : p.pr_start);
-    int pr_end = p.pr_end < 0 ? 0 : (p.pr_end > p.nbin ? p.nbin : p.pr_end);
     // temporary output buffer
     float *R = nullptr;
     CK(hipMalloc((void **)&R, sizeof(float) * s->N));
-    hipError_t e;
-    if (s->fftded) {   // residual + dededisperse (the inverse rotation) in one pass
-        RotateArgs ra = residual_rotate_args(s, pr_start, pr_end);
-        ra.out = R;
-        e = launch_rotate(s->stream, ra);
-    } else {
-        e = launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub, s->nchan,
-                            p.nbin, s->ldD, s->dtiled, p.pr_on, p.pr_factor, pr_start, pr_end, R, s->grid_cap);
-    }
+    hipError_t e = launch_residual_cube(s, R);
     if (e == hipSuccess) e = hipMemcpyAsync(out, R, sizeof(float) * s->N, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     (void)hipFree(R);
     if (e != hipSuccess) return fail(IC_EHIP, "residual: %s", hipGetErrorString(e));
+    return IC_OK;
+}
+
+int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, float *offs)
+{
+    Session *s = (Session *)session;
+    if (!s || !q || !scl || !offs) return fail(IC_EINVAL, "null argument");
+    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    if (s->failed) return failed_session();
+    if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
+    CK(hipSetDevice(s->device));
+    // the encoded residual's staging: first use, kept until ic_session_destroy
+    if (!s->res_q) {
+        if (dalloc(&s->res_q, s->N) != hipSuccess || dalloc(&s->res_so, 2 * s->P) != hipSuccess) {
+            if (s->res_q) (void)hipFree(s->res_q);
+            s->res_q = nullptr;
+            s->res_so = nullptr;
+            return fail(IC_ENOMEM, "quantised residual staging (%zu bytes) failed",
+                        sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P);
+        }
+    }
+    // the f32 cube stays a per-call temporary, as in ic_get_residual
+    float *R = nullptr;
+    if (hipMalloc((void **)&R, sizeof(float) * s->N) != hipSuccess)
+        return fail(IC_ENOMEM, "residual cube (%zu bytes) failed", sizeof(float) * s->N);
+    hipError_t e = launch_residual_cube(s, R);
+    if (e == hipSuccess)
+        e = launch_encode_q(s->stream, R, (int)s->P, s->p.nbin, (flags & IC_Q_BIG_ENDIAN) != 0, s->res_q, s->res_so,
+                            s->res_so + s->P, s->grid_cap);
+    if (e == hipSuccess) e = hipMemcpyAsync(q, s->res_q, sizeof(int16_t) * s->N, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(scl, s->res_so, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(offs, s->res_so + s->P, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    (void)hipFree(R);
+    if (e != hipSuccess) return fail(IC_EHIP, "quantised residual: %s", hipGetErrorString(e));
+    return IC_OK;
+}
+
+int ic_encode_profiles(int device, int nsub, int nchan, int nbin, const float *in, int flags, int16_t *q,
+                       float *scl, float *offs)
+{
+    if (!in || !q || !scl || !offs) return fail(IC_EINVAL, "null argument");
+    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    if (nsub <= 0 || nchan <= 0 || nbin <= 0 || (size_t)nsub * nchan > (size_t)INT32_MAX)
+        return fail(IC_EINVAL, "bad shape (%d, %d, %d)", nsub, nchan, nbin);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    CK(hipSetDevice(device));
+    const size_t P = (size_t)nsub * nchan, N = P * nbin;
+    float *d = nullptr, *dso = nullptr;
+    int16_t *dq = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, sizeof(float) * N);
+    if (e == hipSuccess) e = hipMalloc((void **)&dq, sizeof(int16_t) * N);
+    if (e == hipSuccess) e = hipMalloc((void **)&dso, sizeof(float) * P * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_encode_q(st, d, (int)P, nbin, (flags & IC_Q_BIG_ENDIAN) != 0, dq, dso, dso + P);
+    if (e == hipSuccess) e = hipMemcpyAsync(q, dq, sizeof(int16_t) * N, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(scl, dso, sizeof(float) * P, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(offs, dso + P, sizeof(float) * P, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (d) (void)hipFree(d);
+    if (dq) (void)hipFree(dq);
+    if (dso) (void)hipFree(dso);
+    if (st) (void)hipStreamDestroy(st);
+    if (e == hipErrorOutOfMemory) return fail(IC_ENOMEM, "ic_encode_profiles: device allocation failed");
+    if (e != hipSuccess) return fail(IC_EHIP, "ic_encode_profiles: %s", hipGetErrorString(e));
     return IC_OK;
 }
 

@@ -149,29 +149,76 @@ def save(ar, path: str, stand_in_meta: bool = True) -> None:
     """Write `ar` as fold-mode PSRFITS (stand_in_meta=False: standard columns
     and keywords only, as a foreign writer would produce)."""
     data = ar._data
-    nsub, npol, nchan, nbin = data.shape
     q = getattr(ar, "_psrfits_q", None)
     if q is None or q[0].shape != data.shape or not np.array_equal(decode(*q), data):
         q = quantise(data)
-    qd, scl, offs = q
-    cfreq = float(ar.get_centre_frequency())
-    freqs = getattr(ar, "_chan_freqs", None)
+    _write(path, *q, archive_meta(ar), stand_in_meta)
+
+
+def archive_meta(ar, **changes) -> dict:
+    """What the writer takes from an archive besides its samples, as the
+    keywords of save_quantised; `changes` replace entries (the residual of an
+    archive: its state, weights and frame)."""
+    meta = dict(weights=ar._weights, shift=ar._shift, delay=getattr(ar, "_delay", None),
+                chan_freqs=getattr(ar, "_chan_freqs", None), centre_frequency=float(ar.get_centre_frequency()),
+                period=getattr(ar, "_period", 1.0), tsubint=float(getattr(ar, "_tsubint", 10.0)),
+                dm=float(getattr(ar, "_dm", 0.0)), mjd_start=float(ar.start_time().in_days()),
+                mjd_end=float(ar.end_time().in_days()), source=ar.get_source(), state=ar.get_state(),
+                dedispersed=bool(ar.get_dedispersed()), baseline_duty=float(ar.get_baseline_duty()))
+    meta.update(changes)
+    return meta
+
+
+def save_quantised(path: str, q, scl, offs, weights, shift, delay=None, chan_freqs=None, centre_frequency=1400.0,
+                   period=1.0, tsubint=10.0, dm=0.0, mjd_start=60000.0, mjd_end=60000.01, source="J0000+0000",
+                   state=None, dedispersed=False, baseline_duty=0.15, stand_in_meta: bool = True) -> None:
+    """Write fold-mode PSRFITS from samples that are int16 already (quantise, or
+    GpuSession.residual_quantised): q (nsub, npol, nchan, nbin), or (nsub, nchan,
+    nbin) for one polarisation, in either byte order - '>i2' goes into the DATA
+    column as it is - with scl / offs f32 (nsub, npol, nchan) or (nsub, nchan).
+    No f32 cube is formed.  The keywords are archive_meta's: save(ar, path)
+    writes the bytes of save_quantised(path, *quantise(ar's samples),
+    **archive_meta(ar))."""
+    q = np.asarray(q)
+    if q.dtype.kind != "i" or q.dtype.itemsize != 2:
+        raise ValueError("save_quantised needs int16 samples (native or '>i2'), got %s" % q.dtype)
+    if q.ndim == 3:
+        q = q.reshape(q.shape[0], 1, q.shape[1], q.shape[2])
+    if q.ndim != 4:
+        raise ValueError("q must be (nsub, npol, nchan, nbin) or (nsub, nchan, nbin)")
+    nsub, npol, nchan, _ = q.shape
+    from .archive import default_state
+    meta = dict(weights=np.asarray(weights, np.float32).reshape(nsub, nchan), shift=shift, delay=delay,
+                chan_freqs=chan_freqs, centre_frequency=float(centre_frequency), period=period,
+                tsubint=float(tsubint), dm=float(dm), mjd_start=float(mjd_start), mjd_end=float(mjd_end),
+                source=source, state=state or default_state(npol), dedispersed=bool(dedispersed),
+                baseline_duty=float(baseline_duty))
+    _write(path, q, np.asarray(scl, np.float32).reshape(nsub, npol, nchan),
+           np.asarray(offs, np.float32).reshape(nsub, npol, nchan), meta, stand_in_meta)
+
+
+def _write(path: str, qd, scl, offs, m: dict, stand_in_meta: bool) -> None:
+    """The file: primary header and the SUBINT table of the int16 samples qd
+    (nsub, npol, nchan, nbin) with their scales and offsets; m: archive_meta."""
+    nsub, npol, nchan, nbin = qd.shape
+    cfreq = m["centre_frequency"]
+    freqs = m["chan_freqs"]
     if freqs is None or len(freqs) != nchan:
         freqs = cfreq + (np.arange(nchan) - (nchan - 1) / 2.0) * 1.0
-    period = np.broadcast_to(np.asarray(getattr(ar, "_period", 1.0), np.float64), (nsub,))
-    tsub = float(getattr(ar, "_tsubint", 10.0))
+    period = np.broadcast_to(np.asarray(m["period"], np.float64), (nsub,))
+    tsub = m["tsubint"]
     cols = [("TSUBINT", "1D", None, (nsub,), np.full(nsub, tsub)),
             ("OFFS_SUB", "1D", None, (nsub,), (np.arange(nsub) + 0.5) * tsub),
             ("PERIOD", "1D", None, (nsub,), period),
             ("DAT_FREQ", "%dD" % nchan, None, (nsub, nchan), np.broadcast_to(freqs, (nsub, nchan))),
-            ("DAT_WTS", "%dE" % nchan, None, (nsub, nchan), ar._weights),
+            ("DAT_WTS", "%dE" % nchan, None, (nsub, nchan), m["weights"]),
             ("DAT_OFFS", "%dE" % (nchan * npol), None, (nsub, npol * nchan), offs.reshape(nsub, -1)),
             ("DAT_SCL", "%dE" % (nchan * npol), None, (nsub, npol * nchan), scl.reshape(nsub, -1)),
             ("DATA", "%dI" % (nbin * nchan * npol), "(%d,%d,%d)" % (nbin, nchan, npol),
              (nsub, npol * nchan * nbin), qd.reshape(nsub, -1)),
-            ("IC_SHIFT", "%dJ" % nchan, None, (nsub, nchan), np.broadcast_to(ar._shift, (nsub, nchan)))]
-    if getattr(ar, "_delay", None) is not None:
-        cols.append(("IC_DELAY", "%dD" % nchan, None, (nsub, nchan), np.broadcast_to(ar._delay, (nsub, nchan))))
+            ("IC_SHIFT", "%dJ" % nchan, None, (nsub, nchan), np.broadcast_to(m["shift"], (nsub, nchan)))]
+    if m["delay"] is not None:
+        cols.append(("IC_DELAY", "%dD" % nchan, None, (nsub, nchan), np.broadcast_to(m["delay"], (nsub, nchan))))
     if not stand_in_meta:
         cols = cols[:8]
     fields = []
@@ -183,13 +230,13 @@ def save(ar, path: str, stand_in_meta: bool = True) -> None:
     rows = np.zeros(nsub, dtype=dt)
     for name, form, _, shape, val in cols:
         rows[name] = np.asarray(val).reshape(shape)
-    mjd0 = float(ar.start_time().in_days())
+    mjd0 = m["mjd_start"]
     imjd = int(np.floor(mjd0))
     smjd = (mjd0 - imjd) * 86400.0
-    pol_type = STATE_POL_TYPE.get(ar.get_state(), "AABB")
+    pol_type = STATE_POL_TYPE.get(m["state"], "AABB")
     primary = [("SIMPLE", True), ("BITPIX", 8), ("NAXIS", 0), ("EXTEND", True),
                ("FITSTYPE", "PSRFITS"), ("HDRVER", "6.1"), ("OBS_MODE", "PSR"),
-               ("TELESCOP", "SYNTH"), ("SRC_NAME", ar.get_source()), ("OBSFREQ", cfreq),
+               ("TELESCOP", "SYNTH"), ("SRC_NAME", m["source"]), ("OBSFREQ", cfreq),
                ("OBSBW", float(nchan)), ("OBSNCHAN", nchan), ("STT_IMJD", imjd),
                ("STT_SMJD", int(smjd)), ("STT_OFFS", smjd - int(smjd))]
     sub = [("XTENSION", "BINTABLE"), ("BITPIX", 8), ("NAXIS", 2), ("NAXIS1", dt.itemsize),
@@ -201,10 +248,9 @@ def save(ar, path: str, stand_in_meta: bool = True) -> None:
             sub.append(("TDIM%d" % i, tdim))
     sub += [("EXTNAME", "SUBINT"), ("INT_TYPE", "TIME"), ("INT_UNIT", "SEC"), ("NPOL", npol),
             ("POL_TYPE", pol_type), ("NBIN", nbin), ("NCHAN", nchan), ("CHAN_BW", 1.0),
-            ("DM", float(getattr(ar, "_dm", 0.0))), ("RM", 0.0), ("NCHNOFFS", 0), ("NSBLK", 1)]
+            ("DM", m["dm"]), ("RM", 0.0), ("NCHNOFFS", 0), ("NSBLK", 1)]
     if stand_in_meta:
-        sub += [("IC_DEDSP", bool(ar.get_dedispersed())), ("IC_DUTY", float(ar.get_baseline_duty())),
-                ("IC_MJDE", float(ar.end_time().in_days()))]
+        sub += [("IC_DEDSP", m["dedispersed"]), ("IC_DUTY", m["baseline_duty"]), ("IC_MJDE", m["mjd_end"])]
     body = rows.tobytes()
     with open(path, "wb") as fh:
         fh.write(_header(primary))

@@ -13,6 +13,7 @@
 #include <sched.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -55,6 +56,87 @@ int failed_session()
             return fail(IC_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
                         __LINE__);                                                                \
     } while (0)
+
+// the entry points that report a HIP error under their own name (`bad`: the
+// error -> their return code)
+#define CKF(call, bad)                        \
+    do {                                      \
+        const hipError_t e_ = (call);         \
+        if (e_ != hipSuccess) return bad(e_); \
+    } while (0)
+
+int named_fail(const char *name, hipError_t e, bool oom_is_enomem = false)
+{
+    if (oom_is_enomem && e == hipErrorOutOfMemory) return fail(IC_ENOMEM, "%s: device allocation failed", name);
+    return fail(IC_EHIP, "%s: %s", name, hipGetErrorString(e));
+}
+
+// The owner of device buffers: every hipMalloc and hipFree of this file.  A
+// buffer is added with one alloc() line and freed with its arena.  Buffers
+// are registered by value, not by the address of the pointer handed in: the
+// session swaps and aliases its pointers.
+struct DeviceArena {
+    std::vector<void *> bufs;
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena &) = delete;
+    DeviceArena &operator=(const DeviceArena &) = delete;
+    ~DeviceArena() { free_all(); }
+    hipError_t alloc_bytes(void **p, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) *p = nullptr;
+        else if (*p) bufs.push_back(*p);
+        return e;
+    }
+    // n elements + 16 bytes of padding; exact: no padding (the delays, the per-call
+    // buffers); ensure: a buffer allocated at first need
+    template <typename T> hipError_t alloc(T **p, size_t n) { return alloc_bytes((void **)p, n * sizeof(T) + 16); }
+    template <typename T> hipError_t alloc_exact(T **p, size_t n) { return alloc_bytes((void **)p, n * sizeof(T)); }
+    template <typename T> hipError_t ensure(T **p, size_t n) { return *p ? hipSuccess : alloc(p, n); }
+    template <typename T> void release(T *&p)   // one buffer, early
+    {
+        const auto it = std::find(bufs.begin(), bufs.end(), (void *)p);
+        if (it != bufs.end()) {
+            (void)hipFree(*it);
+            bufs.erase(it);
+        }
+        p = nullptr;
+    }
+    void free_all()
+    {
+        for (void *b : bufs) (void)hipFree(b);
+        bufs.clear();
+    }
+    void abandon() { bufs.clear(); }   // leak on purpose (a failed session's buffers may be in use)
+};
+
+// The one-shot entry points' buffers and private stream, and per-call
+// temporaries of a session: gone when the call returns, on every path.
+struct Scratch {
+    DeviceArena mem;
+    hipStream_t stream = nullptr;
+    hipError_t open_stream() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    ~Scratch()
+    {
+        mem.free_all();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+int select_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    CK(hipSetDevice(device));
+    return IC_OK;
+}
+
+int check_q_flags(int flags)
+{
+    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    return IC_OK;
+}
 
 const char *kKernelNames[K_COUNT] = {"k_chan_partials", "k_window",    "k_base",
                                      "k_fscrunch",      "k_tscrunch",  "k_fit_pass", "k_fit_state",
@@ -102,7 +184,9 @@ struct Session {
     double *std_r = nullptr, *mean_r = nullptr, *fft_r = nullptr;   // owned rows [rows_own][nchan_g]
     double *ptp_r = nullptr;
     uint8_t *valid_r = nullptr;
-    // device buffers
+    // device buffers: owned by `mem`, but for the exchange buffers and a shard's
+    // counters (the transport's: comm->alloc / comm->release)
+    DeviceArena mem;
     float *raw = nullptr, *D = nullptr, *w0 = nullptr, *W = nullptr, *base = nullptr, *base0 = nullptr;
     // input slots (raw/w0/shift alias slot `cur`); slot 1 is allocated by the first
     // ic_upload_async that needs it.  Pending async uploads queue in `fifo`.
@@ -218,12 +302,6 @@ struct Session {
     double kms[K_COUNT] = {0};
     int klaunch[K_COUNT] = {0};
 };
-
-template <typename T>
-hipError_t dalloc(T **p, size_t n)
-{
-    return hipMalloc((void **)p, n * sizeof(T) + 16);
-}
 
 // numpy pairwise plan (loops_utils.h.src): leaves <= 128 in address order
 int plan_build(std::vector<int> &ls, std::vector<int> &ll, std::vector<int> &oa, std::vector<int> &ob,
@@ -377,6 +455,21 @@ static hipError_t spin_sync(Session *s)
         }                                                                      \
     } while (0)
 
+// exp(-2 pi i num / den), rounded from long double
+double2 unit_root(long double num, long double den)
+{
+    const long double a = -2.0L * 3.141592653589793238462643383279502884L * num / den;
+    return make_double2((double)cosl(a), (double)sinl(a));
+}
+
+// the DFT twiddles [nbin] exp(-2 pi i q / nbin)
+std::vector<double2> host_twiddles(int nbin)
+{
+    std::vector<double2> tw(nbin);
+    for (int q = 0; q < nbin; ++q) tw[q] = unit_root((long double)q, (long double)nbin);
+    return tw;
+}
+
 // Twiddles of k_diag_p2 for nbin = N = 2^k: [M = N/2] exp(-2 pi i q/N) for the
 // real-FFT post-processing, then for every Stockham stage after the first (radix
 // R = 8 while >= 3 levels remain, then 4 or 2; Ns = product of earlier radices)
@@ -386,20 +479,15 @@ std::vector<double2> p2_twiddles(int N)
 {
     std::vector<double2> t;
     if (N < 4 || (N & (N - 1))) return t;
-    const long double pi = 3.141592653589793238462643383279502884L;
-    auto w = [&](long double num, long double den) {
-        const long double a = -2.0L * pi * num / den;
-        return make_double2((double)cosl(a), (double)sinl(a));
-    };
     const int M = N / 2;
-    for (int q = 0; q < M; ++q) t.push_back(w(q, N));
+    for (int q = 0; q < M; ++q) t.push_back(unit_root(q, N));
     int lg = 0;
     while ((1 << lg) < M) ++lg;
     for (int done = 0, Ns = 1; done < lg;) {
         const int rem = lg - done, R = rem >= 3 ? 8 : (rem == 2 ? 4 : 2);
         if (Ns > 1)
             for (int k = 0; k < Ns; ++k)
-                for (int r = 1; r < R; ++r) t.push_back(w((long double)r * k, (long double)R * Ns));
+                for (int r = 1; r < R; ++r) t.push_back(unit_root((long double)r * k, (long double)R * Ns));
         Ns *= R;
         done += R == 8 ? 3 : (R == 4 ? 2 : 1);
     }
@@ -423,30 +511,12 @@ int collect_timing(Session *s)
 
 void free_all(Session *s)
 {
-    for (int q = 0; q < 2; ++q) {
-        void *sb[] = {s->slot_raw[q], s->slot_w0[q], s->slot_shift[q], s->slot_q[q], s->slot_so[q],
-                      s->slot_ph[q], s->slot_dly[q]};
-        for (void *b : sb)
-            if (b) (void)hipFree(b);
-        if (s->slot_ev[q]) (void)hipEventDestroy(s->slot_ev[q]);
-    }
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     if (s->dstream) (void)hipStreamDestroy(s->dstream);
-    if (s->fork_ev) (void)hipEventDestroy(s->fork_ev);
-    if (s->join_ev) (void)hipEventDestroy(s->join_ev);
-    if (s->fork2_ev) (void)hipEventDestroy(s->fork2_ev);
-    void *bufs[] = {s->late, s->exA, s->exF, s->D,     s->W,   s->base, s->base0, s->F,   s->wf,
-                    s->T,    s->ptp,   s->hist, s->valid, s->win, s->info, s->comm ? nullptr : s->counters,
-                    s->part, s->wpart, s->T64,  s->amp, s->std_, s->mean, s->fft,  s->test,
-                    s->lstat, s->tw,   s->plan, s->fs_block, s->lists, s->rcount, s->tw_p2, s->part2,
-                    s->wflag, s->TT, s->dr, s->Tc, s->R, s->zbase, s->zshift, s->ph, s->T2, s->fs.U, s->tmark,
-                    s->dly, s->res_q, s->res_so};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    void *rbufs[] = {s->std_r, s->mean_r, s->fft_r, s->ptp_r, s->valid_r};
-    for (void *b : rbufs)
-        if (b) (void)hipFree(b);
-    if (s->comm) {
+    for (hipEvent_t ev : {s->slot_ev[0], s->slot_ev[1], s->fork_ev, s->join_ev, s->fork2_ev})
+        if (ev) (void)hipEventDestroy(ev);
+    s->mem.free_all();
+    if (s->comm) {   // the transport's buffers
         void *xbufs[] = {s->xw_send, s->xw_recv, s->xf_send, s->xf_recv, s->xwg_send, s->xwg_recv, s->xfg_send,
                          s->xfg_recv, s->xd_send, s->xd_recv, s->xr_send, s->xr_recv, s->counters};
         for (void *b : xbufs)
@@ -1025,9 +1095,7 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     std::vector<int32_t> cr(2 * world), rr(2 * world);
     if (const char *e = shard_layout(p.nsub, p.nchan, world, cr.data(), rr.data()))
         return fail(IC_EINVAL, "cannot shard nchan=%d over %d: %s", p.nchan, world, e);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
+    if (int rc = select_device(device)) return rc;
     Session *s = new Session();
     s->p = p;
     s->device = device;
@@ -1056,20 +1124,16 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     s->Ppad = ((s->P + 63) / 64) * 64;
     s->width = (int)(p.baseline_duty * (double)p.nbin);
     if (s->width < 1) s->width = 1;
-    int rc = 0;
     auto bail = [&](int code) {
         free_all(s);
         delete s;
         return code;
     };
-#define AL(ptr, n)                                                                                  \
-    do {                                                                                            \
-        if (dalloc(&(ptr), (n)) != hipSuccess) {                                                    \
-            rc = fail(IC_ENOMEM, "hipMalloc(%s, %zu elements) failed", #ptr, (size_t)(n));          \
-            return bail(rc);                                                                        \
-        }                                                                                           \
+#define AL(ptr, n)                                                                                    \
+    do {                                                                                              \
+        if (s->mem.alloc(&(ptr), (n)) != hipSuccess)                                                  \
+            return bail(fail(IC_ENOMEM, "hipMalloc(%s, %zu elements) failed", #ptr, (size_t)(n)));    \
     } while (0)
-    if (hipSetDevice(device) != hipSuccess) return bail(fail(IC_EHIP, "hipSetDevice(%d) failed", device));
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(IC_EHIP, "hipStreamCreate failed"));
     // the diagnostics fork's stream exists for every session it can serve
@@ -1245,7 +1309,7 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     if (exact) {
         // fit state: 21 double arrays + 5 four-byte arrays, each padded to 256 B
         const size_t dstride = ((P * 8 + 255) / 256) * 256, istride = ((P * 4 + 255) / 256) * 256;
-        if (hipMalloc(&s->fs_block, 21 * dstride + 5 * istride) != hipSuccess)
+        if (s->mem.alloc_bytes(&s->fs_block, 21 * dstride + 5 * istride) != hipSuccess)
             return bail(fail(IC_ENOMEM, "hipMalloc(fit state) failed"));
         char *b = (char *)s->fs_block;
         double **dp[] = {&s->fs.x,     &s->fs.fnorm, &s->fs.par,   &s->fs.delta,   &s->fs.diag, &s->fs.xnorm,
@@ -1257,15 +1321,10 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
         for (auto *q : ip) { *q = (int32_t *)b; b += istride; }
         s->fs.T64 = s->T64;
         // k_fit_prep's 4 scalars
-        if (dalloc(&s->fs.U, 8) != hipSuccess) return bail(fail(IC_ENOMEM, "hipMalloc(fit prep) failed"));
+        if (s->mem.alloc(&s->fs.U, 8) != hipSuccess) return bail(fail(IC_ENOMEM, "hipMalloc(fit prep) failed"));
     }
-    // twiddles exp(-2 pi i q / n) and the pairwise plan
-    std::vector<double2> tw(nbin);
-    for (int q = 0; q < nbin; ++q) {
-        const long double ang = -2.0L * 3.141592653589793238462643383279502884L * (long double)q / (long double)nbin;
-        tw[q] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    const std::vector<double2> tw2 = p2_twiddles(nbin);
+    // twiddles and the pairwise plan
+    const std::vector<double2> tw = host_twiddles(nbin), tw2 = p2_twiddles(nbin);
     PwPlan plan;
     if (make_plan(nbin, &plan) != 0) return bail(fail(IC_EINVAL, "pairwise plan too large for nbin=%d", nbin));
     s->plan_ub = std::max(plan.nleaf, plan.nops);
@@ -1370,12 +1429,45 @@ void ic_session_destroy(void *session)
         // kernels of this session may still be running (a wait timed out):
         // freeing their buffers could hand memory in use to another
         // allocation, and a synchronising free could hang; leak them
+        s->mem.abandon();
         delete s;
         return;
     }
     (void)hipSetDevice(s->device);
     free_all(s);
     delete s;
+}
+
+static int check_shifts(const Session *s, const int32_t *shift)
+{
+    for (int c = 0; c < s->nchan; ++c)
+        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    return IC_OK;
+}
+
+// the end of every synchronous upload: the archive is the session's current one
+static int finish_upload(Session *s)
+{
+    CK(hipStreamSynchronize(s->stream));
+    s->uploaded = true;
+    s->ran = false;
+    return IC_OK;
+}
+
+// The input slot of the next asynchronous upload, the one not holding the
+// newest data (after the queued upload, else after the current archive), made
+// ready: the second slot is allocated at first need, as are the copy stream
+// and the slot's event.
+static int async_slot(Session *s, int *target)
+{
+    const int t = s->fifo_n ? 1 - s->fifo[s->fifo_n - 1] : (s->ever_uploaded ? 1 - s->cur : s->cur);
+    if (s->mem.ensure(&s->slot_raw[t], s->N) != hipSuccess || s->mem.ensure(&s->slot_w0[t], s->P) != hipSuccess ||
+        s->mem.ensure(&s->slot_shift[t], (size_t)s->nchan) != hipSuccess)
+        return fail(IC_ENOMEM, "second input slot (%zu bytes) failed", sizeof(float) * (s->N + s->P));
+    if (!s->copy_stream) CK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    if (!s->slot_ev[t]) CK(hipEventCreateWithFlags(&s->slot_ev[t], hipEventDisableTiming));
+    *target = t;
+    return IC_OK;
 }
 
 int ic_upload(void *session, const float *cube, const float *w0, const int32_t *shift)
@@ -1385,16 +1477,12 @@ int ic_upload(void *session, const float *cube, const float *w0, const int32_t *
     if (s->failed) return failed_session();
     if (s->fifo_n) return fail(IC_ESTATE, "ic_upload with %d asynchronous upload(s) pending", s->fifo_n);
     CK(hipSetDevice(s->device));
-    for (int c = 0; c < s->nchan; ++c)
-        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = check_shifts(s, shift)) return rc;
     s->ever_uploaded = true;
     CK(hipMemcpyAsync(s->raw, cube, sizeof(float) * s->N, hipMemcpyHostToDevice, s->stream));
     CK(hipMemcpyAsync(s->w0, w0, sizeof(float) * s->P, hipMemcpyHostToDevice, s->stream));
     CK(hipMemcpyAsync(s->shift, shift, sizeof(int32_t) * s->nchan, hipMemcpyHostToDevice, s->stream));
-    CK(hipStreamSynchronize(s->stream));
-    s->uploaded = true;
-    s->ran = false;
-    return IC_OK;
+    return finish_upload(s);
 }
 
 int ic_upload_pols(void *session, const float *data, int npol, const float *w0, const int32_t *shift)
@@ -1405,34 +1493,29 @@ int ic_upload_pols(void *session, const float *data, int npol, const float *w0, 
     if (npol < 1) return fail(IC_EINVAL, "npol=%d", npol);
     if (s->fifo_n) return fail(IC_ESTATE, "ic_upload_pols with %d asynchronous upload(s) pending", s->fifo_n);
     CK(hipSetDevice(s->device));
-    for (int c = 0; c < s->nchan; ++c)
-        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = check_shifts(s, shift)) return rc;
     s->ever_uploaded = true;
     const size_t row = sizeof(float) * (size_t)s->nchan * s->p.nbin;   // one subint of one polarisation
     // pol 0 -> raw; pol 1 -> the fit-cube buffer as scratch (rebuilt, and re-zeroed, below),
     // or a temporary buffer when the session keeps no fit cube (fit_mode 1)
     CK(hipMemcpy2DAsync(s->raw, row, data, row * npol, row, s->p.nsub, hipMemcpyHostToDevice, s->stream));
     if (npol >= 2) {
+        const auto bad = [](hipError_t e) { return named_fail("ic_upload_pols", e); };
+        Scratch tmp;
         float *pol1 = s->D;
-        if (!pol1 && hipMalloc((void **)&pol1, sizeof(float) * s->N) != hipSuccess)
+        if (!pol1 && tmp.mem.alloc_exact(&pol1, s->N) != hipSuccess)
             return fail(IC_ENOMEM, "hipMalloc(pol1 scratch, %zu floats) failed", s->N);
-        hipError_t e = hipMemcpy2DAsync(pol1, row, (const char *)data + row, row * npol, row, s->p.nsub,
-                                        hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) e = launch_pscrunch(s->stream, s->raw, pol1, s->N, s->grid_cap);
-        if (e == hipSuccess && s->D)
-            e = hipMemsetAsync(s->D, 0, sizeof(float) * s->Ppad * (size_t)s->ldD, s->stream);
-        if (!s->D) {
-            if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-            (void)hipFree(pol1);
-        }
-        if (e != hipSuccess) return fail(IC_EHIP, "ic_upload_pols: %s", hipGetErrorString(e));
+        CKF(hipMemcpy2DAsync(pol1, row, (const char *)data + row, row * npol, row, s->p.nsub, hipMemcpyHostToDevice,
+                             s->stream), bad);
+        CKF(launch_pscrunch(s->stream, s->raw, pol1, s->N, s->grid_cap), bad);
+        if (s->D)
+            CKF(hipMemsetAsync(s->D, 0, sizeof(float) * s->Ppad * (size_t)s->ldD, s->stream), bad);
+        else
+            CKF(hipStreamSynchronize(s->stream), bad);   // pscrunch has read pol1 before tmp frees it
     }
     CK(hipMemcpyAsync(s->w0, w0, sizeof(float) * s->P, hipMemcpyHostToDevice, s->stream));
     CK(hipMemcpyAsync(s->shift, shift, sizeof(int32_t) * s->nchan, hipMemcpyHostToDevice, s->stream));
-    CK(hipStreamSynchronize(s->stream));
-    s->uploaded = true;
-    s->ran = false;
-    return IC_OK;
+    return finish_upload(s);
 }
 
 int ic_upload_device(void *session, const float *d_cube, const float *d_w0, const int32_t *d_shift)
@@ -1446,10 +1529,7 @@ int ic_upload_device(void *session, const float *d_cube, const float *d_w0, cons
     CK(hipMemcpyAsync(s->raw, d_cube, sizeof(float) * s->N, hipMemcpyDeviceToDevice, s->stream));
     CK(hipMemcpyAsync(s->w0, d_w0, sizeof(float) * s->P, hipMemcpyDeviceToDevice, s->stream));
     CK(hipMemcpyAsync(s->shift, d_shift, sizeof(int32_t) * s->nchan, hipMemcpyDeviceToDevice, s->stream));
-    CK(hipStreamSynchronize(s->stream));
-    s->uploaded = true;
-    s->ran = false;
-    return IC_OK;
+    return finish_upload(s);
 }
 
 int ic_upload_async(void *session, const float *cube, const float *w0, const int32_t *shift)
@@ -1458,18 +1538,10 @@ int ic_upload_async(void *session, const float *cube, const float *w0, const int
     if (!s || !cube || !w0 || !shift) return fail(IC_EINVAL, "null argument");
     if (s->failed) return failed_session();
     if (s->fifo_n == 2) return fail(IC_ESTATE, "two asynchronous uploads already pending (run one first)");
-    for (int c = 0; c < s->nchan; ++c)
-        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = check_shifts(s, shift)) return rc;
     CK(hipSetDevice(s->device));
-    // the slot not holding the newest data: after the queued upload, else after the current archive
-    const int target = s->fifo_n ? 1 - s->fifo[s->fifo_n - 1] : (s->ever_uploaded ? 1 - s->cur : s->cur);
-    if (!s->slot_raw[target]) {
-        if (dalloc(&s->slot_raw[target], s->N) != hipSuccess || dalloc(&s->slot_w0[target], s->P) != hipSuccess ||
-            dalloc(&s->slot_shift[target], (size_t)s->nchan) != hipSuccess)
-            return fail(IC_ENOMEM, "second input slot (%zu bytes) failed", sizeof(float) * (s->N + s->P));
-    }
-    if (!s->copy_stream) CK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    if (!s->slot_ev[target]) CK(hipEventCreateWithFlags(&s->slot_ev[target], hipEventDisableTiming));
+    int target = 0;
+    if (int rc = async_slot(s, &target)) return rc;
     CK(hipMemcpyAsync(s->slot_raw[target], cube, sizeof(float) * s->N, hipMemcpyHostToDevice, s->copy_stream));
     CK(hipMemcpyAsync(s->slot_w0[target], w0, sizeof(float) * s->P, hipMemcpyHostToDevice, s->copy_stream));
     CK(hipMemcpyAsync(s->slot_shift[target], shift, sizeof(int32_t) * s->nchan, hipMemcpyHostToDevice,
@@ -1487,8 +1559,7 @@ static int q_check_args(const void *q, const float *scl, const float *offs, int 
     if (npol < 1) return fail(IC_EINVAL, "npol=%d", npol);
     if (nsum != 1 && nsum != 2) return fail(IC_EINVAL, "nsum=%d (1: pol 0, 2: pol 0 + pol 1)", nsum);
     if (nsum > npol) return fail(IC_EINVAL, "nsum=%d > npol=%d", nsum, npol);
-    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
-    return IC_OK;
+    return check_q_flags(flags);
 }
 
 // the first nsum polarisations of every subint of host[nsub][npol][row bytes]
@@ -1505,18 +1576,13 @@ static hipError_t q_copy_pols(void *dev, const void *host, size_t row, int nsub,
 static int q_stage(Session *s, int slot, int nsum)
 {
     if (s->slot_qsum[slot] >= nsum) return IC_OK;
-    if (s->slot_q[slot]) (void)hipFree(s->slot_q[slot]);
-    if (s->slot_so[slot]) (void)hipFree(s->slot_so[slot]);
-    s->slot_q[slot] = nullptr;
-    s->slot_so[slot] = nullptr;
+    s->mem.release(s->slot_q[slot]);
+    s->mem.release(s->slot_so[slot]);
     s->slot_qsum[slot] = 0;
-    if (dalloc(&s->slot_q[slot], s->N * nsum) != hipSuccess || dalloc(&s->slot_so[slot], s->P * 2 * nsum) != hipSuccess) {
-        if (s->slot_q[slot]) (void)hipFree(s->slot_q[slot]);
-        s->slot_q[slot] = nullptr;
-        s->slot_so[slot] = nullptr;
+    if (s->mem.alloc(&s->slot_q[slot], s->N * nsum) != hipSuccess ||
+        s->mem.alloc(&s->slot_so[slot], s->P * 2 * nsum) != hipSuccess)
         return fail(IC_ENOMEM, "quantised staging (%zu bytes) failed",
                     (size_t)nsum * (sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P));
-    }
     s->slot_qsum[slot] = nsum;
     return IC_OK;
 }
@@ -1546,15 +1612,11 @@ int ic_upload_quantised(void *session, const int16_t *q, const float *scl, const
     if (s->failed) return failed_session();
     if (s->fifo_n) return fail(IC_ESTATE, "ic_upload_quantised with %d asynchronous upload(s) pending", s->fifo_n);
     CK(hipSetDevice(s->device));
-    for (int c = 0; c < s->nchan; ++c)
-        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = check_shifts(s, shift)) return rc;
     if (int rc = q_stage(s, s->cur, nsum)) return rc;
     s->ever_uploaded = true;
     if (int rc = q_enqueue(s, s->cur, s->stream, q, scl, offs, npol, nsum, flags, w0, shift)) return rc;
-    CK(hipStreamSynchronize(s->stream));
-    s->uploaded = true;
-    s->ran = false;
-    return IC_OK;
+    return finish_upload(s);
 }
 
 int ic_upload_quantised_async(void *session, const int16_t *q, const float *scl, const float *offs, int npol, int nsum,
@@ -1565,19 +1627,11 @@ int ic_upload_quantised_async(void *session, const int16_t *q, const float *scl,
     if (int rc = q_check_args(q, scl, offs, npol, nsum, flags)) return rc;
     if (s->failed) return failed_session();
     if (s->fifo_n == 2) return fail(IC_ESTATE, "two asynchronous uploads already pending (run one first)");
-    for (int c = 0; c < s->nchan; ++c)
-        if (shift[c] < 0 || shift[c] >= s->p.nbin) return fail(IC_EINVAL, "shift[%d]=%d out of [0,nbin)", c, shift[c]);
+    if (int rc = check_shifts(s, shift)) return rc;
     CK(hipSetDevice(s->device));
-    // the slot rule of ic_upload_async
-    const int target = s->fifo_n ? 1 - s->fifo[s->fifo_n - 1] : (s->ever_uploaded ? 1 - s->cur : s->cur);
-    if (!s->slot_raw[target]) {
-        if (dalloc(&s->slot_raw[target], s->N) != hipSuccess || dalloc(&s->slot_w0[target], s->P) != hipSuccess ||
-            dalloc(&s->slot_shift[target], (size_t)s->nchan) != hipSuccess)
-            return fail(IC_ENOMEM, "second input slot (%zu bytes) failed", sizeof(float) * (s->N + s->P));
-    }
+    int target = 0;
+    if (int rc = async_slot(s, &target)) return rc;
     if (int rc = q_stage(s, target, nsum)) return rc;
-    if (!s->copy_stream) CK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    if (!s->slot_ev[target]) CK(hipEventCreateWithFlags(&s->slot_ev[target], hipEventDisableTiming));
     // the decode runs on the copy stream behind its copies and slot_ev follows
     // it: ic_run waits for a decoded cube as it waits for an f32 copy
     if (int rc = q_enqueue(s, target, s->copy_stream, q, scl, offs, npol, nsum, flags, w0, shift)) return rc;
@@ -1593,31 +1647,23 @@ int ic_decode_profiles(int device, int nsub, int npol, int nsum, int nchan, int 
     if (!out) return fail(IC_EINVAL, "null argument");
     if (int rc = q_check_args(q, scl, offs, npol, nsum, flags)) return rc;
     if (nsub <= 0 || nchan <= 0 || nbin <= 0) return fail(IC_EINVAL, "bad shape (%d, %d, %d)", nsub, nchan, nbin);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    CK(hipSetDevice(device));
+    if (int rc = select_device(device)) return rc;
     const size_t P = (size_t)nsub * nchan, N = P * nbin;
+    const auto bad = [](hipError_t e) { return named_fail("ic_decode_profiles", e, true); };
+    Scratch sc;
     int16_t *dq = nullptr;
     float *dso = nullptr, *d = nullptr;
-    hipStream_t st = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&dq, sizeof(int16_t) * N * nsum);
-    if (e == hipSuccess) e = hipMalloc((void **)&dso, sizeof(float) * P * 2 * nsum);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, sizeof(float) * N);
-    if (e == hipSuccess) e = q_copy_pols(dq, q, sizeof(int16_t) * (size_t)nchan * nbin, nsub, npol, nsum, st);
-    if (e == hipSuccess) e = q_copy_pols(dso, scl, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st);
-    if (e == hipSuccess) e = q_copy_pols(dso + P * nsum, offs, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st);
-    if (e == hipSuccess)
-        e = launch_decode_q(st, dq, dso, dso + P * nsum, nsub, nchan, nbin, nsum, (flags & IC_Q_BIG_ENDIAN) != 0, d);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(float) * N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (dq) (void)hipFree(dq);
-    if (dso) (void)hipFree(dso);
-    if (d) (void)hipFree(d);
-    if (st) (void)hipStreamDestroy(st);
-    if (e == hipErrorOutOfMemory) return fail(IC_ENOMEM, "ic_decode_profiles: device allocation failed");
-    if (e != hipSuccess) return fail(IC_EHIP, "ic_decode_profiles: %s", hipGetErrorString(e));
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    CKF(sc.mem.alloc_exact(&dq, N * nsum), bad);
+    CKF(sc.mem.alloc_exact(&dso, P * 2 * nsum), bad);
+    CKF(sc.mem.alloc_exact(&d, N), bad);
+    CKF(q_copy_pols(dq, q, sizeof(int16_t) * (size_t)nchan * nbin, nsub, npol, nsum, st), bad);
+    CKF(q_copy_pols(dso, scl, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st), bad);
+    CKF(q_copy_pols(dso + P * nsum, offs, sizeof(float) * (size_t)nchan, nsub, npol, nsum, st), bad);
+    CKF(launch_decode_q(st, dq, dso, dso + P * nsum, nsub, nchan, nbin, nsum, (flags & IC_Q_BIG_ENDIAN) != 0, d), bad);
+    CKF(hipMemcpyAsync(out, d, sizeof(float) * N, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
     return IC_OK;
 }
 
@@ -1752,10 +1798,8 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     if (s->events.size() > 4096)
         if (int rc = collect_timing(s)) return rc;
     if (s->fftded && !s->delays_set) return fail(IC_ESTATE, "ic_run before ic_set_delays (dedisp_mode FFT)");
-    if (s->fftded && !rot_stats_on(s) && !s->R && dalloc(&s->R, s->N) != hipSuccess) {
-        s->R = nullptr;
+    if (s->fftded && !rot_stats_on(s) && s->mem.ensure(&s->R, s->N) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(R: %zu floats) failed", s->N);
-    }
     // the second fork's tail marks are cleared at the end of each iteration; a
     // run that failed in between may have left some set
     if (s->tmark) CK(hipMemsetAsync(s->tmark, 0, s->P, s->stream));
@@ -1949,14 +1993,13 @@ int ic_get_residual(void *session, float *out)
     if (s->failed) return failed_session();
     if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
     CK(hipSetDevice(s->device));
-    // temporary output buffer
+    const auto bad = [](hipError_t e) { return named_fail("residual", e); };
+    Scratch tmp;   // the output cube; freed after the synchronise below
     float *R = nullptr;
-    CK(hipMalloc((void **)&R, sizeof(float) * s->N));
-    hipError_t e = launch_residual_cube(s, R);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, R, sizeof(float) * s->N, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    (void)hipFree(R);
-    if (e != hipSuccess) return fail(IC_EHIP, "residual: %s", hipGetErrorString(e));
+    CK(tmp.mem.alloc_exact(&R, s->N));
+    CKF(launch_residual_cube(s, R), bad);
+    CKF(hipMemcpyAsync(out, R, sizeof(float) * s->N, hipMemcpyDeviceToHost, s->stream), bad);
+    CKF(hipStreamSynchronize(s->stream), bad);
     return IC_OK;
 }
 
@@ -1964,35 +2007,27 @@ int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, 
 {
     Session *s = (Session *)session;
     if (!s || !q || !scl || !offs) return fail(IC_EINVAL, "null argument");
-    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    if (int rc = check_q_flags(flags)) return rc;
     if (s->failed) return failed_session();
     if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
     CK(hipSetDevice(s->device));
     // the encoded residual's staging: first use, kept until ic_session_destroy
-    if (!s->res_q) {
-        if (dalloc(&s->res_q, s->N) != hipSuccess || dalloc(&s->res_so, 2 * s->P) != hipSuccess) {
-            if (s->res_q) (void)hipFree(s->res_q);
-            s->res_q = nullptr;
-            s->res_so = nullptr;
-            return fail(IC_ENOMEM, "quantised residual staging (%zu bytes) failed",
-                        sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P);
-        }
-    }
+    if (s->mem.ensure(&s->res_q, s->N) != hipSuccess || s->mem.ensure(&s->res_so, 2 * s->P) != hipSuccess)
+        return fail(IC_ENOMEM, "quantised residual staging (%zu bytes) failed",
+                    sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P);
     // the f32 cube stays a per-call temporary, as in ic_get_residual
+    const auto bad = [](hipError_t e) { return named_fail("quantised residual", e); };
+    Scratch tmp;
     float *R = nullptr;
-    if (hipMalloc((void **)&R, sizeof(float) * s->N) != hipSuccess)
+    if (tmp.mem.alloc_exact(&R, s->N) != hipSuccess)
         return fail(IC_ENOMEM, "residual cube (%zu bytes) failed", sizeof(float) * s->N);
-    hipError_t e = launch_residual_cube(s, R);
-    if (e == hipSuccess)
-        e = launch_encode_q(s->stream, R, (int)s->P, s->p.nbin, (flags & IC_Q_BIG_ENDIAN) != 0, s->res_q, s->res_so,
-                            s->res_so + s->P, s->grid_cap);
-    if (e == hipSuccess) e = hipMemcpyAsync(q, s->res_q, sizeof(int16_t) * s->N, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(scl, s->res_so, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(offs, s->res_so + s->P, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    (void)hipFree(R);
-    if (e != hipSuccess) return fail(IC_EHIP, "quantised residual: %s", hipGetErrorString(e));
+    CKF(launch_residual_cube(s, R), bad);
+    CKF(launch_encode_q(s->stream, R, (int)s->P, s->p.nbin, (flags & IC_Q_BIG_ENDIAN) != 0, s->res_q, s->res_so,
+                        s->res_so + s->P, s->grid_cap), bad);
+    CKF(hipMemcpyAsync(q, s->res_q, sizeof(int16_t) * s->N, hipMemcpyDeviceToHost, s->stream), bad);
+    CKF(hipMemcpyAsync(scl, s->res_so, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream), bad);
+    CKF(hipMemcpyAsync(offs, s->res_so + s->P, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream), bad);
+    CKF(hipStreamSynchronize(s->stream), bad);
     return IC_OK;
 }
 
@@ -2000,33 +2035,26 @@ int ic_encode_profiles(int device, int nsub, int nchan, int nbin, const float *i
                        float *scl, float *offs)
 {
     if (!in || !q || !scl || !offs) return fail(IC_EINVAL, "null argument");
-    if (flags & ~IC_Q_BIG_ENDIAN) return fail(IC_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IC_Q_BIG_ENDIAN));
+    if (int rc = check_q_flags(flags)) return rc;
     if (nsub <= 0 || nchan <= 0 || nbin <= 0 || (size_t)nsub * nchan > (size_t)INT32_MAX)
         return fail(IC_EINVAL, "bad shape (%d, %d, %d)", nsub, nchan, nbin);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    CK(hipSetDevice(device));
+    if (int rc = select_device(device)) return rc;
     const size_t P = (size_t)nsub * nchan, N = P * nbin;
+    const auto bad = [](hipError_t e) { return named_fail("ic_encode_profiles", e, true); };
+    Scratch sc;
     float *d = nullptr, *dso = nullptr;
     int16_t *dq = nullptr;
-    hipStream_t st = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, sizeof(float) * N);
-    if (e == hipSuccess) e = hipMalloc((void **)&dq, sizeof(int16_t) * N);
-    if (e == hipSuccess) e = hipMalloc((void **)&dso, sizeof(float) * P * 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_encode_q(st, d, (int)P, nbin, (flags & IC_Q_BIG_ENDIAN) != 0, dq, dso, dso + P);
-    if (e == hipSuccess) e = hipMemcpyAsync(q, dq, sizeof(int16_t) * N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(scl, dso, sizeof(float) * P, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(offs, dso + P, sizeof(float) * P, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d) (void)hipFree(d);
-    if (dq) (void)hipFree(dq);
-    if (dso) (void)hipFree(dso);
-    if (st) (void)hipStreamDestroy(st);
-    if (e == hipErrorOutOfMemory) return fail(IC_ENOMEM, "ic_encode_profiles: device allocation failed");
-    if (e != hipSuccess) return fail(IC_EHIP, "ic_encode_profiles: %s", hipGetErrorString(e));
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    CKF(sc.mem.alloc_exact(&d, N), bad);
+    CKF(sc.mem.alloc_exact(&dq, N), bad);
+    CKF(sc.mem.alloc_exact(&dso, P * 2), bad);
+    CKF(hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st), bad);
+    CKF(launch_encode_q(st, d, (int)P, nbin, (flags & IC_Q_BIG_ENDIAN) != 0, dq, dso, dso + P), bad);
+    CKF(hipMemcpyAsync(q, dq, sizeof(int16_t) * N, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipMemcpyAsync(scl, dso, sizeof(float) * P, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipMemcpyAsync(offs, dso + P, sizeof(float) * P, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
     return IC_OK;
 }
 
@@ -2041,10 +2069,7 @@ int ic_set_delays(void *session, const double *delay_bins)
     CK(hipSetDevice(s->device));
     // the table is built on the device (k_phasor_table), as an attached
     // upload's is: one code path
-    if (!s->dly && hipMalloc((void **)&s->dly, sizeof(double) * s->P) != hipSuccess) {
-        s->dly = nullptr;
-        return fail(IC_ENOMEM, "hipMalloc(delays) failed");
-    }
+    if (!s->dly && s->mem.alloc_exact(&s->dly, s->P) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(delays) failed");
     s->delay2 = nullptr;   // dly holds the channel row from here on
     s->delays_set = false;
     CK(hipMemcpyAsync(s->dly, delay_bins, sizeof(double) * s->nchan, hipMemcpyHostToDevice, s->stream));
@@ -2077,15 +2102,11 @@ int ic_upload_delays_async(void *session, const double *delay_bins, int per_prof
             table = memcmp(delay_bins, delay_bins + (size_t)sb * nchan, sizeof(double) * nchan) == 0;
     }
     CK(hipSetDevice(s->device));
-    if (!s->slot_dly[slot] && hipMalloc((void **)&s->slot_dly[slot], sizeof(double) * s->P) != hipSuccess) {
-        s->slot_dly[slot] = nullptr;
+    if (!s->slot_dly[slot] && s->mem.alloc_exact(&s->slot_dly[slot], s->P) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(slot delays, %zu bytes) failed", sizeof(double) * s->P);
-    }
-    if (table && !s->slot_ph[slot] && dalloc(&s->slot_ph[slot], 2 * (size_t)nchan * (s->p.nbin / 2 + 1)) != hipSuccess) {
-        s->slot_ph[slot] = nullptr;
+    if (table && s->mem.ensure(&s->slot_ph[slot], 2 * (size_t)nchan * (s->p.nbin / 2 + 1)) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(slot phasor table, %zu bytes) failed",
                     sizeof(float) * 2 * (size_t)nchan * (s->p.nbin / 2 + 1));
-    }
     // behind the upload's copies on the copy stream; the slot's event moves
     // behind the delays' copy and the table kernel, so ic_run waits for both
     CK(hipMemcpyAsync(s->slot_dly[slot], delay_bins, sizeof(double) * (table ? (size_t)nchan : s->P),
@@ -2112,10 +2133,8 @@ int ic_set_delays2(void *session, const double *delay_bins)
         rows_equal = memcmp(delay_bins, delay_bins + (size_t)sb * nchan, sizeof(double) * nchan) == 0;
     if (rows_equal) return ic_set_delays(session, delay_bins);
     CK(hipSetDevice(s->device));
-    if (!s->dly && hipMalloc((void **)&s->dly, sizeof(double) * s->P) != hipSuccess) {
-        s->dly = nullptr;
+    if (!s->dly && s->mem.alloc_exact(&s->dly, s->P) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(per-profile delays) failed");
-    }
     CK(hipMemcpyAsync(s->dly, delay_bins, sizeof(double) * s->P, hipMemcpyHostToDevice, s->stream));
     CK(hipStreamSynchronize(s->stream));
     s->delay2 = s->dly;
@@ -2137,60 +2156,45 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
     const size_t nd = per_profile ? (size_t)nsub * nchan : (size_t)nchan;
     for (size_t c = 0; c < nd; ++c)
         if (!isfinite(delay_bins[c])) return fail(IC_EINVAL, "delay[%zu] is not finite", c);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    CK(hipSetDevice(device));
+    if (int rc = select_device(device)) return rc;
     const size_t N = (size_t)nsub * nchan * nbin;
     const std::vector<float> ph = per_profile ? std::vector<float>(2) : make_phasors(nbin, nchan, delay_bins);
-    std::vector<double2> tw(nbin);
-    for (int q = 0; q < nbin; ++q) {
-        const long double ang = -2.0L * 3.141592653589793238462643383279502884L * (long double)q / (long double)nbin;
-        tw[q] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    const std::vector<double2> tw2 = p2_twiddles(nbin);   // the rotation's stage tables
-    float *d = nullptr;
-    float *dph = nullptr;
+    const std::vector<double2> tw = host_twiddles(nbin), tw2 = p2_twiddles(nbin);   // tw2: the rotation's stage tables
+    const auto bad = [](hipError_t e) { return named_fail("ic_rotate_profiles", e); };
+    Scratch sc;
+    float *d = nullptr, *dph = nullptr;
     double2 *dtw = nullptr, *dtw2 = nullptr;
     double *ddl = nullptr;
-    hipStream_t st = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, sizeof(float) * N);
-    if (e == hipSuccess && per_profile) e = hipMalloc((void **)&ddl, sizeof(double) * nd);
-    if (e == hipSuccess && per_profile)
-        e = hipMemcpyAsync(ddl, delay_bins, sizeof(double) * nd, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMalloc((void **)&dph, sizeof(float) * ph.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&dtw, sizeof(double2) * tw.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dph, ph.data(), sizeof(float) * ph.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dtw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMalloc((void **)&dtw2, sizeof(double2) * tw2.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        RotateArgs a{};
-        a.in = d;
-        a.ld_in = nbin;
-        a.ph = per_profile ? nullptr : dph;
-        a.delay2 = ddl;
-        a.sign = sign;
-        a.tw = dtw;
-        a.tw_p2 = dtw2;
-        a.nsub = nsub;
-        a.nchan = nchan;
-        a.nbin = nbin;
-        a.out = d;
-        a.ldo = nbin;
-        e = launch_rotate(st, a);
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    CKF(sc.mem.alloc_exact(&d, N), bad);
+    if (per_profile) {
+        CKF(sc.mem.alloc_exact(&ddl, nd), bad);
+        CKF(hipMemcpyAsync(ddl, delay_bins, sizeof(double) * nd, hipMemcpyHostToDevice, st), bad);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(float) * N, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d) (void)hipFree(d);
-    if (dph) (void)hipFree(dph);
-    if (dtw) (void)hipFree(dtw);
-    if (dtw2) (void)hipFree(dtw2);
-    if (ddl) (void)hipFree(ddl);
-    if (st) (void)hipStreamDestroy(st);
-    if (e != hipSuccess) return fail(IC_EHIP, "ic_rotate_profiles: %s", hipGetErrorString(e));
+    CKF(sc.mem.alloc_exact(&dph, ph.size()), bad);
+    CKF(sc.mem.alloc_exact(&dtw, tw.size()), bad);
+    CKF(hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dph, ph.data(), sizeof(float) * ph.size(), hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dtw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice, st), bad);
+    CKF(sc.mem.alloc_exact(&dtw2, tw2.size()), bad);
+    CKF(hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st), bad);
+    RotateArgs a{};
+    a.in = d;
+    a.ld_in = nbin;
+    a.ph = per_profile ? nullptr : dph;
+    a.delay2 = ddl;
+    a.sign = sign;
+    a.tw = dtw;
+    a.tw_p2 = dtw2;
+    a.nsub = nsub;
+    a.nchan = nchan;
+    a.nbin = nbin;
+    a.out = d;
+    a.ldo = nbin;
+    CKF(launch_rotate(st, a), bad);
+    CKF(hipMemcpyAsync(out, d, sizeof(float) * N, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
     return IC_OK;
 }
 }  // namespace
@@ -2391,49 +2395,35 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     if (nsub <= 0 || nchan <= 0 || nbin <= 0 || nsub > 16384 || nchan > 16384 || nbin > 32768)
         return fail(IC_EINVAL, "bad shape nsub=%d nchan=%d nbin=%d", nsub, nchan, nbin);
     if (diag_lds_bytes(nbin) > 160 * 1024) return fail(IC_EINVAL, "nbin=%d unsupported", nbin);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(IC_EHIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IC_EINVAL, "device %d out of range (%d devices)", device, ndev);
-    CK(hipSetDevice(device));
+    if (int rc = select_device(device)) return rc;
     const size_t P = (size_t)nsub * nchan, N = P * (size_t)nbin;
     PwPlan plan;
     if (make_plan(nbin, &plan) != 0) return fail(IC_EINVAL, "pairwise plan too large for nbin=%d", nbin);
-    std::vector<double2> tw(nbin);
-    for (int q = 0; q < nbin; ++q) {
-        const long double ang = -2.0L * 3.141592653589793238462643383279502884L * (long double)q / (long double)nbin;
-        tw[q] = make_double2((double)cosl(ang), (double)sinl(ang));
-    }
-    const std::vector<double2> tw2 = p2_twiddles(nbin);
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } bD, bw, bvalid, bW, bhist, bstd, bmean, bfft, bptp, btest, blstat, bcnt, btw, btw2, bplan;
-    hipStream_t st = nullptr;
-    CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StreamGuard {
-        hipStream_t s;
-        ~StreamGuard() { (void)hipStreamDestroy(s); }
-    } sg{st};
+    const std::vector<double2> tw = host_twiddles(nbin), tw2 = p2_twiddles(nbin);
+    Scratch sc;
+    CK(sc.open_stream());
+    hipStream_t st = sc.stream;
+    float *D, *w0, *W, *hist;
+    uint8_t *valid;
+    double *sd, *mn, *ff, *pt, *test, *lstat;
+    int32_t *cnt;
+    double2 *dtw, *dtw2;
+    PwPlan *dplan;
     struct {
-        Buf *b;
+        void **p;
         size_t bytes;
-    } al[] = {{&bD, 4 * N},       {&bw, 4 * P},      {&bvalid, P},      {&bW, 4 * P},
-              {&bhist, 8 * P},    {&bstd, 8 * P},    {&bmean, 8 * P},   {&bfft, 8 * P},
-              {&bptp, 8 * P},     {&btest, 8 * P},   {&blstat, 8 * 16 * ((size_t)nsub + nchan)},
-              {&bcnt, 4 * 8},     {&btw, 16 * (size_t)nbin}, {&btw2, 16 * (size_t)nbin + 16}, {&bplan, sizeof plan}};
+    } al[] = {{(void **)&D, 4 * N},     {(void **)&w0, 4 * P},   {(void **)&valid, P},  {(void **)&W, 4 * P},
+              {(void **)&hist, 8 * P},  {(void **)&sd, 8 * P},   {(void **)&mn, 8 * P}, {(void **)&ff, 8 * P},
+              {(void **)&pt, 8 * P},    {(void **)&test, 8 * P}, {(void **)&lstat, 8 * 16 * ((size_t)nsub + nchan)},
+              {(void **)&cnt, 4 * 8},   {(void **)&dtw, 16 * (size_t)nbin}, {(void **)&dtw2, 16 * (size_t)nbin + 16},
+              {(void **)&dplan, sizeof plan}};
     for (auto &x : al)
-        if (hipMalloc(&x.b->p, x.bytes + 16) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(%zu) failed", x.bytes);
-    float *D = (float *)bD.p, *w0 = (float *)bw.p, *W = (float *)bW.p, *hist = (float *)bhist.p;
-    uint8_t *valid = (uint8_t *)bvalid.p;
-    double *sd = (double *)bstd.p, *mn = (double *)bmean.p, *ff = (double *)bfft.p, *test = (double *)btest.p;
-    double *pt = (double *)bptp.p;
-    double *lstat = (double *)blstat.p;
-    int32_t *cnt = (int32_t *)bcnt.p;
+        if (sc.mem.alloc_bytes(x.p, x.bytes + 16) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(%zu) failed", x.bytes);
     CK(hipMemcpyAsync(D, data, 4 * N, hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(w0, weights, 4 * P, hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(btw.p, tw.data(), 16 * (size_t)nbin, hipMemcpyHostToDevice, st));
-    if (!tw2.empty()) CK(hipMemcpyAsync(btw2.p, tw2.data(), 16 * tw2.size(), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(bplan.p, &plan, sizeof plan, hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(dtw, tw.data(), 16 * (size_t)nbin, hipMemcpyHostToDevice, st));
+    if (!tw2.empty()) CK(hipMemcpyAsync(dtw2, tw2.data(), 16 * tw2.size(), hipMemcpyHostToDevice, st));
+    CK(hipMemcpyAsync(dplan, &plan, sizeof plan, hipMemcpyHostToDevice, st));
     CK(hipMemsetAsync(cnt, 0, 4 * 8, st));
     IC_GGL(k_valid, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, w0, valid, W, hist, P);
     CK(hipGetLastError());
@@ -2442,9 +2432,9 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     a.D = D;
     a.ldD = nbin;
     a.w0 = w0;
-    a.tw = (const double2 *)btw.p;
-    a.tw_p2 = (const double2 *)btw2.p;
-    a.plan = (const PwPlan *)bplan.p;
+    a.tw = dtw;
+    a.tw_p2 = dtw2;
+    a.plan = dplan;
     a.nsub = nsub;
     a.nchan = nchan;
     a.nbin = nbin;
@@ -2535,14 +2525,14 @@ int ic_fit_profiles(int device, int nprof, int nbin, const float *T, const float
     if (amp_out) CK(hipMemcpyAsync(amp_out, s->amp, sizeof(double) * nprof, hipMemcpyDeviceToHost, s->stream));
     if (info_out) CK(hipMemcpyAsync(info_out, s->info, sizeof(int32_t) * nprof, hipMemcpyDeviceToHost, s->stream));
     if (resid_out) {
+        const auto bad = [](hipError_t e) { return named_fail("ic_fit_profiles residual", e); };
+        Scratch tmp;
         float *R = nullptr;
-        CK(hipMalloc((void **)&R, sizeof(float) * s->N));
-        hipError_t e = launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub,
-                                       s->nchan, nbin, s->ldD, s->dtiled, 0, 1.0, 0, 0, R, s->grid_cap);
-        if (e == hipSuccess) e = hipMemcpyAsync(resid_out, R, row * nprof, hipMemcpyDeviceToHost, s->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        (void)hipFree(R);
-        if (e != hipSuccess) return fail(IC_EHIP, "ic_fit_profiles residual: %s", hipGetErrorString(e));
+        CK(tmp.mem.alloc_exact(&R, s->N));
+        CKF(launch_residual(s->stream, s->D, s->raw, s->base0, s->T64, s->amp, s->info, s->shift, p.nsub, s->nchan,
+                            nbin, s->ldD, s->dtiled, 0, 1.0, 0, 0, R, s->grid_cap), bad);
+        CKF(hipMemcpyAsync(resid_out, R, row * nprof, hipMemcpyDeviceToHost, s->stream), bad);
+        CKF(hipStreamSynchronize(s->stream), bad);   // before tmp frees R
     }
     CK(hipStreamSynchronize(s->stream));
     return IC_OK;

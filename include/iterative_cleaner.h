@@ -48,7 +48,9 @@ extern "C" {
  * (k_diag_p2 / k_diag_cl; at 8192 a profile is shared by eight waves), any
  * other length the generic k_diag, as far as its per-profile LDS need allows
  * (ic_session_create says how many bytes a refused length would take: every
- * power of two above 8192 is refused that way).  nsub, nchan <= 16384. */
+ * power of two above 8192 is refused that way).  With IC_DEDISP_FFT the
+ * length must also be one the rotation serves (see dedisp_mode below).
+ * nsub, nchan <= 16384. */
 typedef struct {
     int32_t nsub, nchan, nbin;
     int32_t max_iter;          /* -m                                          */
@@ -108,7 +110,15 @@ typedef struct {
  *                    irfft(rfft(x) * phasor); parity with real psrchive
  *                    unpinned).  nbin must be a power of
  *                    two in 64..8192 (either fit_mode, f32 or f64 data,
- *                    per-channel or per-profile delays); the shift arrays of the
+ *                    per-channel or per-profile delays), or a mixed-radix
+ *                    length: a multiple of 8 in 64..4096 whose half has only
+ *                    the prime factors 2, 3 and 5 (72, 96, 120, 200, 1000, 1200,
+ *                    1536, 2000, 3000, 4000, ...: IC_FIT_EXACT only, f32 or f64
+ *                    data, either kind of delays; the statistics of these
+ *                    lengths run in the generic diagnostics kernel, whose
+ *                    direct DFT dominates the clean).  Any other length, and
+ *                    IC_FIT_CLOSED at a mixed-radix length, is refused with
+ *                    IC_EINVAL by ic_session_create.  The shift arrays of the
  *                    uploads are then unused (pass zeros). */
 #define IC_DEDISP_SHIFT 0
 #define IC_DEDISP_FFT 1

@@ -20,7 +20,7 @@ order so that the HIP kernels can reproduce it bit-for-bit:
   with fractional delays ``dm_delay`` (f64 bins: ``[c]`` per channel, or
   ``[s, c]`` per profile - psrchive's per-Integration folding period) rotates
   instead by psrchive's FFT phase rotation, in the arithmetic order written in
-  :mod:`.phase_rotation` (power-of-two nbin); an archive stored dedispersed
+  :mod:`.phase_rotation` (power-of-two and mixed-radix nbin); an archive stored dedispersed
   (``dedispersed=True``) returns its samples as they are from the dedispersed
   view, and only ``dededisperse`` moves them;
 * channel sums (baseline total, fscrunch) use the CANONICAL CHANNEL ORDER
@@ -175,9 +175,9 @@ class Archive:
         self._shift = np.mod(np.asarray(dm_shift, dtype=np.int64), nbin).reshape(nchan)
         self._delay = None
         if dm_delay is not None:
-            from .phase_rotation import is_supported
+            from .phase_rotation import UNSUPPORTED, is_supported
             if not is_supported(nbin):
-                raise ValueError("fractional dedispersion needs a power-of-two nbin (got %d)" % nbin)
+                raise ValueError("fractional dedispersion %s (nbin=%d)" % (UNSUPPORTED, nbin))
             d = np.array(dm_delay, dtype=np.float64)
             self._delay = d.reshape((nsub, nchan) if d.ndim == 2 else (nchan,))
         self._dedispersed = bool(dedispersed)

@@ -272,6 +272,30 @@ inline bool p2_supported(int nbin)
     return false;
 }
 
+// The mixed-radix set MR of the rotation (k_rotate_mr; phase_rotation.py
+// mr_supported): kMrMin <= nbin <= kMrMax, a multiple of 8 (rows and half rows
+// stay 16-byte addressable: RotateArgs' strides are multiples of 4), nbin/2 =
+// 2^a 3^b 5^c, not a power of two (those are k_rotate<N>'s).  Like IC_P2_SIZES
+// this is the one place the set lives; the checks and error texts derive from
+// it.  The diagnostics of these lengths are the generic k_diag's.
+constexpr int kMrMin = 64, kMrMax = 4096;
+constexpr int kMrMaxStages = 12;            // Stockham stages of FFT_{nbin/2} (4096: 5)
+constexpr size_t kMrLdsBytes = 64 * 1024;   // k_rotate_mr's LDS per block (one wave at 4096)
+inline bool mr_supported(int nbin)
+{
+    if (nbin < kMrMin || nbin > kMrMax || (nbin & 7) || !(nbin & (nbin - 1))) return false;
+    int m = nbin / 2;
+    const int primes[3] = {2, 3, 5};
+    for (const int f : primes)
+        while (m % f == 0) m /= f;
+    return m == 1;
+}
+// the lengths the FFT dedispersion serves, for the error texts:
+// fail(..., "... needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, nbin)
+#define IC_ROT_NBIN_FMT                                                                            \
+    "a power-of-two nbin in %d..%d, or a multiple of 8 in %d..%d whose half has only the prime factors 2, 3 and 5"
+#define IC_ROT_NBIN_ARGS ::icgpu::kP2Min, ::icgpu::kP2Max, ::icgpu::kMrMin, ::icgpu::kMrMax
+
 // Diagnostics kernels (k_diag_p2<N> for the power-of-two nbin above, k_diag
 // otherwise).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
 // the fit cube D (row stride ldD); DIAG_CLOSED = fit_mode 1, the closed-form
@@ -332,14 +356,15 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
                           double subintthresh, double *test, float *W, float *hist, int iter,
                           int32_t *counters, int grid_cap = 0);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
-// bins, n a power of two (<= 8192): the phase rotation's multiplier
+// bins, n even (<= 8192; 1/n and 4/n are rounded factors unless n is a power
+// of two): the phase rotation's multiplier
 // (phase_rotation.py phasors; oracle orc_phasor).  One fixed sequence of
 // separately rounded f64 operations, so that the host's per-channel table
 // (ic_set_delays), the device's per-profile evaluation (ic_set_delays2) and
 // the two restatements agree bit for bit:
 //   the delay is split (Veltkamp, 2^13 + 1) into dh (40 significant bits) and
-//   dl, so k dh and k dl are exact; t = k dh - n rint(k dh / n) is exact and
-//   |t| <= n/2; y = (t + k dl) 4/n counts quarter turns (one rounding); with
+//   dl, so k dh and k dl are exact; t = k dh - n rint(k dh (1/n)) is exact and
+//   |t| <= n/2 (an ulp of the quotient beyond it when n is no power of two); y = (t + k dl) 4/n counts quarter turns (one rounding); with
 //   q = rint(y), z = y - q (exact, |z| <= 1/2), the angle is (pi/2)(q + z):
 //   sin and cos of (pi/2) z by their Taylor polynomials in z^2 (through z^17
 //   and z^16, Horner; truncation < 1e-17), then the quadrant q mod 4.
@@ -349,7 +374,8 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
 // P(k) = P0(k mod 64) P0(k - k mod 64), one complex multiply of separately
 // rounded operations ((a.x b.x - a.y b.y), (a.x b.y + a.y b.x)): a profile's
 // n/2 + 1 phasors then need 64 + n/128 polynomial evaluations instead of one
-// each (k_rotate's per-profile delays), within 7e-16 of the exact phasor.
+// each (k_rotate's per-profile delays), within 7e-16 of the exact phasor for a
+// power-of-two n, 1e-15 otherwise.
 __host__ __device__ inline double2 ic_phasor0(int k, double d, int n)
 {
     const double c = d * 8193.0;
@@ -408,7 +434,9 @@ __host__ __device__ inline double2 ic_phasor(int k, double d, int n)
 // (in_tiled / out2_tiled: d_ofs, strides multiples of 32); flags: only subints
 // with flags[s] != 0; late: only profiles with (late[p] != 0) == late_sel (the
 // diagnostics fork's two passes).  in may equal out (each row is read whole
-// before it is written).  nbin a power of two, 64 .. 8192 (IC_P2_SIZES).
+// before it is written).  nbin a power of two, 64 .. 8192 (IC_P2_SIZES:
+// k_rotate<N>), or a mixed-radix length (mr_supported: k_rotate_mr, which
+// honours everything here but the fused statistics).
 struct RotateArgs {
     const float *in;
     long ld_in;
@@ -446,7 +474,7 @@ struct RotateArgs {
     // measures X = f32(row * w0[p]) as k_diag's DIAG_STATS pass would (ic.py:
     // 111-117, :206-212) and writes std / mean / ptp / fftmax of p; out unused
     const float *w0;
-    const double2 *tw_p2;       // k_diag_p2's twiddle table (p2_twiddles)
+    const double2 *tw_p2;       // k_diag_p2's twiddle table (p2_twiddles); unused at a mixed-radix nbin
     double *std_o, *mean_o, *ptp_o, *fft_o;
     int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
 };

@@ -4603,6 +4603,247 @@ __global__ __launch_bounds__(RotCfg<N>::TB * RotCfg<N>::WPB, N <= 1024 ? 3 : 2) 
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_rotate_mr: the same rotation for the mixed-radix lengths (mr_supported:
+// N = 2M, M = 2^a 3^b 5^c, N a multiple of 8, 64 .. 4096), N a runtime value.
+// One wave per profile, blockDim.x / 64 waves per block; a wave's M complex
+// points ping-pong between two LDS buffers (8 N bytes per wave), one Stockham
+// stage per trip, and the block shares the f32 twiddle table (tw[q], q < N: 8 N
+// bytes, staged once per block).  The host factors M (mr_plan: the stage order
+// of phase_rotation.py stage_radices) and passes the radices as 4-bit fields;
+// the kernel switches per stage to the radix-templated body.  Every complex
+// operation is the packed f32 arithmetic of k_rotate (each half one IEEE f32
+// operation of the definition), rows move as 16-byte accesses and every global
+// load of a profile is issued before the first stage.  NJ: float4 rows per lane
+// (N <= 256 NJ).  PP: per-profile delays (RotateArgs.delay2).
+// DFT_3 / DFT_5 in the written order of phase_rotation.py (_dft3, _dft5)
+__device__ __forceinline__ void rot_dft3(rc2 *b)
+{
+    constexpr float s3 = (float)0x1.bb67ae8584caap-1;   // f32(f64(sqrt(3)/2))
+    const rc2 t = b[1] + b[2], d = b[1] - b[2];
+    const rc2 m = b[0] - t * (rc2){0.5f, 0.5f};
+    const rc2 e = d * (rc2){s3, s3};
+    b[0] = b[0] + t;
+    b[1] = pk_mi(m, e);   // m - i e
+    b[2] = pk_pi(m, e);   // m + i e
+}
+__device__ __forceinline__ void rot_dft5(rc2 *b)
+{
+    constexpr float c1 = (float)0x1.3c6ef372fe950p-2;    // f32(f64(cos(2 pi/5)))
+    constexpr float c2 = (float)-0x1.9e3779b97f4a8p-1;   // f32(f64(cos(4 pi/5)))
+    constexpr float s1 = (float)0x1.e6f0e134454ffp-1;    // f32(f64(sin(2 pi/5)))
+    constexpr float s2 = (float)0x1.2cf2304755a5ep-1;    // f32(f64(sin(4 pi/5)))
+    const rc2 t1 = b[1] + b[4], t2 = b[2] + b[3], d1 = b[1] - b[4], d2 = b[2] - b[3];
+    const rc2 m1 = (b[0] + t1 * (rc2){c1, c1}) + t2 * (rc2){c2, c2};
+    const rc2 m2 = (b[0] + t1 * (rc2){c2, c2}) + t2 * (rc2){c1, c1};
+    const rc2 e1 = d1 * (rc2){s1, s1} + d2 * (rc2){s2, s2};
+    const rc2 e2 = d1 * (rc2){s2, s2} - d2 * (rc2){s1, s1};
+    b[0] = b[0] + (t1 + t2);
+    b[1] = pk_mi(m1, e1);
+    b[2] = pk_mi(m2, e2);
+    b[3] = pk_pi(m2, e2);
+    b[4] = pk_pi(m1, e1);
+}
+
+// One stage of radix R and span ns (the product of the earlier radices) of the
+// wave's FFT_M: butterfly j < G = M/R reads in[j + q G], multiplies by
+// tw[q k step] (k = j mod ns, step = N/(R ns); not in the first stage), and
+// writes DFT_R's y_p to out[(j - k) R + k + p ns].  magic = ceil(2^32 / ns):
+// j / ns = (j magic) >> 32 exactly for j, ns < 2^16.
+template <int R>
+__device__ __forceinline__ void mr_stage(const rc2 *in, rc2 *out, const rc2 *tw, int M, int step, int ns, int lane)
+{
+    const int G = M / R;
+    const unsigned magic = ns > 1 ? 0xffffffffu / (unsigned)ns + 1u : 0u;
+    for (int j = lane; j < G; j += 64) {
+        const int k = ns > 1 ? j - (int)__umulhi((unsigned)j, magic) * ns : 0;
+        rc2 u[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) u[q] = in[j + q * G];
+        if (ns > 1) {
+            rc2 w[R];
+#pragma unroll
+            for (int q = 1; q < R; ++q) w[q] = tw[q * k * step];
+#pragma unroll
+            for (int q = 1; q < R; ++q) u[q] = rot_cmul(u[q], w[q]);
+        }
+        if constexpr (R == 8) {
+            rot_dft8(u);
+        } else if constexpr (R == 5) {
+            rot_dft5(u);
+        } else if constexpr (R == 4) {
+            rot_dft4(u);
+        } else if constexpr (R == 3) {
+            rot_dft3(u);
+        } else {
+            const rc2 a = u[0], b = u[1];
+            u[0] = a + b;
+            u[1] = a - b;
+        }
+        rc2 *o = out + (j - k) * R + k;
+#pragma unroll
+        for (int p = 0; p < R; ++p) o[p * ns] = u[p];
+    }
+}
+
+// FFT_M of the wave's points in `a` (stages ping-pong between a and b);
+// returns the buffer that holds the result
+__device__ __forceinline__ rc2 *mr_fft(rc2 *a, rc2 *b, const rc2 *tw, int M, int N, unsigned long long radices,
+                                       int nst, int lane)
+{
+    int ns = 1, step = N;
+    for (int s = 0; s < nst; ++s) {
+        const int R = (int)((radices >> (4 * s)) & 15);
+        step /= R;
+        switch (R) {
+        case 8: mr_stage<8>(a, b, tw, M, step, ns, lane); break;
+        case 5: mr_stage<5>(a, b, tw, M, step, ns, lane); break;
+        case 4: mr_stage<4>(a, b, tw, M, step, ns, lane); break;
+        case 3: mr_stage<3>(a, b, tw, M, step, ns, lane); break;
+        default: mr_stage<2>(a, b, tw, M, step, ns, lane); break;
+        }
+        ns *= R;
+        rc2 *t = a;
+        a = b;
+        b = t;
+        wave_sync();
+    }
+    return a;
+}
+
+template <int NJ, bool PP>
+__global__ __launch_bounds__(256) void k_rotate_mr(RotateArgs a, unsigned long long radices, int nst)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char mr_sm[];
+    const int N = a.nbin, M = N >> 1, H = M >> 1, NQ = N >> 2;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    rc2 *tws = (rc2 *)mr_sm;                      // [N] f32 of tw
+    rc2 *v0 = tws + N + (size_t)wv * 2 * M;       // the wave's two buffers of M points
+    rc2 *v1 = v0 + M;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) tws[i] = rc2_of(a.tw[i]);
+    __syncthreads();
+    const unsigned nsub = (unsigned)a.nsub, nchan = (unsigned)a.nchan;
+    const size_t P = (size_t)nsub * nchan;
+    const rc2 sgv = {1.0f, a.sign > 0 ? 1.0f : -1.0f};
+    const float inv = (float)(1.0 / (double)M);
+    const rc2 scl = {inv, -inv};   // (r.re / M, -r.im / M): x (-1/M) = -(x) (1/M)
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const size_t nitems = a.list ? (size_t)rl.n() : P;
+    // items as k_rotate's: channel-major over every profile, or a round list
+    for (size_t item = (size_t)blockIdx.x * wpb + wv; item < nitems; item += (size_t)gridDim.x * wpb) {
+        unsigned c, s;
+        size_t p;
+        if (a.list) {
+            p = (size_t)rl.at((long)item);
+            c = (unsigned)(p % nchan);
+            s = (unsigned)(p / nchan);
+        } else {
+            c = (unsigned)(item / nsub);
+            s = (unsigned)(item % nsub);
+            p = (size_t)s * nchan + c;
+        }
+        if ((a.flags && a.flags[s] == 0) || (a.late && ((a.late[p] != 0) != (a.late_sel != 0)))) continue;
+        // every global load of the profile in flight at once
+        fv4 xin[NJ];
+#pragma unroll
+        for (int u = 0; u < NJ; ++u) {
+            const int j4 = lane + 64 * u;
+            if (j4 < NQ)
+                xin[u] = __builtin_nontemporal_load((const fv4 *)(a.in + d_ofs(p, 4 * j4, (int)a.ld_in, a.in_tiled)));
+        }
+        // PP: the profile's phasor parts (ic_phasor's product form): lane l holds
+        // the low part P0(l) and the high part P0(64 l) (64 l <= M), evaluated
+        // once per profile
+        double2 Alo{}, Bhi{};
+        const float *phc = nullptr;
+        if constexpr (PP) {
+            const double dly = a.delay2[p];
+            Alo = ic_phasor0(lane, dly, N);
+            Bhi = ic_phasor0(64 * lane <= M ? 64 * lane : 0, dly, N);
+        } else {
+            phc = a.ph + 2 * (size_t)c * (M + 1);
+        }
+        // f32(ic_phasor(k, delay, N)), k <= M; every lane of the wave calls it together
+        auto phasor = [&](int k) {
+            if constexpr (PP) {
+                const int lo = k & 63, hi = k >> 6;
+                const double2 A = make_double2(__shfl(Alo.x, lo), __shfl(Alo.y, lo));
+                const double2 B = make_double2(__shfl(Bhi.x, hi), __shfl(Bhi.y, hi));
+                return rc2_of(lo == 0 ? B : (hi == 0 ? A : ic_phasor_mul(A, B)));
+            } else {
+                return *(const rc2 *)(phc + 2 * k);
+            }
+        };
+        if (a.amp) {
+            // the residual of the exact fit (k_residual's arithmetic), formed on the fly
+            const int st = a.info[p];
+            const bool ok = st >= 1 && st <= 4;
+            const double am = a.amp[p];
+#pragma unroll
+            for (int u = 0; u < NJ; ++u) {
+                const int j4 = lane + 64 * u;
+                if (j4 >= NQ) break;
+                float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (ok) {
+                    const double2 ta = *(const double2 *)(a.T64 + 4 * j4), tb = *(const double2 *)(a.T64 + 4 * j4 + 2);
+                    const float pv[4] = {xin[u].x, xin[u].y, xin[u].z, xin[u].w};
+                    const double tv[4] = {ta.x, ta.y, tb.x, tb.y};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int i = 4 * j4 + e;
+                        const double uu = am * tv[e];
+                        double d = uu - (double)pv[e];
+                        if (a.pr_on && i >= a.pr_start && i < a.pr_end) d = d * a.pr_factor;
+                        r[e] = (float)d;
+                    }
+                }
+                *(fv4 *)(v0 + 2 * j4) = (fv4){r[0], r[1], r[2], r[3]};
+            }
+        } else {
+            const float b = a.base ? a.base[p] : 0.0f;
+#pragma unroll
+            for (int u = 0; u < NJ; ++u) {
+                const int j4 = lane + 64 * u;
+                if (j4 >= NQ) break;
+                *(fv4 *)(v0 + 2 * j4) = xin[u] - (fv4){b, b, b, b};
+            }
+        }
+        wave_sync();
+        rc2 *z = mr_fft(v0, v1, tws, M, N, radices, nst, lane);
+        // pairs (k, M - k), k = 1 .. H, in place; lane 0's first slot is the DC /
+        // Nyquist step.  Uniform trip count: the shuffles of phasor() need every lane
+        for (int k0 = 0; k0 <= H; k0 += 64) {
+            const int k = k0 + lane, kc = k <= H ? k : H;
+            const rc2 pk = phasor(kc), pq = phasor(M - kc);
+            if (k == 0) {
+                const rc2 z0 = z[0];
+                const float X0 = z0.x + z0.y, XM = z0.x - z0.y;
+                const float Y0 = X0 * pk.x, YM = XM * pq.x;
+                z[0] = (rc2){(Y0 + YM) * 0.5f, -((Y0 - YM) * 0.5f)};
+            } else if (k <= H) {
+                const int q = M - k;
+                rc2 Zk, Zq;   // conjugated
+                rot_pair(z[k], z[q], tws[k], pk * sgv, pq * sgv, Zk, Zq);
+                z[q] = Zq;
+                z[k] = Zk;   // k = M/2 pairs with itself: the k values are stored last
+            }
+        }
+        wave_sync();
+        rc2 *r = mr_fft(z, z == v0 ? v1 : v0, tws, M, N, radices, nst, lane);
+        float *o = a.out + p * (size_t)a.ldo;
+#pragma unroll
+        for (int u = 0; u < NJ; ++u) {
+            const int j4 = lane + 64 * u;
+            if (j4 >= NQ) break;
+            const rc2 r0 = r[2 * j4] * scl, r1 = r[2 * j4 + 1] * scl;
+            const fv4 yv = {r0.x, r0.y, r1.x, r1.y};
+            __builtin_nontemporal_store(yv, (fv4 *)(o + 4 * j4));
+            if (a.out2) __builtin_nontemporal_store(yv, (fv4 *)(a.out2 + d_ofs(p, 4 * j4, (int)a.ldo2, a.out2_tiled)));
+        }
+        wave_sync();   // the buffers are reused by the wave's next profile
+    }
+}
+
 // TT = numpy pairwise sum of T64[i]^2 (fit_mode 1's denominator), one wave
 __global__ __launch_bounds__(64) void k_tnorm(const double *__restrict__ T64, const PwPlan *__restrict__ plan,
                                               double *__restrict__ TT)
@@ -5807,7 +6048,60 @@ hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, con
     return hipGetLastError();
 }
 
-bool rotate_supported(int nbin) { return p2_supported(nbin); }
+bool rotate_supported(int nbin) { return p2_supported(nbin) || mr_supported(nbin); }
+
+// the Stockham stages of FFT_{nbin/2} in the definition's order
+// (phase_rotation.py stage_radices): radix 8 while three or more power-of-two
+// levels remain, then 4 or 2, then the 3s, then the 5s; 4 bits per stage
+static int mr_plan(int nbin, unsigned long long *radices)
+{
+    int m = nbin / 2, lg = 0, nst = 0;
+    unsigned long long r = 0;
+    const auto push = [&](int R) {
+        if (nst < kMrMaxStages) r |= (unsigned long long)R << (4 * nst);
+        ++nst;
+    };
+    while (m % 2 == 0) {
+        m /= 2;
+        ++lg;
+    }
+    for (; lg >= 3; lg -= 3) push(8);
+    if (lg) push(1 << lg);
+    const int odd[2] = {3, 5};
+    for (const int f : odd)
+        while (m % f == 0) {
+            m /= f;
+            push(f);
+        }
+    *radices = r;
+    return m == 1 && nst <= kMrMaxStages ? nst : 0;
+}
+
+// k_rotate_mr: waves per block from the LDS it needs, 8 nbin bytes for the
+// block's f32 twiddle table and 8 nbin per wave, within kMrLdsBytes
+static hipError_t launch_rotate_mr(hipStream_t st, const RotateArgs &a, size_t P)
+{
+    unsigned long long radices = 0;
+    const int nst = mr_plan(a.nbin, &radices);
+    if (!nst) return hipErrorInvalidValue;
+    const size_t unit = 8 * (size_t)a.nbin;
+    const int wpb = (int)std::min<size_t>(4, kMrLdsBytes / unit - 1);
+    if (wpb < 1) return hipErrorInvalidValue;
+    const size_t shm = unit * (size_t)(1 + wpb);
+    const dim3 grid(cap_grid(std::min<size_t>(cdiv(P, wpb), 2048), a.grid_cap)), block(64 * wpb);
+    const int rows = (a.nbin / 4 + 63) / 64;   // float4 rows per lane
+#define IC_ROT_MR(NJ)                                                                              \
+    if (rows <= NJ) {                                                                              \
+        if (a.delay2) IC_GGL((k_rotate_mr<NJ, true>), grid, block, shm, st, a, radices, nst);      \
+        else IC_GGL((k_rotate_mr<NJ, false>), grid, block, shm, st, a, radices, nst);              \
+        return hipGetLastError();                                                                  \
+    }
+    IC_ROT_MR(4)
+    IC_ROT_MR(8)
+    IC_ROT_MR(16)
+#undef IC_ROT_MR
+    return hipErrorInvalidValue;
+}
 
 bool rotate_stats_supported(int nbin, bool data_f64) { return nbin == 1024 && !data_f64; }
 
@@ -5838,7 +6132,8 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
     if (stats && (!rotate_stats_supported(a.nbin, false) || !a.amp || a.sign > 0 || a.out2 || !a.w0 || !a.mean_o ||
                   !a.ptp_o || !a.fft_o))
         return hipErrorInvalidValue;
-    if (!rotate_supported(a.nbin) || !a.in || (!a.out && !stats) || !a.tw || !a.tw_p2 || a.ld_in < a.nbin ||
+    const bool mr = mr_supported(a.nbin);
+    if (!rotate_supported(a.nbin) || !a.in || (!a.out && !stats) || !a.tw || (!mr && !a.tw_p2) || a.ld_in < a.nbin ||
         (!stats && a.ldo < a.nbin) ||
         (!a.ph && !a.delay2 && !a.identity) ||
         (a.ld_in & 3) || (a.ldo & 3) || (a.out2 && (a.ldo2 < a.nbin || (a.ldo2 & 3))) ||
@@ -5850,6 +6145,7 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
         IC_GGL(k_rotate_identity, dim3(grid), dim3(256), 0, st, a);
         return hipGetLastError();
     }
+    if (mr) return launch_rotate_mr(st, a, P);
 #define IC_ROT(NN)                                                                                 \
     case NN:                                                                                       \
         if (a.delay2)                                                                              \

@@ -1083,8 +1083,12 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     if (p.input_dedispersed != 0 && (p.input_dedispersed != 1 || p.dedisp_mode != IC_DEDISP_FFT))
         return fail(IC_EINVAL, "input_dedispersed=%d needs dedisp_mode IC_DEDISP_FFT (0 or 1)", p.input_dedispersed);
     if (p.dedisp_mode == IC_DEDISP_FFT && !rotate_supported(p.nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in %d..%d (nbin=%d)", kP2Min, kP2Max,
-                    p.nbin);
+        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, p.nbin);
+    // launch_diag has no DIAG_FIT for the generic kernel these lengths use
+    if (p.dedisp_mode == IC_DEDISP_FFT && p.fit_mode == IC_FIT_CLOSED && mr_supported(p.nbin))
+        return fail(IC_EINVAL,
+                    "fit_mode IC_FIT_CLOSED with fractional dedispersion needs a power-of-two nbin in %d..%d; "
+                    "a mixed-radix nbin takes IC_FIT_EXACT (nbin=%d)", kP2Min, kP2Max, p.nbin);
     if (diag_lds_bytes(p.nbin) > 160 * 1024)
         return fail(IC_EINVAL, "nbin=%d needs %zu bytes of LDS for the diagnostics (> 160 KiB)", p.nbin,
                     diag_lds_bytes(p.nbin));
@@ -2150,8 +2154,7 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
 {
     if (!in || !delay_bins || !out || nsub <= 0 || nchan <= 0) return fail(IC_EINVAL, "bad argument");
     if (!rotate_supported(nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs a power-of-two nbin in %d..%d (nbin=%d)", kP2Min, kP2Max,
-                    nbin);
+        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, nbin);
     if (sign != 1 && sign != -1) return fail(IC_EINVAL, "sign must be +1 or -1");
     const size_t nd = per_profile ? (size_t)nsub * nchan : (size_t)nchan;
     for (size_t c = 0; c < nd; ++c)
@@ -2177,8 +2180,10 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
     CKF(hipMemcpyAsync(d, in, sizeof(float) * N, hipMemcpyHostToDevice, st), bad);
     CKF(hipMemcpyAsync(dph, ph.data(), sizeof(float) * ph.size(), hipMemcpyHostToDevice, st), bad);
     CKF(hipMemcpyAsync(dtw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice, st), bad);
-    CKF(sc.mem.alloc_exact(&dtw2, tw2.size()), bad);
-    CKF(hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st), bad);
+    if (!tw2.empty()) {   // a power-of-two nbin; k_rotate_mr reads tw alone
+        CKF(sc.mem.alloc_exact(&dtw2, tw2.size()), bad);
+        CKF(hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st), bad);
+    }
     RotateArgs a{};
     a.in = d;
     a.ld_in = nbin;

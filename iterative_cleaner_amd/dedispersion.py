@@ -21,13 +21,17 @@ Mode selection (:func:`plan`):
     a whole number of bins is;
   * otherwise             -> psrchive's fractional FFT rotation (IC_DEDISP_FFT):
     one delay per channel when every subint has the same row, else one per
-    profile (ic_set_delays2).  nbin must then be a power of two in 64..8192;
-    any other nbin raises (the rotation kernels do not serve it, and rounding
-    the delays would silently change which profiles get zapped).
+    profile (ic_set_delays2).  nbin must then be a power of two in 64..8192,
+    or a multiple of 8 in 64..4096 whose half has only the prime factors 2, 3
+    and 5 (phase_rotation.mr_supported: 1000, 1200, 1536, 2000, ...); any
+    other nbin raises (the rotation kernels do not serve it, and rounding the
+    delays would silently change which profiles get zapped).
 """
 from __future__ import annotations
 
 import numpy as np
+
+from .phase_rotation import UNSUPPORTED, mr_supported
 
 DISPERSION_CONSTANT = 1.0 / 2.41e-4    # s MHz^2 cm^3 / pc (psrchive, dspsr, tempo)
 
@@ -38,8 +42,9 @@ FFT_NBIN_MIN, FFT_NBIN_MAX = 64, 8192    # the library's IC_P2_SIZES (csrc/ic_in
 
 
 def fft_supported(nbin: int) -> bool:
-    """nbin the rotation kernels serve: a power of two in 64..8192."""
-    return FFT_NBIN_MIN <= nbin <= FFT_NBIN_MAX and (nbin & (nbin - 1)) == 0
+    """nbin the rotation kernels serve: a power of two in 64..8192, or a
+    mixed-radix length (phase_rotation.mr_supported)."""
+    return (FFT_NBIN_MIN <= nbin <= FFT_NBIN_MAX and (nbin & (nbin - 1)) == 0) or mr_supported(nbin)
 
 
 def delays_from_dm(dm, freqs, fref, periods, nbin) -> np.ndarray:
@@ -69,9 +74,8 @@ def plan(delay, nbin: int, what: str = "archive"):
         # integral, but a channel's shift differs between subints: the shift
         # arrays are per channel, so these go through the per-profile rotation
     if not fft_supported(nbin):
-        raise ValueError("%s: fractional dedispersion delays need a power-of-two nbin in %d..%d for the "
-                         "FFT phase rotation (nbin=%d); the delays are not rounded"
-                         % (what, FFT_NBIN_MIN, FFT_NBIN_MAX, nbin))
+        raise ValueError("%s: the FFT phase rotation of fractional dedispersion delays %s (nbin=%d); "
+                         "the delays are not rounded" % (what, UNSUPPORTED, nbin))
     zeros = np.zeros(nchan, np.int64)
     if np.all(d == d[:1]):
         return zeros, np.ascontiguousarray(d[0])

@@ -11,16 +11,19 @@ GPU kernel (k_rotate, ic_kernels.hip), the C restatement the tests check
 against (orc_rotate in the oracle/ directory) and this numpy version agree bit for
 bit.
 
-Definition, for a profile x of N = 2M samples (N a power of two) and a delay
+Definition, for a profile x of N = 2M samples (N a power of two, or a multiple
+of 8 whose half M has only the prime factors 2, 3 and 5) and a delay
 of s bins (``y[j] = x[j + s]`` for integer s; ``dedisperse`` rotates by +s,
 ``dededisperse`` by -s).  The arithmetic is IEEE single precision, as psrchive's
 (its FTransform runs FFTW's single-precision plans on the f32 amplitudes):
 
 1. x' = f32(x - base) (base 0 when no baseline is subtracted), then
    z[j] = (x'[2j], x'[2j+1]), j < M.
-2. Z = FFT_M(z): Stockham autosort, stages of radix R = 8 while three or
-   more of the log2 M levels remain, then one of radix 4 or 2; Ns = the
-   product of the earlier radices.  Butterfly j < M/R: k = j mod Ns,
+2. Z = FFT_M(z), M = 2^a 3^b 5^c: Stockham autosort, in this stage order
+   (:func:`stage_radices`): the a power-of-two levels first, as stages of
+   radix R = 8 while three or more of them remain, then one of radix 4 or 2;
+   then b stages of radix 3; then c stages of radix 5.  Ns = the product of
+   the earlier radices.  Butterfly j < M/R: k = j mod Ns,
    a_q = z[j + q M/R]; from the second stage on (Ns > 1) b_q = a_q * w_q for
    q >= 1 with w_q = tw[q k N/(R Ns)] and the product (a.r w.r - a.i w.i,
    a.r w.i + a.i w.r), else b = a; y = DFT_R(b); out[(j - k) R + k + p Ns] = y_p.
@@ -30,6 +33,15 @@ of s bins (``y[j] = x[j + s]`` for integer s; ``dedisperse`` rotates by +s,
    b_(q+4) (q < 4); c5 = ((c5.r + c5.i) s, (c5.i - c5.r) s), c6 = (c6.i, -c6.r),
    c7 = ((c7.i - c7.r) s, -((c7.r + c7.i) s)) with s = f32(f64(sqrt(2)/2)); the
    even outputs y_(2p) = DFT_4(c0..c3)_p, the odd y_(2p+1) = DFT_4(c4..c7)_p.
+   DFT_3: t = b1 + b2, d = b1 - b2, y0 = b0 + t, m = b0 - t h (h = 1/2),
+   e = d s3 (both parts by the real s3 = f32(f64(sqrt(3)/2))); y1 = m - i e =
+   (m.r + e.i, m.i - e.r), y2 = m + i e = (m.r - e.i, m.i + e.r).
+   DFT_5: t1 = b1 + b4, t2 = b2 + b3, d1 = b1 - b4, d2 = b2 - b3;
+   y0 = b0 + (t1 + t2); m1 = (b0 + t1 c1) + t2 c2, m2 = (b0 + t1 c2) + t2 c1;
+   e1 = d1 s1 + d2 s2, e2 = d1 s2 - d2 s1 (every product a complex by a real:
+   both parts); y1 = m1 - i e1, y4 = m1 + i e1, y2 = m2 - i e2, y3 = m2 + i e2
+   (-i e and +i e as in DFT_3), with c1 = f32(f64(cos(2 pi/5))), c2 =
+   f32(f64(cos(4 pi/5))), s1 = f32(f64(sin(2 pi/5))), s2 = f32(f64(sin(4 pi/5))).
 3. For k = 1 .. M/2, q = M - k: the half-length spectrum of the inverse from
    Z_k, Z_q in one linear map (:func:`_pair`: the real spectrum, the phasors
    (P.r, sign * P.i) and the inverse's packing composed), stored conjugated,
@@ -38,7 +50,8 @@ of s bins (``y[j] = x[j + s]`` for integer s; ``dedisperse`` rotates by +s,
    DC and Nyquist: X_0 = Z_0.r + Z_0.i, X_M = Z_0.r - Z_0.i (real),
    Y_0 = X_0 P_0.r, Y_M = X_M P_M.r, stored (Y_0 + Y_M)/2, -((Y_0 - Y_M)/2).
 4. r = FFT_M(stored) (same stages); out[2j] = r[j].r * (1/M),
-   out[2j+1] = (-r[j].i) * (1/M).
+   out[2j+1] = (-r[j].i) * (1/M), 1/M the f32 of the f64 quotient (exact for
+   a power of two).
 
 Every step is a single IEEE f32 operation in the written order (no fused
 multiply-add).  Tables: tw[q] = exp(-2 pi i q / N), evaluated in x87 long
@@ -58,19 +71,68 @@ LDS traffic.  The result is within a few f32 ulps of the profile's largest
 sample of numpy's f64 ``irfft(rfft(x) * exp(2j pi k s / N))`` (oracle/restated.py
 fft_phase_shift, tests/test_phase_rotation.py), as psrchive's FFTW-f32 rotation
 is.
+
+Lengths: the definition holds for every N above; the GPU kernels serve the
+powers of two 64 .. 8192 (k_rotate<N>) and the mixed-radix set MR of
+:func:`mr_supported` (k_rotate_mr): 64 <= N <= 4096, N a multiple of 8 (rows
+and half rows stay 16-byte addressable), N/2 = 2^a 3^b 5^c, N not a power of
+two.  Measured on random profiles (tests/test_phase_rotation_mr.py) the MR
+lengths stay within the same 4 f32 epsilons of the largest sample as the
+powers of two.
 """
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["PI_L", "twiddles", "phasors", "rotate", "is_supported"]
+__all__ = ["PI_L", "twiddles", "phasors", "rotate", "is_supported", "mr_supported", "stage_radices",
+           "MR_NBIN_MIN", "MR_NBIN_MAX", "UNSUPPORTED"]
 
 PI_L = np.longdouble("3.141592653589793238462643383279502884")
 
 
+MR_NBIN_MIN, MR_NBIN_MAX = 64, 4096    # the library's mr_supported (csrc/ic_internal.h)
+
+# what every refusal says (the checks of archive.py, dedispersion.py and rotate())
+UNSUPPORTED = ("needs a power-of-two nbin in 64..8192, or a multiple of 8 in %d..%d whose half has only "
+               "the prime factors 2, 3 and 5" % (MR_NBIN_MIN, MR_NBIN_MAX))
+
+
+def _smooth235(m: int) -> bool:
+    for f in (2, 3, 5):
+        while m % f == 0:
+            m //= f
+    return m == 1
+
+
+def mr_supported(nbin: int) -> bool:
+    """The mixed-radix set MR: 64 <= nbin <= 4096, a multiple of 8, nbin/2 =
+    2^a 3^b 5^c, not a power of two (those are the templated kernels')."""
+    return (MR_NBIN_MIN <= nbin <= MR_NBIN_MAX and nbin % 8 == 0 and (nbin & (nbin - 1)) != 0
+            and _smooth235(nbin // 2))
+
+
 def is_supported(nbin: int) -> bool:
-    """The rotation needs a power-of-two nbin (the GPU kernels: 64 .. 8192)."""
-    return nbin >= 4 and (nbin & (nbin - 1)) == 0
+    """The rotation is defined for a power-of-two nbin (the GPU kernels: 64 ..
+    8192) and for the mixed-radix lengths of :func:`mr_supported`."""
+    return (nbin >= 4 and (nbin & (nbin - 1)) == 0) or mr_supported(nbin)
+
+
+def stage_radices(m: int) -> list:
+    """The Stockham stages of FFT_m, m = 2^a 3^b 5^c, in the definition's order:
+    radix 8 while three or more power-of-two levels remain, then 4 or 2, then
+    the 3s, then the 5s."""
+    a = 0
+    while m % 2 == 0:
+        m //= 2
+        a += 1
+    out = [8] * (a // 3) + {0: [], 1: [2], 2: [4]}[a % 3]
+    for f in (3, 5):
+        while m % f == 0:
+            m //= f
+            out.append(f)
+    if m != 1:
+        raise ValueError("FFT length with a prime factor above 5")
+    return out
 
 
 def twiddles(nbin: int) -> np.ndarray:
@@ -95,11 +157,14 @@ _PH_C = tuple(float.fromhex(h) for h in (
 
 def phasors(nbin: int, delays) -> np.ndarray:
     """(2, *delays.shape, nbin/2 + 1) f64: exp(+2 pi i k s / nbin) for every
-    delay s (bins) and harmonic k <= nbin/2, in this f64 operation order:
+    delay s (bins) and harmonic k <= nbin/2 (any even nbin <= 8192; 1/nbin and
+    4/nbin are rounded f64 factors unless nbin is a power of two), in this f64
+    operation order:
 
     * Veltkamp split s = sh + sl (c = s * 8193; sh = c - (c - s); sl = s - sh):
       sh has 40 significant bits, so k*sh and k*sl are exact (k < 2^13);
-    * t = k sh - nbin rint(k sh / nbin)   (exact; |t| <= nbin/2)
+    * t = k sh - nbin rint((k sh) (1 / nbin))   (exact; |t| <= nbin/2, or an
+      ulp of k sh / nbin beyond it when nbin is not a power of two)
     * y = (t + k sl) * (4 / nbin)          quarter turns, one rounding
     * q = rint(y); z = y - q               (exact; |z| <= 1/2)
     * w = z*z; sin = z * (S0 + w (S1 + ... w S8)); cos = C0 + w (C1 + ... w C8)
@@ -109,8 +174,9 @@ def phasors(nbin: int, delays) -> np.ndarray:
     and for multiples of 64, else the product P0(k mod 64) * P0(k - k mod 64)
     with separately rounded operations (re = a.re b.re - a.im b.im, im = a.re
     b.im + a.im b.re), so that a profile's phasors take 64 + nbin/128
-    polynomial evaluations.  Within 7e-16 of the exact phasor
-    (tests/test_phase_rotation.py checks it against x87 long double)."""
+    polynomial evaluations.  Within 7e-16 of the exact phasor for a
+    power-of-two nbin (tests/test_phase_rotation.py checks it against x87 long
+    double) and within 1e-15 otherwise (tests/test_phase_rotation_mr.py)."""
     m = nbin // 2
     k = np.arange(m + 1, dtype=np.float64)
     s = np.asarray(delays, dtype=np.float64)[..., None]
@@ -176,19 +242,45 @@ def _dft8(ar, ai):
             [ei[0], oi[0], ei[1], oi[1], ei[2], oi[2], ei[3], oi[3]])
 
 
+S3 = np.float32(0.8660254037844386)    # f32 of f64(sqrt(3)/2)
+HALF = np.float32(0.5)
+C51 = np.float32(0.30901699437494745)   # f32 of f64(cos(2 pi/5))
+C52 = np.float32(-0.8090169943749475)   # f32 of f64(cos(4 pi/5))
+S51 = np.float32(0.9510565162951535)    # f32 of f64(sin(2 pi/5))
+S52 = np.float32(0.5877852522924731)    # f32 of f64(sin(4 pi/5))
+
+
+def _dft3(ar, ai):
+    tr, ti = ar[1] + ar[2], ai[1] + ai[2]
+    dr, di = ar[1] - ar[2], ai[1] - ai[2]
+    mr, mi = ar[0] - tr * HALF, ai[0] - ti * HALF
+    er, ei = dr * S3, di * S3
+    return ([ar[0] + tr, mr + ei, mr - ei], [ai[0] + ti, mi - er, mi + er])
+
+
+def _dft5(ar, ai):
+    t1r, t1i = ar[1] + ar[4], ai[1] + ai[4]
+    t2r, t2i = ar[2] + ar[3], ai[2] + ai[3]
+    d1r, d1i = ar[1] - ar[4], ai[1] - ai[4]
+    d2r, d2i = ar[2] - ar[3], ai[2] - ai[3]
+    m1r, m1i = (ar[0] + t1r * C51) + t2r * C52, (ai[0] + t1i * C51) + t2i * C52
+    m2r, m2i = (ar[0] + t1r * C52) + t2r * C51, (ai[0] + t1i * C52) + t2i * C51
+    e1r, e1i = d1r * S51 + d2r * S52, d1i * S51 + d2i * S52
+    e2r, e2i = d1r * S52 - d2r * S51, d1i * S52 - d2i * S51
+    return ([ar[0] + (t1r + t2r), m1r + e1i, m2r + e2i, m2r - e2i, m1r - e1i],
+            [ai[0] + (t1i + t2i), m1i - e1r, m2i - e2r, m2i + e2r, m1i + e1r])
+
+
 def _stockham(vr: np.ndarray, vi: np.ndarray, tw: np.ndarray):
-    """FFT of the last axis (M complex points): Stockham stages of radix 8 while
-    three or more levels remain, then one of radix 4 or 2 (module docstring)."""
+    """FFT of the last axis (M complex points): Stockham stages in the order of
+    :func:`stage_radices` (module docstring)."""
     m = vr.shape[-1]
     n = 2 * m
-    lg = m.bit_length() - 1
-    ns, done = 1, 0
-    while done < lg:
-        rem = lg - done
-        r = 8 if rem >= 3 else (4 if rem == 2 else 2)
+    ns = 1
+    for r in stage_radices(m):
         g = m // r
         j = np.arange(g)
-        k = j & (ns - 1)
+        k = j % ns
         ar = [vr[..., q * g:(q + 1) * g] for q in range(r)]
         ai = [vi[..., q * g:(q + 1) * g] for q in range(r)]
         if ns > 1:
@@ -200,6 +292,10 @@ def _stockham(vr: np.ndarray, vi: np.ndarray, tw: np.ndarray):
             yr, yi = _dft8(ar, ai)
         elif r == 4:
             yr, yi = _dft4(ar, ai)
+        elif r == 5:
+            yr, yi = _dft5(ar, ai)
+        elif r == 3:
+            yr, yi = _dft3(ar, ai)
         else:
             yr, yi = [ar[0] + ar[1], ar[0] - ar[1]], [ai[0] + ai[1], ai[0] - ai[1]]
         o = (j - k) * r + k
@@ -210,7 +306,6 @@ def _stockham(vr: np.ndarray, vi: np.ndarray, tw: np.ndarray):
             ni[..., o + p * ns] = yi[p]
         vr, vi = nr, ni
         ns *= r
-        done += {8: 3, 4: 2, 2: 1}[r]
     return vr, vi
 
 
@@ -254,7 +349,7 @@ def rotate(x: np.ndarray, ph: np.ndarray, sign: int, tw: np.ndarray | None = Non
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[-1]
     if not is_supported(n):
-        raise ValueError("fractional dedispersion needs a power-of-two nbin (got %d)" % n)
+        raise ValueError("fractional dedispersion %s (nbin=%d)" % (UNSUPPORTED, n))
     if tw is None:
         tw = twiddles(n)
     tw = np.asarray(tw, dtype=np.float64).astype(np.float32)   # f32 of the f64 table

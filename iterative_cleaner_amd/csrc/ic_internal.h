@@ -1,5 +1,6 @@
 // ic_internal.h — shared declarations between the host session (ic_session.hip)
-// and the gfx950 kernels (ic_kernels.hip).  Not part of the public C-ABI.
+// and the gfx950 kernel units (ic_kernels.hip, ic_rotate.hip, ic_linestats.hip,
+// ic_shards.hip).  Not part of the public C-ABI.
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -148,8 +149,13 @@ inline unsigned cap_grid(size_t grid, int grid_cap)
 {
     return (unsigned)(grid_cap > 0 && grid > (size_t)grid_cap ? (size_t)grid_cap : grid);
 }
+// the launchers' ceiling division, and the block size of the lane-per-bin
+// kernels: whole waves, at most 256 threads
+inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+inline int bin_block(int nbin) { return nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64; }
 
-// ---- launch wrappers (ic_kernels.hip); all asynchronous on `st` ----
+// ---- launch wrappers (each below its kernels: ic_kernels.hip, ic_rotate.hip,
+// ic_linestats.hip, ic_shards.hip); all asynchronous on `st` ----
 // mode 0: part = sum W*ded; 1: part2 = sum W*f32(ded-base) + wpart; 2: both;
 // 3: mode 1 + the fit cube D[k][i] = f32(ded-base) (row stride ldD).
 // flags: only subints with flags[s] != 0 (nullptr: all)

@@ -1,4 +1,6 @@
-// ic_kernels.hip — gfx950 kernels of the surgical-cleaning loop
+// ic_kernels.hip — gfx950 kernels of the surgical-cleaning loop: template stage,
+// sample codec, exact fit and diagnostics (the rotation is in ic_rotate.hip, line
+// statistics and combine in ic_linestats.hip, the shard exchanges in ic_shards.hip)
 // (/root/reference/iterative_cleaner.py:83-146).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see Makefile).
@@ -16,12 +18,14 @@
 //   k_fscrunch       combine super-block partials -> F[s][i], wf[s]
 //   k_sb_tree        (channel shards) local super-block partials -> shard root
 //   k_tscrunch       weighted mean over subints, *10000 -> T (ic.py:94)
-//   k_fit            exact scipy leastsq(a*T-p, [1.0]) per profile (ic.py:278)
+//   k_fit_*          exact scipy leastsq(a*T-p, [1.0]) per profile (ic.py:278):
+//                    k_fit_init, k_fit_prep, k_fit_pass, k_fit_state, k_fit_tail
 //   k_diag           residual (ic.py:279-288), f32 store (:272), dededisperse
 //                    (:104), apply_weights (:296), diagnostics (:206-217)
-//   k_linestats      per channel / subint median & MAD (ic.py:229-256)
+//   k_linestats      per channel / subint median & MAD (ic.py:229-256; ic_linestats.hip)
 //   k_combine        scale, max, median-of-4, threshold, new weights,
 //                    convergence counters (ic.py:221-225, :303-305, :127-141)
+// Code that several sections share lives in ic_wave.h and ic_fftdiag.h.
 #include <algorithm>
 #include <float.h>
 #include <math.h>
@@ -31,88 +35,12 @@
 
 #include <type_traits>
 
-#include "ic_internal.h"
+#include "ic_fftdiag.h"
 
 namespace icgpu {
 
 __device__ constexpr double kRdwarf = 3.834e-20;
 __device__ constexpr double kRgiant = 1.304e19;
-
-// LDS ordering between lanes of ONE wave: DS instructions of a wave execute in
-// order, so only compiler reordering must be prevented (no s_barrier).
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---- cross-lane trees on DPP + readlane (VALU latency, no LDS crossbar) ----
-// Level m of an xor-butterfly pairs lane groups [0,m) and [m,2m).  Within a
-// row of 16 that is quad_perm (m = 1, 2), row_half_mirror (m = 4) and
-// row_mirror (m = 8): after level m every lane of a group of m holds the same
-// value, so a mirror delivers the partner group's value.  The last two levels
-// combine lanes 0, 16, 32, 48 read into scalars, in tree order.  The result is
-// wave-uniform.  (IEEE add/max/min are commutative: a lane adding its partner's
-// value gets the same bits as the partner adding its own.)
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp(int v)
-{
-    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
-}
-// (every lane reads an in-range lane for these controls, so the f64 form needs
-// no `old` operand: mov_dpp saves the two zeroing moves per level)
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v)
-{
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float lane_read(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ int lane_read(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ double lane_read(double v, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
-                            __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
-// tree over lanes [0, ACT) (ACT a power of two <= 64), uniform result
-template <int ACT, typename T, typename Op>
-__device__ __forceinline__ T wave_tree(T v, Op op)
-{
-    if (ACT >= 2) v = op(v, dpp<kDppXor1>(v));
-    if (ACT >= 4) v = op(v, dpp<kDppXor2>(v));
-    if (ACT >= 8) v = op(v, dpp<kDppHalfMirror>(v));
-    if (ACT >= 16) v = op(v, dpp<kDppMirror>(v));
-    if (ACT == 64) return op(op(lane_read(v, 0), lane_read(v, 16)), op(lane_read(v, 32), lane_read(v, 48)));
-    if (ACT == 32) return op(lane_read(v, 0), lane_read(v, 16));
-    return lane_read(v, 0);
-}
-
-struct OpAdd {
-    template <typename T>
-    __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpMaxF {
-    __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
-    __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); }
-};
-struct OpMinF {
-    __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); }
-    __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); }
-};
-struct OpOr {
-    __device__ __forceinline__ int operator()(int a, int b) const { return a | b; }
-};
-
 
 // ============================================================ template stage
 
@@ -1325,19 +1253,12 @@ __device__ __forceinline__ bool x_in_sq_range(double x)
 #define FIT_TB 16
 #define FIT_BUF 4096
 
-typedef float fv4 __attribute__((ext_vector_type(4)));
-
 struct DmaTiles {
     const float *src[4];   // this lane's DMA source for instruction m at bin 0
     int tiled;             // fit cube layout (dt_ofs): bin b0 of a row is at + (b0/32) 2048 + b0 % 32
     uint32_t rd[4];        // LDS byte address of this lane's chunk c in buffer 0
     char *lds;             // buffer 0 (buffer 1 at +FIT_BUF)
 };
-
-__device__ __forceinline__ uint32_t lds_u32(const void *p)
-{
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
 
 __device__ __forceinline__ void dma_tile(const DmaTiles &d, char *buf, int b0)
 {
@@ -1704,41 +1625,6 @@ __device__ __forceinline__ void lm_store(const LmState &L, const FitStateArrays 
     S.x2[k] = L.x2; S.pnorm[k] = L.pnorm; S.wa1[k] = L.wa1;
     S.iter[k] = L.iter; S.nfev[k] = L.nfev;
 }
-
-// A round's input list.  k_fit_state writes the survivors of a round into the
-// P-entry list buffer partitioned by request: A requests from the front
-// (list[0 .. nA)), B requests from the end down (list[P - 1 - j], j < nB), so
-// that the next round's waves hold one kind each (a wave with both runs both
-// sweep bodies; round 0's unanswered B requests and the profiles one stage
-// behind after them would otherwise spread over most waves).  Both counts
-// share one 64-bit word, [63:32] nB and [31:0] nA, so that one atomic per
-// block returns both list offsets; the blocks that finished are counted in a
-// word of their own (k_fit_state).
-__host__ __device__ constexpr unsigned long long rl_pack(unsigned long long nB, unsigned long long nA)
-{
-    return (nB << 32) | nA;
-}
-struct RoundList {
-    const int32_t *list;
-    long nA, nB, P;
-    __device__ __forceinline__ RoundList(const int32_t *l, const unsigned long long *ctr, long P_) : list(l), P(P_)
-    {
-        if (!l) {
-            nA = P_;
-            nB = 0;
-        } else {
-            const unsigned long long v = *ctr;
-            nA = (long)(v & 0xffffffffull);
-            nB = (long)(v >> 32);
-        }
-    }
-    __device__ __forceinline__ long n() const { return nA + nB; }
-    __device__ __forceinline__ long at(long s) const
-    {
-        if (!list) return s;
-        return s < nA ? (long)list[s] : (long)list[P - 1 - (s - nA)];
-    }
-};
 
 // m[k] = v for every profile k of a round list (the second fork: the profiles
 // handed to k_fit_tail)
@@ -2443,65 +2329,6 @@ __device__ Tp wave_pairwise(const PwPlan &pl, Get get, Tp *scratch, int lane)
 // Per profile: the f32 residual (iterative_cleaner.py:279-288, :272), dededispersion
 // (:104), the ORIGINAL weight (:296) and the four diagnostics (:206-217) with
 // numpy.ma data conventions.
-// ---- mixed-radix (8/4/2) Stockham FFT helpers (forward, exp(-2 pi i jk/N)) ----
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 w)
-{
-    return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-// fused form for the power-of-two path (the FFT diagnostic is compared within
-// a tolerance, never bit-for-bit: pocketfft's own rounding is not reproduced)
-__device__ __forceinline__ double2 cmul_f(double2 a, double2 w)
-{
-    return make_double2(__builtin_fma(a.x, w.x, -(a.y * w.y)), __builtin_fma(a.x, w.y, a.y * w.x));
-}
-__device__ __forceinline__ double2 mul_mi(double2 a) { return make_double2(a.y, -a.x); }   // * (-i)
-
-template <int R>
-__device__ __forceinline__ void dft_small(double2 (&v)[R]);
-
-template <>
-__device__ __forceinline__ void dft_small<2>(double2 (&v)[2])
-{
-    const double2 a = v[0], b = v[1];
-    v[0] = cadd(a, b);
-    v[1] = csub(a, b);
-}
-
-template <>
-__device__ __forceinline__ void dft_small<4>(double2 (&v)[4])
-{
-    const double2 s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]);
-    const double2 s13 = cadd(v[1], v[3]), d13 = mul_mi(csub(v[1], v[3]));
-    v[0] = cadd(s02, s13);
-    v[2] = csub(s02, s13);
-    v[1] = cadd(d02, d13);
-    v[3] = csub(d02, d13);
-}
-
-template <>
-__device__ __forceinline__ void dft_small<8>(double2 (&v)[8])
-{
-    double2 e[4] = {v[0], v[2], v[4], v[6]};
-    double2 o[4] = {v[1], v[3], v[5], v[7]};
-    dft_small<4>(e);
-    dft_small<4>(o);
-    const double h = 0.70710678118654752440;   // sqrt(1/2)
-    // o_k * exp(-2 pi i k/8), k = 0..3
-    const double2 o1 = make_double2(h * (o[1].x + o[1].y), h * (o[1].y - o[1].x));
-    const double2 o2 = mul_mi(o[2]);
-    const double2 o3 = make_double2(h * (o[3].y - o[3].x), -h * (o[3].x + o[3].y));
-    v[0] = cadd(e[0], o[0]);
-    v[4] = csub(e[0], o[0]);
-    v[1] = cadd(e[1], o1);
-    v[5] = csub(e[1], o1);
-    v[2] = cadd(e[2], o2);
-    v[6] = csub(e[2], o2);
-    v[3] = cadd(e[3], o3);
-    v[7] = csub(e[3], o3);
-}
-
 // exp(-2 pi i q/n) for 0 <= q < n from the half table tw[0..n/2)
 __device__ __forceinline__ double2 twid(const double2 *tw, int q, int half)
 {
@@ -2626,7 +2453,7 @@ __global__ __launch_bounds__(256) void k_diag(DiagArgs a)
         }
         const bool tr = a.dtiled && mode == DIAG_EXACT;   // the tiled fit cube (dt_ofs)
         auto prow = [&](int i) -> float { return tr ? a.D[dt_ofs(k, i, a.ldD)] : p[i]; };
-        const bool ok = stt >= 1 && stt <= 4;
+        const bool ok = fit_ok(stt);
         // residual -> X (dispersed frame): X[j] = f32(f32(r[i]) * w), j = (i + sh) mod n
         // (f64(f32(r[i])) * f64(w) for f64 data)
         for (int i = lane; i < n; i += 64) {
@@ -2634,17 +2461,14 @@ __global__ __launch_bounds__(256) void k_diag(DiagArgs a)
             if (mode == DIAG_STATS) {
                 R = p[i];
             } else if (ok) {
-                const double u = x * T64[i];
-                double e = u - (double)prow(i);
-                if (a.pr_on && i >= a.pr_start && i < a.pr_end) e = e * a.pr_factor;
-                R = (float)e;
+                R = residual_sample(x, T64[i], prow(i), i, a);
             }
             int j = i + sh;
             if (j >= n) j -= n;
             X[j] = a.data_f64 ? (double)R * (double)w : (double)(R * w);
         }
         wave_sync();
-        double mean = 0.0, sd = 0.0, ptp = a.data_f64 ? 1e20 : (double)1e20f;   // numpy.ma fill value
+        double mean = 0.0, sd = 0.0, ptp = ptp_fill(a.data_f64);
         if (valid) {
             if (a.data_f64)
                 mean = wave_pairwise<double>(pl, [&](int q) { return X[q]; }, scr, lane) / (double)n;
@@ -2750,7 +2574,7 @@ __global__ __launch_bounds__(256) void k_diag(DiagArgs a)
             best = fmax(best, __shfl_xor(best, off));
             nanf |= __shfl_xor(nanf, off);
         }
-        if (lane == 0) {
+        if (lane == 0) {   // diag_store, restated: the call moved the epilogue's code
             a.std_o[k] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
             a.mean_o[k] = valid ? mean : 0.0;
             a.ptp_o[k] = ptp;
@@ -2783,215 +2607,6 @@ __global__ __launch_bounds__(256) void k_diag(DiagArgs a)
 //                fit cube row p = f32(ded - base0) formed from the raw cube),
 //                then the same residual; writes amp / info
 //   DIAG_STATS   comprehensive_stats alone (ic.py:181-226): X = f32(row * w)
-template <int N, bool D64 = false>
-struct P2 {
-    static constexpr int WPP = N >= 2048 ? N / 1024 : 1;   // waves per profile
-    static constexpr int TPP = 64 * WPP;                    // threads per profile
-    static constexpr int M = N / 2;
-    static constexpr int LEAF = N < 128 ? N : 128;
-    static constexpr int NL = N / LEAF;
-    static constexpr int CL = LEAF / 8;
-    static constexpr int CH = 8 * NL;
-    static constexpr int CPL = CH > TPP ? CH / TPP : 1;     // chains per thread
-    static constexpr int ACT = CH < TPP ? CH : TPP;         // threads holding a chain
-    static constexpr int WACT = ACT < 64 ? ACT : 64;        // ... per wave
-    static constexpr int NPT = N / TPP;                     // samples per thread
-    static constexpr int XPAD = N + 8 * NL;
-    static constexpr int XBYTES = ((XPAD * (D64 ? 8 : 4) + 15) / 16) * 16;   // X: f32, or f64 (data_f64)
-    static constexpr int CBYTES = M * 16;   // complex points at cidx(q)
-    static constexpr int WORK_BYTES = XBYTES > CBYTES ? XBYTES : CBYTES;
-    static constexpr int RED_BYTES = WPP > 1 ? 512 : 0;     // cross-wave partials
-    static constexpr int GROUP_BYTES = WORK_BYTES + RED_BYTES;
-    static constexpr int LG = __builtin_ctz(M);
-    static constexpr int TW = 2 * M;   // twiddle entries: M post-processing + <= M stage tables
-    // multi-wave groups: the table (up to 64 KiB) would cost blocks; it is read
-    // through L1/L2 and the LDS holds only the groups' work arrays
-    static constexpr bool TWG = WPP > 1;
-    static constexpr int TW_LDS = TWG ? 0 : TW;
-};
-
-__device__ __forceinline__ int xaddr(int idx) { return idx + 8 * (idx >> 7); }
-
-// xaddr((j0 + TPP u) mod N) for 0 <= j0 < N, in 3 VALU ops per u: the
-// unwrapped address has compile-time offsets from one base (two for TPP = 64:
-// xaddr(j0 + 64 u) = xaddr(j0) + 64 u + 8 ((u + bit6(j0)) >> 1)), and
-// xaddr(j + N) = xaddr(j) + xaddr(N), so the wrap is an unsigned min
-template <int N, int TPP>
-struct XWrap {
-    int a0, a1;
-    __device__ __forceinline__ explicit XWrap(int j0) : a0(xaddr(j0)), a1(TPP == 64 ? xaddr(j0) + ((j0 >> 3) & 8) : 0) {}
-    __device__ __forceinline__ int operator()(int u) const
-    {
-        constexpr int XN = N + 8 * (N >> 7);
-        const int off = TPP % 128 == 0 ? u * (TPP + TPP / 16) : 64 * u + 8 * (u >> 1);
-        const int au = ((TPP == 64 && (u & 1)) ? a1 : a0) + off;
-        return (int)min((unsigned)au, (unsigned)(au - XN));
-    }
-};
-// complex work array slot of point q: XOR swizzle of the low 3 bits with bits
-// 3-5.  Conflict-free for every access of the kernel: the radix-8 scatters
-// (ds_write_b128, 8-lane groups over 32 banks: low bits (b&7)^r or r^(b&7)) and
-// the contiguous / reversed gathers (ds_read_b128, 16-lane groups over 64 banks).
-__device__ __forceinline__ int cidx(int q) { return q ^ ((q >> 3) & 7); }
-// Address forms with compile-time offsets (the thread index is opaque to the
-// compiler, so it cannot split these itself):
-//   cidx(x + 64 m) = cidx(x) + 64 m                 (the XOR reads bits 3-5 only)
-//   xaddr(x + 8 q) = xaddr(x) + 8 q                 if x % 128 + 8 q < 128
-//   xaddr(x + 128 m) = xaddr(x) + 136 m
-
-// barrier of a profile group: one wave needs only ordering of its LDS ops
-template <int WPP>
-__device__ __forceinline__ void gsync()
-{
-    if constexpr (WPP > 1) __syncthreads();
-    else wave_sync();
-}
-
-template <typename T, int CPL>
-__device__ __forceinline__ T tree_slots(const T (&v)[CPL])
-{
-    if constexpr (CPL == 1) return v[0];
-    else if constexpr (CPL == 2) return v[0] + v[1];
-    else if constexpr (CPL == 4) return (v[0] + v[1]) + (v[2] + v[3]);
-    else return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));   // CPL == 8
-}
-
-// Group-uniform reduction of a per-thread value: the wave tree over its WACT
-// active lanes, then (WPP > 1) a balanced tree over the group's waves through
-// `red` (WPP <= 8 slots of 8 B, one slot array per call site; both barriers keep
-// the slots reusable on the next profile).  With the wave tree this is numpy's
-// pairwise order: wave w holds leaves 8w .. 8w + 7, so waves pair up as the
-// leaves' blocks of 8 do.
-template <int WPP, int WACT, typename T, typename Op>
-__device__ __forceinline__ T group_tree(T v, Op op, T *red, int wave, int lane)
-{
-    T w = wave_tree<WACT>(v, op);
-    if constexpr (WPP == 1) {
-        return w;
-    } else {
-        if (lane == 0) red[wave] = w;
-        __syncthreads();
-        T r;
-        static_assert(WPP == 2 || WPP == 4 || WPP == 8, "the balanced tree is spelled out for 2, 4 and 8 waves");
-        if constexpr (WPP == 2) r = op(red[0], red[1]);
-        else if constexpr (WPP == 4) r = op(op(red[0], red[1]), op(red[2], red[3]));
-        else r = op(op(op(red[0], red[1]), op(red[2], red[3])), op(op(red[4], red[5]), op(red[6], red[7])));
-        __syncthreads();
-        return r;
-    }
-}
-
-// chain sums (one per slot) -> the pairwise total over the group, balanced
-// over threads, then over slots
-template <int N, typename T>
-__device__ __forceinline__ T chain_total(const T (&cs)[P2<N>::CPL], T *red, int wave, int lane)
-{
-    using C = P2<N>;
-    T fs[C::CPL];
-#pragma unroll
-    for (int sl = 0; sl < C::CPL; ++sl) fs[sl] = group_tree<C::WPP, C::WACT>(cs[sl], OpAdd(), red + 8 * sl, wave, lane);
-    return tree_slots<T, C::CPL>(fs);
-}
-
-// One radix-R Stockham stage (compile-time R, NS = product of earlier radices),
-// in place: every input of the stage is in registers before it writes.
-// stw: this stage's twiddles w^(r k), w = exp(-2 pi i/(R NS)), as [k][r-1]
-// (host-built in long double; no recurrences).  FIRST: the input is the real
-// signal X (f32, padded addresses) minus mu, read as complex pairs.
-// DER: only each butterfly's base twiddle w = stw[k][0] is read; w^2 .. w^(R-1)
-// come from repeated complex products (a few ulp off the table's correctly
-// rounded values: the FFT diagnostic is compared within 1e-9, and this trades
-// R - 2 LDS reads for 4 (R - 2) VALU ops per butterfly)
-template <int R, int NS, bool FIRST, int M, int TPP, typename XT, bool DER = false>
-__device__ __forceinline__ void p2_stage(double2 *C, const XT *X, double mu, const double2 *stw, int t)
-{
-    constexpr int NB = M / R;
-    constexpr int BPL = (NB + TPP - 1) / TPP;
-    double2 v[BPL][R];
-#pragma unroll
-    for (int u = 0; u < BPL; ++u) {
-        const int b = t + TPP * u;
-        if (NB % TPP == 0 || b < NB) {
-            // 2 q = 2 b + 2 r NB: a multiple of 128 apart when NB % 64 == 0
-            const XT *xb = X + xaddr(2 * b);
-            const double2 *cb = C + cidx(b);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int q = b + r * NB;
-                if (FIRST) {
-                    const XT *xq = NB % 64 == 0 ? xb + r * (2 * NB + NB / 8) : X + xaddr(2 * q);
-                    if constexpr (sizeof(XT) == 8) {
-                        const double2 xv = *(const double2 *)xq;
-                        v[u][r] = make_double2(xv.x - mu, xv.y - mu);
-                    } else {
-                        const float2 xv = *(const float2 *)xq;
-                        v[u][r] = make_double2((double)xv.x - mu, (double)xv.y - mu);
-                    }
-                } else {
-                    v[u][r] = NB % 64 == 0 ? cb[r * NB] : C[cidx(q)];
-                }
-            }
-        }
-    }
-    gsync<TPP / 64>();
-#pragma unroll
-    for (int u = 0; u < BPL; ++u) {
-        const int b = t + TPP * u;
-        if (NB % TPP == 0 || b < NB) {
-            const int k = b & (NS - 1);
-            if (NS > 1) {
-                const double2 *tk = stw + k * (R - 1);
-                if constexpr (DER) {
-                    const double2 w1 = tk[0];
-                    double2 wr = w1;
-#pragma unroll
-                    for (int r = 1; r < R; ++r) {
-                        if (r > 1) wr = cmul_f(wr, w1);
-                        v[u][r] = cmul_f(v[u][r], wr);
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 1; r < R; ++r) v[u][r] = cmul_f(v[u][r], tk[r - 1]);
-                }
-            }
-            dft_small<R>(v[u]);
-            const int idx = (b - k) * R + k;
-            if constexpr (NS % 64 == 0) {
-                double2 *cw = C + cidx(idx);
-#pragma unroll
-                for (int r = 0; r < R; ++r) cw[r * NS] = v[u][r];
-            } else if constexpr (NS == 8 && R == 8) {
-                // idx = 64 m + k (k < 8): cidx(idx + 8 r) = 64 m + 8 r + (k ^ r)
-#pragma unroll
-                for (int r = 0; r < R; ++r) C[(idx ^ r) + 8 * r] = v[u][r];
-            } else if constexpr (NS == 1 && R == 8) {
-                // idx = 8 b: cidx(idx + r) = idx + (r ^ (b & 7)) = (idx + (b & 7)) ^ r
-                const int A = idx + (b & 7);
-#pragma unroll
-                for (int r = 0; r < R; ++r) C[A ^ r] = v[u][r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) C[cidx(idx + r * NS)] = v[u][r];
-            }
-        }
-    }
-    gsync<TPP / 64>();
-}
-
-// the whole N/2-point FFT as a compile-time chain of stages (radix 8 while >= 3
-// levels remain, then 4 or 2); OFF = offset of the next stage table in tw
-template <int M, int TPP, int LG, int DONE, int NS, int OFF, typename XT, bool DER = false>
-__device__ __forceinline__ void p2_fft(double2 *C, const XT *X, double mu, const double2 *tw, int t)
-{
-    if constexpr (DONE < LG) {
-        constexpr int REM = LG - DONE;
-        constexpr int R = REM >= 3 ? 8 : (REM == 2 ? 4 : 2);
-        constexpr int LR = R == 8 ? 3 : (R == 4 ? 2 : 1);
-        p2_stage<R, NS, DONE == 0, M, TPP, XT, DER>(C, X, mu, tw + OFF, t);
-        p2_fft<M, TPP, LG, DONE + LR, NS * R, (NS > 1 ? OFF + NS * (R - 1) : OFF), XT, DER>(C, X, mu, tw, t);
-    }
-}
-
 // occupancy floors (waves per SIMD, <= 128 VGPRs): 4 for the multi-wave groups
 // (the LDS allows 4 blocks of 4096 per CU and 2 of 8192, 16 waves either way)
 // and for N = 1024 (the LDS allows 4
@@ -3148,7 +2763,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
             if (PREFETCH && snext < nslot) loadrow((unsigned)rl.at(snext));
             continue;
         }
-        const bool ok = st >= 1 && st <= 4;
+        const bool ok = fit_ok(st);
         // residual -> X (dispersed frame, padded addresses)
         // X = apply_weights(R, w0): f32(R * w), or f64(R) * f64(w) for f64 data
         auto weigh = [&](float R) -> XT {
@@ -3179,17 +2794,16 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
                 for (int u = 0; u < NPT; ++u) {
                     const int i = (i0 + TPP * u) & (N - 1);
                     const float pj = pv[u] - bk;
-                    double e = x * tg[u] - (double)pj;
-                    if (i >= a.pr_start && i < a.pr_end) e = e * a.pr_factor;
-                    const float R = ok ? (float)e : 0.0f;
+                    const float e = residual_sample(x, tg[u], pj, i, PulseRegion{true, a.pr_start, a.pr_end, a.pr_factor});
+                    const float R = ok ? e : 0.0f;
                     X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)] = weigh(R);
                 }
             } else {
 #pragma unroll
                 for (int u = 0; u < NPT; ++u) {
                     const float pj = pv[u] - bk;
-                    const double e = x * tg[u] - (double)pj;
-                    const float R = ok ? (float)e : 0.0f;
+                    const float e = residual_sample(x, tg[u], pj);
+                    const float R = ok ? e : 0.0f;
                     X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)] = weigh(R);
                 }
             }
@@ -3198,6 +2812,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
 #pragma unroll
             for (int u = 0; u < NPT; ++u) {
                 const int i = t + TPP * u;
+                // residual_sample, restated: either call changed some closed forms of this kernel
                 const double uu = x * (TREG ? tv[u] : T[i]);
                 double e = uu - (double)pv[u];
                 if (i >= a.pr_start && i < a.pr_end) e = e * a.pr_factor;
@@ -3209,9 +2824,8 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
 #pragma unroll
             for (int u = 0; u < NPT; ++u) {
                 const int i = t + TPP * u;
-                const double uu = x * (TREG ? tv[u] : T[i]);
-                const double e = uu - (double)pv[u];
-                const float R = ok ? (float)e : 0.0f;
+                const float e = residual_sample(x, TREG ? tv[u] : T[i], pv[u]);
+                const float R = ok ? e : 0.0f;
                 X[xw(u)] = weigh(R);
             }
         }
@@ -3227,8 +2841,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
             nsh = mode == DIAG_STATS ? 0 : a.shift[kn % (unsigned)nchan];
         }
         gsync<WPP>();
-        // masked ptp data is numpy.ma's fill value of the dtype: 1e20 (f64) / f32(1e20)
-        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = D64 ? 1e20 : (double)1e20f;
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(D64);
         if (valid) {
             // chain values -> registers
             XT v[C::CPL][C::CL];
@@ -3306,30 +2919,17 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
             constexpr int H = C::M / 2;
             constexpr int JF = H / TPP;   // pair tasks every thread holds
             double best2 = 0.0, nsum = 0.0;
-            auto post = [&](const double2 zk, const double2 zm, const double2 wv) {
-                const double er = zk.x + zm.x, ei = zk.y - zm.y;
-                const double orr = zk.y + zm.y, oi = zm.x - zk.x;
-                const double tr = __builtin_fma(orr, wv.x, -(oi * wv.y));
-                const double ti = __builtin_fma(orr, wv.y, oi * wv.x);
-                const double re = er + tr, im = ei + ti;
-                const double rm = er - tr, imm = ti - ei;
-                const double a2 = __builtin_fma(re, re, im * im);
-                const double b2 = __builtin_fma(rm, rm, imm * imm);
-                nsum = nsum + a2;
-                nsum = nsum + b2;
-                best2 = fmax(best2, fmax(a2, b2));
-            };
 #pragma unroll
             for (int j = 0; j < JF; ++j) {
                 // kk = t + TPP j, M - kk = (TPP - t) + (M - TPP (j + 1)): 64-multiples apart
                 const int kk = t + TPP * j;
                 const double2 zk = Cb[cidx(t) + TPP * j];
                 const double2 zm = Cb[kk == 0 ? 0 : cidx(TPP - t) + (C::M - TPP * (j + 1))];
-                post(zk, zm, tw[kk]);
+                spec_pair_nan(zk, zm, tw[kk], best2, nsum);
             }
             {
                 const int kk = t + TPP * JF;   // the rest: kk <= M/2 (one thread at N >= 256)
-                if (kk <= H) post(Cb[cidx(kk)], Cb[cidx(kk == 0 ? 0 : C::M - kk)], tw[kk]);
+                if (kk <= H) spec_pair_nan(Cb[cidx(kk)], Cb[cidx(kk == 0 ? 0 : C::M - kk)], tw[kk], best2, nsum);
             }
             int nanf = isnan(nsum);
             best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 52, wave, lane);
@@ -3342,7 +2942,7 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
             nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 48), wave, lane);
             fftv = nanx ? NAN : 0.0;
         }
-        if (t == 0) {
+        if (t == 0) {   // diag_store, restated: the call changed three of this kernel's forms
             a.std_o[k] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
             a.mean_o[k] = valid ? mean : 0.0;
             a.ptp_o[k] = ptp;
@@ -3373,56 +2973,6 @@ __global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) vo
 // DIAG_CLOSED first forms the closed-form amplitude over the same chains (the
 // stored order: the products T_i p_i of the lane's samples j, i = (j - sh) mod
 // N, with the template gathered for the residual).
-constexpr int p2_tw_entries(int N)
-{
-    const int M = N / 2;
-    int lg = 0;
-    while ((1 << lg) < M) ++lg;
-    int n = M;
-    for (int done = 0, ns = 1; done < lg;) {
-        const int rem = lg - done, R = rem >= 3 ? 8 : (rem == 2 ? 4 : 2);
-        if (ns > 1) n += ns * (R - 1);
-        ns *= R;
-        done += R == 8 ? 3 : (R == 4 ? 2 : 1);
-    }
-    return n;
-}
-
-// The one-wave (N = 1024) form: twiddles from an LDS copy (through L1/L2:
-// 2.59 ms per pass against 2.00), 4 waves per SIMD, 8 profile groups per
-// block.  Closed mode takes the dedispersed-order samples of the row by a
-// second global read, not from an LDS copy of the registers' dispersed-order
-// ones: the read misses L2 often enough to add 15 % to the pass's HBM traffic,
-// but the copy costs LDS bandwidth, which binds at N = 1024 (C2 fast mode
-// 2.48 -> 2.62 ms per pass with the copy).  Stage and spectrum twiddles are
-// derived from one base twiddle per butterfly / lane (p2_stage DER; tw[t + L j]
-// = tw[t] exp(-2 pi i j / 16)) instead of read one each for the multi-wave
-// groups (N >= 2048), whose table is read through L1/L2 (C5 k_diag 2.81 ->
-// 2.68 ms per launch); at N = 1024, whose table is in LDS, that measured no
-// faster (2.005 -> 2.03).
-template <int N>
-struct CLay {
-    static constexpr int L = N / 16;     // threads per profile = chains of 16 samples
-    static constexpr int WPP = L / 64;   // waves per profile
-    static constexpr int M = N / 2;
-    static constexpr int LG = __builtin_ctz(M);
-    static constexpr int GPB = WPP > 1 ? 1 : 8;   // profile groups per block
-    static constexpr bool TWG = WPP > 1;   // multi-wave groups read the table through L1/L2
-    static constexpr int TW_LDS = TWG ? 0 : p2_tw_entries(N);
-    static constexpr int CBYTES = M * 16;
-    static constexpr int RED_BYTES = WPP > 1 ? 512 : 0;
-    static constexpr int GROUP_BYTES = CBYTES + RED_BYTES;
-    static_assert(N >= 1024 && L % 64 == 0, "chain layout: one chain of 16 samples per thread");
-};
-
-__device__ __forceinline__ float ufirst(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double ufirst(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
-                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
 template <int N, int MODE>
 __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagArgs a)
 {
@@ -3564,7 +3114,7 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
         }
         // residual (ic.py:279-288) of the dispersed-frame sample j, f32 store
         // (:272), apply_weights (:296): X_j = f32(f32(x T_i - D_i) * w), D_i = f32(raw_j - base0)
-        const bool ok = stats || (st >= 1 && st <= 4);
+        const bool ok = stats || (st >= 1 && st <= 4);   // fit_ok, restated: the call moved the closed mode's code
         const bool valid = w != 0.0f;
         float X[16];
 #pragma unroll
@@ -3592,9 +3142,11 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
             k = (unsigned)kq;
             prefetch(k);
         }
-        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = (double)1e20f;
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(false);
         if (valid) {
             // mean: f32 chain, then the pairwise tree (ic.py:207)
+            // (this chain arithmetic is restated in rot_stats, ic_rotate.hip: edit both.  A
+            // shared helper changed the operand order of the adds in the machine code)
             float s = X[0];
 #pragma unroll
             for (int q = 1; q < 16; ++q) s = s + X[q];
@@ -3654,17 +3206,6 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
             constexpr int H = M / 2;
             constexpr int JF = H / L;
             double best2 = 0.0;
-            auto post = [&](const double2 zk, const double2 zm, const double2 wv) {
-                const double er = zk.x + zm.x, ei = zk.y - zm.y;
-                const double orr = zk.y + zm.y, oi = zm.x - zk.x;
-                const double tr = __builtin_fma(orr, wv.x, -(oi * wv.y));
-                const double ti = __builtin_fma(orr, wv.y, oi * wv.x);
-                const double re = er + tr, im = ei + ti;
-                const double rm = er - tr, imm = ti - ei;
-                const double a2 = __builtin_fma(re, re, im * im);
-                const double b2 = __builtin_fma(rm, rm, imm * imm);
-                best2 = fmax(best2, fmax(a2, b2));
-            };
             static_assert(JF == 4 && 16 * L == N, "tw[t + L j] = tw[t] exp(-2 pi i j / 16)");
             const double2 wt = tw[t];
 #pragma unroll
@@ -3679,20 +3220,12 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
                     constexpr double s16[4] = {0.0, 0.38268343236508977173, 0.70710678118654752440,
                                                0.92387953251128675613};
                     const double2 wj = make_double2(c16[j], -s16[j]);
-                    post(zk, zm, j == 0 ? wt : cmul_f(wt, wj));
+                    spec_pair(zk, zm, j == 0 ? wt : cmul_f(wt, wj), best2);
                 } else {
-                    post(zk, zm, tw[kk]);
+                    spec_pair(zk, zm, tw[kk], best2);
                 }
             }
-            {
-                // the self-paired bin k = M/2 (one task): post(Z, Z, w) with the
-                // exact zeros ei = oi = 0 of a finite Z folded in, on every lane
-                const double2 z = Cb[cidx(H)], wv = tw[H];
-                const double er = z.x + z.x, orr = z.y + z.y;
-                const double tr = orr * wv.x, ti = orr * wv.y;
-                const double re = er + tr, rm = er - tr, q2 = ti * ti;
-                best2 = fmax(best2, fmax(__builtin_fma(re, re, q2), __builtin_fma(rm, rm, q2)));
-            }
+            spec_self_pair(Cb[cidx(H)], tw[H], best2);   // k = M/2 (one task, on every lane)
             best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 44, wave, lane);
             fftv = isfinite(s32) ? 0.5 * sqrt(best2) : (double)NAN;
         } else {
@@ -3703,12 +3236,7 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
             nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 52), wave, lane);
             fftv = nanx ? NAN : 0.0;
         }
-        if (t == 0) {
-            a.std_o[kc] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
-            a.mean_o[kc] = valid ? mean : 0.0;
-            a.ptp_o[kc] = ptp;
-            a.fft_o[kc] = fftv;
-        }
+        if (t == 0) diag_store(a, kc, valid, mean, sd, ptp, fftv);
     }
 }
 
@@ -3725,8 +3253,7 @@ __global__ __launch_bounds__(256) void k_residual(const float *__restrict__ D, c
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (size_t k = (size_t)blockIdx.x * 4 + wave; k < P; k += (size_t)gridDim.x * 4) {
         const int sh = shift[k % nchan];
-        const int st = info[k];
-        const bool ok = st >= 1 && st <= 4;
+        const bool ok = fit_ok(info[k]);
         const double a = amp[k];
         const float b = D ? 0.0f : base[k];
         for (int i = lane; i < nbin; i += 64) {
@@ -3735,1112 +3262,10 @@ __global__ __launch_bounds__(256) void k_residual(const float *__restrict__ D, c
             float v = 0.0f;
             if (ok) {
                 const float p = D ? D[d_ofs(k, i, ldD, dtiled)] : raw[k * nbin + j] - b;
-                const double u = a * T64[i];
-                double e = u - (double)p;
-                if (pr_on && i >= pr_start && i < pr_end) e = e * pr_factor;
-                v = (float)e;
+                v = residual_sample(a, T64[i], p, i, PulseRegion{pr_on != 0, pr_start, pr_end, pr_factor});
             }
             R[k * nbin + j] = v;
         }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Fractional dedispersion: psrchive's FFT phase rotation in the stand-in's
-// written order (phase_rotation.py; oracle orc_rotate), in IEEE f32 as
-// psrchive's.  A profile per wave (N <= 1024: four to a block, sharing the
-// twiddle tables staged in LDS) or per block (N >= 2048); grid-stride over
-// channel-major items so that the profiles in flight share a channel's phasor
-// row in L2; the N/2 complex points live in LDS between the passes.
-//   1. z[j] = (f32(x[2j] - b), f32(x[2j+1] - b))
-//   2. Z = FFT_{N/2}(z): Stockham stages of radix 8 (then 4 or 2), one LDS
-//      round trip per stage
-//   3. pairs (k, N/2 - k): real spectrum, x phasor, inverse half-spectrum
-//      (conj) in one linear map (rot_pair)
-//   4. r = FFT_{N/2}(that); out = r.re / M, -r.im / M
-// A complex point is an f32 pair (rc2) and every complex operation one packed
-// VOP3P instruction (v_pk_add_f32 / v_pk_mul_f32 with op_sel / neg modifiers
-// for the swaps and the one-sided signs), each half an IEEE f32 operation of
-// the definition: the same bits as the oracle's scalar f32 code
-// (-ffp-contract=off), at half the f64 instruction count.
-typedef float rc2 __attribute__((ext_vector_type(2)));
-
-#ifndef IC_ROT_TW_LDS_MAX
-#define IC_ROT_TW_LDS_MAX 4096   // the longest nbin whose rotation stages its twiddle table in LDS
-#endif
-
-template <int N>
-struct RotCfg {
-    static constexpr int M = N / 2, H = M / 2;
-    static constexpr int LG = __builtin_ctz(M);   // log2 M
-    static constexpr int TB = M / 8 < 64 ? 64 : (M / 8 > 256 ? 256 : M / 8);
-    // one-wave profiles run four to a block, which stages the twiddle table in
-    // LDS once for all four; the one-block profiles of N = 2048 / 4096 stage it too,
-    // once per block of the grid-stride loop (16 profiles per block at C5:
-    // 62.7-63.1 -> 58.0-58.2 ms per C5 clean in the FFT mode, against f64
-    // entries through L1/L2 rounded at each use)
-    static constexpr int WPB = TB == 64 ? 4 : 1;
-    // N = 8192: the f32 table (64 KiB) beside the 36 KiB of points would leave
-    // one block (one wave per SIMD) per CU; its entries are read as f64 through
-    // L1/L2 and rounded at the use (TwGlobal): the LDS then allows 4 blocks per
-    // CU and the 251-256 VGPRs two (2 waves per SIMD).  Measured on a 64 x 512
-    // x 8192 archive, alternating: 33.0-33.2 ms per clean with per-profile
-    // delays and 33.9-34.1 per channel, against 38.5-38.6 and 40.3-40.5 staged
-    // (-DIC_ROT_TW_LDS_MAX=8192 builds the staged form, tools/build_variant.sh)
-    static constexpr bool TW_LDS = N <= IC_ROT_TW_LDS_MAX;
-};
-
-// LDS slot of complex point i: one pad slot after every 8 points.  With 8-byte
-// points ds_write_b64 banks 16 contiguous lanes on (slot mod 16) and ds_read_b64
-// 32 lanes on (slot mod 32) (MI355X_MICROARCH.md): the stage stores (lane t ->
-// points 8 t + q, and 64 (t / 8) + t % 8 + 8 q) are conflict-free, the
-// contiguous reads (t + 64 q) 2-way on 3 of 32 banks.  A XOR swizzle cannot
-// make the stores conflict-free without per-q address arithmetic on the reads
-// (bits 6+ of the slot change with q).  All offsets are per-lane bases plus
-// immediates: rsl(i + 8 c) = rsl(i) + 9 c.
-__device__ __forceinline__ constexpr int rsl(int i) { return i + (i >> 3); }
-template <int M> constexpr int rot_slots() { return M + M / 8; }
-
-// packed complex arithmetic (each half one IEEE f32 operation)
-__device__ __forceinline__ rc2 pk_nlo(rc2 a, rc2 b)   // (a.x - b.x, a.y + b.y)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_nhi(rc2 a, rc2 b)   // (a.x + b.x, a.y - b.y)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_mi(rc2 a, rc2 b)   // a + (-i) b = (a.x + b.y, a.y - b.x)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_pi(rc2 a, rc2 b)   // a + i b = (a.x - b.y, a.y + b.x)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_c7(rc2 c)   // (c.y - c.x, c.x + c.y)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1]" : "=v"(r) : "v"(c));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_cross(rc2 a, rc2 b)   // (a.y + b.y, a.x - b.x)
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 pk_addc(rc2 a, rc2 b)   // (a.x + b.x, (-a.y) + (-b.y))
-{
-    rc2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ rc2 rc2_of(double2 d) { return (rc2){(float)d.x, (float)d.y}; }
-
-// 8-byte loads of the phasor table / 16-byte loads of the f64 twiddle table
-// through a buffer descriptor: a 32-bit per-lane offset plus an immediate,
-// instead of a 64-bit address register per table entry kept live across the
-// profile loop
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rot_rsrc(const void *p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ double2 rot_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)
-{
-    return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ rc2 rot_ld2(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)
-{
-    return __builtin_bit_cast(rc2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
-
-// Twiddle sources: k_diag_p2's table (p2_twiddles: M plain entries tw[i] =
-// exp(-2 pi i i / N), then for every Stockham stage after the first, of radix
-// R and span ns, the entries w^(q k), w = exp(-2 pi i / (R ns)), as [k][q - 1]
-// at M + ns - 8: the spans are 8, 64, 512, so the earlier tables fill ns - 8
-// slots), the same long-double values rounded to f64; the rotation uses them
-// rounded to f32.  Staged in LDS as f32 (TwLds32; with the statistics, whose
-// FFT needs the f64 table in LDS too, the f32 stage tables only: TwLdsSt), or
-// read as f64 through L1/L2 and rounded at the use (TwGlobal, one-block
-// profiles N = 8192, whose f32 table would take 64 KiB).
-template <int N>
-struct TwGlobal {
-    static constexpr bool ASM_ROWS = false;
-    __amdgpu_buffer_rsrc_t r;
-    template <int NS, int R>
-    __device__ __forceinline__ rc2 stage(unsigned k, int q) const
-    {
-        return rc2_of(rot_ld(r, 16u * (unsigned)(k * (R - 1)), 16u * (unsigned)(N / 2 + NS - 8 + q - 1)));
-    }
-    __device__ __forceinline__ rc2 post(unsigned i) const { return rc2_of(rot_ld(r, 16u * i, 0)); }
-};
-template <int N>
-struct TwLds32 {
-    static constexpr bool ASM_ROWS = true;   // rot_pass reads the stage rows with ds_read_b64
-    const rc2 *t;
-    template <int NS, int R>
-    __device__ __forceinline__ rc2 stage(unsigned k, int q) const
-    {
-        return t[N / 2 + NS - 8 + q - 1 + k * (R - 1)];
-    }
-    // LDS byte address of entry [k][0] of the stage table of span NS
-    template <int NS, int R>
-    __device__ __forceinline__ uint32_t row(unsigned k) const
-    {
-        return lds_u32(t + (N / 2 + NS - 8 + k * (R - 1)));
-    }
-    __device__ __forceinline__ rc2 post(unsigned i) const { return t[i]; }
-};
-// with the statistics: the f32 stage tables alone (s: the entries from M on)
-// beside the f64 table the statistics FFT reads, whose plain part serves the
-// post step (rounded at the use); 53 KB of LDS per four-wave block, three
-// blocks per CU
-template <int N>
-struct TwLdsSt {
-    static constexpr bool ASM_ROWS = true;
-    const rc2 *s;
-    const double2 *t;
-    template <int NS, int R>
-    __device__ __forceinline__ rc2 stage(unsigned k, int q) const
-    {
-        return s[NS - 8 + q - 1 + k * (R - 1)];
-    }
-    template <int NS, int R>
-    __device__ __forceinline__ uint32_t row(unsigned k) const
-    {
-        return lds_u32(s + (NS - 8 + k * (R - 1)));
-    }
-    __device__ __forceinline__ rc2 post(unsigned i) const { return rc2_of(t[i]); }
-};
-
-// the rotation's complex product (a.r w.r - a.i w.i, a.r w.i + a.i w.r):
-// (a.r w.r, a.r w.i) and (a.i w.i, a.i w.r), then one add with the low half
-// subtracted
-__device__ __forceinline__ rc2 rot_cmul(rc2 a, rc2 w)
-{
-    return pk_nlo(a.xx * w, a.yy * w.yx);
-}
-// DFT of 4 / 8 points in place, natural output order, in the written order of
-// phase_rotation.py (_dft4, _dft8) and the oracle (dft4, dft8): c3 = -i d is
-// folded into y1 = c1 + c3 = pk_mi(c1, d) and y3 = c1 - c3 = pk_pi(c1, d)
-// (x + (-y) is x - y bit for bit), and c6 = -i c6 into the odd DFT_4's first
-// level the same way
-__device__ __forceinline__ void rot_dft4(rc2 *b)
-{
-    const rc2 c0 = b[0] + b[2], c1 = b[0] - b[2], c2 = b[1] + b[3], d = b[1] - b[3];
-    b[0] = c0 + c2;
-    b[1] = pk_mi(c1, d);
-    b[2] = c0 - c2;
-    b[3] = pk_pi(c1, d);
-}
-__device__ __forceinline__ void rot_dft8(rc2 *b)
-{
-    constexpr float s = (float)0x1.6a09e667f3bcdp-1;   // f32(f64(sqrt(2)/2))
-    rc2 c[8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        c[q] = b[q] + b[q + 4];
-        c[q + 4] = b[q] - b[q + 4];
-    }
-    c[5] = pk_mi(c[5], c[5]) * (rc2){s, s};    // ((c.r + c.i) s, (c.i - c.r) s)
-    c[7] = pk_c7(c[7]) * (rc2){s, -s};         // ((c.i - c.r) s, -((c.r + c.i) s))
-    rot_dft4(c);
-    // odd DFT_4 of (c4, c5, -i c6, c7)
-    const rc2 e0 = pk_mi(c[4], c[6]), e1 = pk_pi(c[4], c[6]), e2 = c[5] + c[7], d = c[5] - c[7];
-    b[0] = c[0];
-    b[2] = c[1];
-    b[4] = c[2];
-    b[6] = c[3];
-    b[1] = e0 + e2;
-    b[3] = pk_mi(e1, d);
-    b[5] = e0 - e2;
-    b[7] = pk_pi(e1, d);
-}
-
-// One Stockham stage of radix Q = 2^R and span ns = 2^LGS (phase_rotation.py
-// _stockham): group ja < G = M/Q holds the points v[ja + q G]; from the second
-// stage on they are multiplied by the stage's twiddles w^(q k), k = ja mod ns,
-// then transformed by DFT_Q, and y_p lands at v[(ja - k) Q + k + p ns].  One LDS
-// round trip per stage (8 points per lane at N = 1024, three stages per FFT).
-// IN_REG: the pass's input is z (one group per thread, G == TB) instead of
-// LDS; OUT_REG: its output stays in z.  The last pass's group ja holds points
-// ja + q G, the distribution the first pass reads, so a profile can enter and
-// leave the FFT in registers (k_rotate's direct layout).
-template <int N, int R, int LGS, bool IN_REG = false, bool OUT_REG = false, typename TW>
-__device__ __forceinline__ void rot_pass(rc2 *v, const TW &tw, int t, rc2 *z = nullptr)
-{
-    using C = RotCfg<N>;
-    constexpr int M = C::M, TB = C::TB, G = M >> R, Q = 1 << R;
-    constexpr int GPT = (G + TB - 1) / TB;
-    constexpr int ns = 1 << LGS;
-    static_assert(!(IN_REG || OUT_REG) || G == TB, "register passes hold one group per thread");
-    static_assert(ns == 1 || ns >= 8, "stage spans are 1, 8, 64, 512");
-    rc2 u[GPT][Q];
-    // the stage's twiddles first (their latency overlaps the LDS reads and the barrier)
-    rc2 w[GPT][Q - 1];
-    // one-group-per-lane passes read their points (and the f32 twiddle rows)
-    // as separate ds_read_b64 in asm: the compiler pairs adjacent 8-byte LDS
-    // loads into ds_read2_b64, which serves 16-lane groups on 32 banks at 4x
-    // the LDS cycles per byte (MI355X_MICROARCH.md); one lgkmcnt wait ties
-    // the values
-    constexpr bool ASM = GPT == 1 && G == TB && G % 8 == 0 && !IN_REG;
-    if constexpr (ASM) {
-        const int ja = t, k = ja & (ns - 1);
-        if constexpr (ns > 1 && TW::ASM_ROWS) {
-            const uint32_t wa = tw.template row<ns, Q>((unsigned)k);
-#pragma unroll
-            for (int q = 1; q < Q; ++q)
-                asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(w[0][q - 1]) : "v"(wa), "i"(8 * (q - 1)));
-        } else if constexpr (ns > 1) {
-#pragma unroll
-            for (int q = 1; q < Q; ++q) w[0][q - 1] = tw.template stage<ns, Q>((unsigned)k, q);
-        }
-        const uint32_t va = lds_u32(v + rsl(ja));   // rsl(ja + q G) = rsl(ja) + q (G + G/8)
-#pragma unroll
-        for (int q = 0; q < Q; ++q)
-            asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(u[0][q]) : "v"(va), "i"(8 * q * (G + G / 8)));
-        if constexpr (Q == 8) {
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(u[0][0]), "+v"(u[0][1]), "+v"(u[0][2]), "+v"(u[0][3]), "+v"(u[0][4]), "+v"(u[0][5]),
-                           "+v"(u[0][6]), "+v"(u[0][7]));
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(u[0][q]));
-        }
-        if constexpr (ns > 1 && TW::ASM_ROWS) {
-#pragma unroll
-            for (int q = 0; q < Q - 1; ++q) asm volatile("" : "+v"(w[0][q]));
-        }
-    }
-#pragma unroll
-    for (int gi = 0; gi < GPT && !ASM; ++gi) {
-        const int ja = t + TB * gi;
-        const int k = ja & (ns - 1);
-        if (G % TB == 0 || ja < G) {
-            if constexpr (ns > 1) {
-#pragma unroll
-                for (int q = 1; q < Q; ++q) w[gi][q - 1] = tw.template stage<ns, Q>((unsigned)k, q);
-            }
-            if constexpr (IN_REG) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) u[gi][q] = z[q];
-            } else if constexpr (G % 8 == 0) {
-                const rc2 *vj = v + rsl(ja);    // rsl(ja + q G) = rsl(ja) + q (G + G/8)
-#pragma unroll
-                for (int q = 0; q < Q; ++q) u[gi][q] = vj[q * (G + G / 8)];
-            } else {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) u[gi][q] = v[rsl(ja + q * G)];
-            }
-        }
-    }
-    gsync<C::TB / 64>();
-#pragma unroll
-    for (int gi = 0; gi < GPT; ++gi) {
-        const int ja = t + TB * gi;
-        if (G % TB == 0 || ja < G) {
-            const int k = ja & (ns - 1);
-            if constexpr (ns > 1) {
-#pragma unroll
-                for (int q = 1; q < Q; ++q) u[gi][q] = rot_cmul(u[gi][q], w[gi][q - 1]);
-            }
-            if constexpr (Q == 8) {
-                rot_dft8(u[gi]);
-            } else if constexpr (Q == 4) {
-                rot_dft4(u[gi]);
-            } else {
-                const rc2 a = u[gi][0], b = u[gi][1];
-                u[gi][0] = a + b;
-                u[gi][1] = a - b;
-            }
-            const int base = ((ja >> LGS) << (LGS + R)) + k;
-            if constexpr (OUT_REG) {
-                static_assert(ns * Q == M, "only the last pass keeps its output");
-#pragma unroll
-                for (int q = 0; q < Q; ++q) z[q] = u[gi][q];
-            } else if constexpr (ns % 8 == 0) {
-                rc2 *vb = v + rsl(base);   // rsl(base + q ns) = rsl(base) + q (ns + ns/8)
-#pragma unroll
-                for (int q = 0; q < Q; ++q) vb[q * (ns + ns / 8)] = u[gi][q];
-            } else {
-                // ns = 1: base = Q ja, a multiple of 8 for Q = 8 (rsl(base + q) = rsl(base) + q)
-                rc2 *vb = v + rsl(base);
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    if constexpr (Q == 8) vb[q] = u[gi][q];
-                    else v[rsl(base + q)] = u[gi][q];
-                }
-            }
-        }
-    }
-    gsync<C::TB / 64>();
-}
-
-// the full N/2-point FFT: passes of 3 stages (the last one shorter); IN_REG /
-// OUT_REG: the first pass reads z / the last pass leaves its output in z
-template <int N, int LG0 = 0, bool IN_REG = false, bool OUT_REG = false, typename TW>
-__device__ __forceinline__ void rot_fft(rc2 *v, const TW &tw, int t, rc2 *z = nullptr)
-{
-    constexpr int LG = RotCfg<N>::LG;
-    if constexpr (LG0 < LG) {
-        constexpr int R = LG - LG0 >= 3 ? 3 : LG - LG0;
-        constexpr bool LAST = LG0 + R >= LG;
-        rot_pass<N, R, LG0, IN_REG && LG0 == 0, OUT_REG && LAST>(v, tw, t, z);
-        rot_fft<N, LG0 + R, false, OUT_REG>(v, tw, t, z);
-    }
-}
-
-// The inverse's half-length inputs Z'_k, Z'_q (q = M - k) from the transform's
-// Z_k, Z_q in one linear map (phase_rotation.py _pair, oracle rot_pair): the
-// real spectrum X_k = E_k + w O_k, the phasors and the inverse's packing
-// composed, Z'_k = A_k Z_k + B_k conj(Z_q), Z'_q = A_q Z_q - conj(B_k) conj(Z_k),
-// with w = exp(-2 pi i k / N) = (c, sn) and the signed phasors pk, pq.  Returns
-// conj(Z'_k), conj(Z'_q) (what the inverse stores; the imaginary part as (-a) +
-// (-b) of the two terms', the definition's order).  Packed: (h1, h2) = ((1 +
-// sn), (1 - sn)) * 0.5; A_k = (h1 pk.r + h2 pq.r, h1 pk.i - h2 pq.i), A_q
-// likewise; B_k = (pk.i + pq.i, pk.r - pq.r) * (-c/2, c/2) (-(x y) = (-x) y);
-// A Z is rot_cmul; B_k conj(Z_q) = (b.r zq.r + b.i zq.i, b.i zq.r - b.r zq.i);
-// -conj(B_k) conj(Z_k) = (b.i zk.i - b.r zk.r, b.i zk.r + b.r zk.i).
-__device__ __forceinline__ void rot_pair(rc2 zk, rc2 zq, rc2 w, rc2 pk, rc2 pq, rc2 &ok, rc2 &oq)
-{
-    rc2 hh;
-    const rc2 one = {1.0f, 1.0f};
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(hh) : "v"(one), "v"(w));
-    hh = hh * (rc2){0.5f, 0.5f};
-    const rc2 hcv = w.xx * (rc2){-0.5f, 0.5f};
-    const rc2 ak = pk_nhi(hh.xx * pk, hh.yy * pq);
-    const rc2 aq = pk_nhi(hh.xx * pq, hh.yy * pk);
-    const rc2 b = pk_cross(pk, pq) * hcv;
-    ok = pk_addc(rot_cmul(ak, zk), pk_nhi(b * zq.xx, b.yx * zq.yy));
-    oq = pk_addc(rot_cmul(aq, zq), pk_nlo(b.yy * zk.yx, b.xx * zk));
-}
-
-// comprehensive_stats (ic.py:206-212) of the rotated residual row held by one
-// wave in the direct layout: z[q] = point j = t + TB q, i.e. R[2j] = f32(z.re /
-// M), R[2j + 1] = f32(-z.im / M) (k_rotate's store), X = f32(R w) (apply_weights,
-// ic.py:111-117, 296).  Every value is k_diag_cl<N, DIAG_STATS>'s, bit for bit:
-// - mean / var / ptp: X goes through the wave's LDS slots once (the padded
-//   xaddr image) and each lane reads its pairwise chain (leaf t/8, accumulator
-//   t%8: samples 128(t/8) + t%8 + 8q); the trees are chain_total's;
-// - fftmax: k_diag_cl's first radix-8 stage reads the points t + 64 r of d =
-//   f64(X) - mean, which is exactly the direct layout this lane holds, so the
-//   rFFT starts from registers; the later stages are p2_fft's with its f64
-//   table (tw_p2, which k_rotate stages in LDS: tw64), the spectrum's post
-//   twiddles tw[k < M] from the same table's plain part.  v: the wave's LDS
-//   work array (M f64 complex points).
-template <int N>
-__device__ __forceinline__ void rot_stats(const RotateArgs &a, size_t p, double2 *v, const double2 *tw64, int t,
-                                          rc2 (&z)[8], float inv, float w)
-{
-    constexpr int M = RotCfg<N>::M, H = M / 2, TB = RotCfg<N>::TB, L = TB;
-    static_assert(N == 1024 && TB == 64 && CLay<N>::L == 64, "one wave per profile, 16 samples per lane");
-    static_assert(RotCfg<N>::TW_LDS, "the statistics FFT reads k_diag's table from the rotation's LDS copy (tw64)");
-    float xr[16];   // sample 2(t + 64 q) + e at xr[2q + e]
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        xr[2 * q] = z[q].x * inv;
-        xr[2 * q + 1] = (-z[q].y) * inv;
-    }
-    if (w != 1.0f) {   // fractional weights (w * 1 = w exactly: skipped)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) xr[e] = xr[e] * w;
-    }
-    const bool valid = w != 0.0f;
-    double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = (double)1e20f;
-    if (valid) {
-        // the row into LDS (the last pass's reads of v are done: rot_pass ends
-        // with gsync), float pairs at xaddr(2j) = 2t + 136 q
-        float *xs = (float *)v;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) *(float2 *)(xs + 2 * t + 136 * q) = make_float2(xr[2 * q], xr[2 * q + 1]);
-        wave_sync();
-        float X[16];
-        {
-            const float *xc = xs + 136 * (t >> 3) + (t & 7);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) X[q] = xc[8 * q];
-        }
-        float s = X[0];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) s = s + X[q];
-        float fs[1] = {s};
-        const float s32 = 0.0f + chain_total<N, float>(fs, (float *)nullptr, 0, t);
-        mean = (double)s32 / (double)N;
-        double r = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const double d = (double)X[q] - mean;
-            const double sq = d * d;
-            r = q == 0 ? sq : r + sq;
-        }
-        double rs[1] = {r};
-        const double ss = 0.0 + chain_total<N, double>(rs, (double *)nullptr, 0, t);
-        sd = sqrt(ss / (double)N);
-        float mx = -INFINITY, mn = INFINITY;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            mx = OpMaxF()(mx, X[q]);
-            mn = OpMinF()(mn, X[q]);
-        }
-        mx = group_tree<1, 64>(mx, OpMaxF(), (float *)nullptr, 0, t);
-        mn = group_tree<1, 64>(mn, OpMinF(), (float *)nullptr, 0, t);
-        int nan = 0;
-        if (isnan(s32)) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) nan |= isnan(X[q]);
-            nan = group_tree<1, 64>(nan, OpOr(), (int *)nullptr, 0, t);
-        }
-        ptp = nan ? (double)NAN : (double)(float)(mx - mn);
-        // rfft of d (ic.py:210-212): stage 1 (radix 8, no twiddles) on the
-        // lane's points t + 64 r, then k_diag_p2's stages in the complex work
-        // array Cb = v (cidx slots, M entries: inside the rotation's padded
-        // array).  The chain reads above precede the stores (one wave: its LDS
-        // operations stay in order)
-        double2 c8[8];
-#pragma unroll
-        for (int r8 = 0; r8 < 8; ++r8) c8[r8] = make_double2((double)xr[2 * r8] - mean, (double)xr[2 * r8 + 1] - mean);
-        dft_small<8>(c8);
-        double2 *Cb = v;
-        {
-            const int A = 8 * t + (t & 7);   // cidx(8t + r) = A ^ r
-#pragma unroll
-            for (int r8 = 0; r8 < 8; ++r8) Cb[A ^ r8] = c8[r8];
-        }
-        wave_sync();
-        p2_fft<M, L, CLay<N>::LG, 3, 8, M, float, false>(Cb, (const float *)nullptr, 0.0, tw64, t);
-        // the spectrum in conjugate bin pairs (k_diag_cl's post, 2 X_k)
-        constexpr int JF = H / L;
-        double best2 = 0.0;
-        auto post = [&](const double2 zk, const double2 zm, const double2 wv) {
-            const double er = zk.x + zm.x, ei = zk.y - zm.y;
-            const double orr = zk.y + zm.y, oi = zm.x - zk.x;
-            const double tr = __builtin_fma(orr, wv.x, -(oi * wv.y));
-            const double ti = __builtin_fma(orr, wv.y, oi * wv.x);
-            const double re = er + tr, im = ei + ti;
-            const double rm = er - tr, imm = ti - ei;
-            const double a2 = __builtin_fma(re, re, im * im);
-            const double b2 = __builtin_fma(rm, rm, imm * imm);
-            best2 = fmax(best2, fmax(a2, b2));
-        };
-#pragma unroll
-        for (int j = 0; j < JF; ++j) {
-            const int kk = t + L * j;
-            const double2 zk = Cb[cidx(t) + L * j];
-            const double2 zm = Cb[kk == 0 ? 0 : cidx(L - t) + (M - L * (j + 1))];
-            post(zk, zm, tw64[kk]);
-        }
-        {
-            // the self-paired bin k = M/2 (k_diag_cl)
-            const double2 zc = Cb[cidx(H)], wv = tw64[H];
-            const double er = zc.x + zc.x, orr = zc.y + zc.y;
-            const double tr = orr * wv.x, ti = orr * wv.y;
-            const double re = er + tr, rm = er - tr, q2 = ti * ti;
-            best2 = fmax(best2, fmax(__builtin_fma(re, re, q2), __builtin_fma(rm, rm, q2)));
-        }
-        best2 = group_tree<1, 64>(best2, OpMaxF(), (double *)nullptr, 0, t);
-        // a non-finite f32 sum means a NaN / Inf sample: some bin is NaN (k_diag_cl)
-        fftv = isfinite(s32) ? 0.5 * sqrt(best2) : (double)NAN;
-    } else {
-        // w = 0: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
-        int nanx = 0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) nanx |= isnan(xr[e]);
-        nanx = group_tree<1, 64>(nanx, OpOr(), (int *)nullptr, 0, t);
-        fftv = nanx ? NAN : 0.0;
-    }
-    if (t == 0) {
-        a.std_o[p] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
-        a.mean_o[p] = valid ? mean : 0.0;
-        a.ptp_o[p] = ptp;
-        a.fft_o[p] = fftv;
-    }
-}
-
-// PP: per-profile delays (a.delay2, ic_set_delays2): each lane evaluates its
-// phasors with ic_phasor instead of loading the channel's table row.
-// ST: the residual's rotation measures its rows instead of storing them
-// (RotateArgs.std_o; the direct layout only): the rotated row R, still in the
-// lane's registers, becomes X = f32(R w0), whose mean / var / ptp run on the
-// numpy pairwise chains (one LDS transposition into k_diag_cl's chain layout,
-// the same trees: the same bits) and whose real spectrum comes from a third
-// pass of the rotation's own FFT (max |rfft|, within 1e-9 of numpy like every
-// diagnostics kernel's).  R never goes to HBM: the residual's 4N write and the
-// statistics pass's 4N read are gone, and so is the R buffer.
-template <int N, bool PP, bool ST = false>
-// 3 waves per SIMD (137-167 VGPRs at N = 1024; 4 waves spill 2-13 VGPRs without
-// the statistics: C2 fft 40.7 either way, fft_pp 40.9 -> 41.3 ms)
-__global__ __launch_bounds__(RotCfg<N>::TB * RotCfg<N>::WPB, N <= 1024 ? 3 : 2) void k_rotate(RotateArgs a)
-{
-    using C = RotCfg<N>;
-    constexpr int M = C::M, H = C::H, TB = C::TB, WPB = C::WPB;
-    constexpr int NJ = (M / 2 + TB - 1) / TB;    // float4 rows per lane (4 samples = 2 points)
-    constexpr int NK = H / TB + 1;               // spectrum pairs (k, M - k) per lane, k <= H
-    // direct layout (every pass radix 8, one group per lane: N = 1024): lane t
-    // loads points t + TB q (q < 8) straight into the first pass's registers and
-    // stores the last pass's registers, which are the same points; two LDS round
-    // trips per profile fewer
-    constexpr bool DIRECT = C::LG % 3 == 0 && (M >> 3) == TB;
-    // the wave's points (rot_slots f32 pairs); with the statistics the same
-    // array holds their f64 FFT's M complex points
-    constexpr int VS = ST ? 2 * M : rot_slots<M>();
-    static_assert(rot_slots<M>() <= VS, "the rotation's slots fit");
-    __shared__ __attribute__((aligned(16))) rc2 vv[WPB][VS];
-    constexpr int TWE = p2_tw_entries(N);   // k_diag_p2's table: M plain + the stage tables
-    // the twiddle table: f32 for the rotation, or f64 when the statistics FFT
-    // needs it (the rotation then rounds each entry at its use)
-    __shared__ rc2 tws32[C::TW_LDS ? (ST ? TWE - M : TWE) : 1];
-    __shared__ double2 tws64[C::TW_LDS && ST ? TWE : 1];
-    const int t = threadIdx.x % TB, wv = threadIdx.x / TB;
-    rc2 *v = vv[wv];
-    const unsigned nsub = (unsigned)a.nsub, nchan = (unsigned)a.nchan;
-    const size_t P = (size_t)nsub * nchan;
-    const float sg = a.sign > 0 ? 1.0f : -1.0f;
-    const float inv = (float)(1.0 / (double)M);
-    const __amdgpu_buffer_rsrc_t twr = rot_rsrc(a.tw_p2, 16u * TWE);
-    const auto tw = [&]() {
-        if constexpr (!C::TW_LDS) return TwGlobal<N>{twr};
-        else if constexpr (ST) return TwLdsSt<N>{tws32, tws64};
-        else return TwLds32<N>{tws32};
-    }();
-    if constexpr (C::TW_LDS) {
-        for (int i = threadIdx.x; i < TWE; i += TB * WPB) {
-            if constexpr (ST) {
-                tws64[i] = a.tw_p2[i];
-                if (i >= M) tws32[i - M] = rc2_of(a.tw_p2[i]);
-            } else {
-                tws32[i] = rc2_of(a.tw_p2[i]);
-            }
-        }
-        __syncthreads();
-    }
-    // every global load of a profile in flight at once: one memory latency
-    // per profile, not one per row (or per flag / fit lookup)
-    auto load_rows = [&](size_t k, float4 (&xr)[NJ]) {
-#pragma unroll
-        for (int u = 0; u < NJ; ++u) {
-            const int j2 = t + u * TB;
-            if ((M / 2) % TB == 0 || j2 < M / 2)
-            {
-                // non-temporal, as the direct layout's (C5 fft 58.8 -> 57.4-57.9 ms,
-                // C4 fft 3.90 -> 3.76 ms with the stores below)
-                const fv4 xv = __builtin_nontemporal_load((const fv4 *)(a.in + d_ofs(k, 4 * j2, (int)a.ld_in, a.in_tiled)));
-                xr[u] = make_float4(xv.x, xv.y, xv.z, xv.w);
-            }
-        }
-    };
-    // the profile is left out (uniform over the block): its subint's flag is 0,
-    // or its late flag is not the one selected
-    auto skip = [&](size_t p, unsigned s) {
-        return (a.flags && a.flags[s] == 0) || (a.late && ((a.late[p] != 0) != (a.late_sel != 0)));
-    };
-    // a block's profiles are consecutive items (channel-major): they share a
-    // channel's phasor row
-    // items: channel-major over every profile, or the profiles of a round list
-    // (RotateArgs.list: the diagnostics fork's second pass, the profiles still
-    // fitting at its round - a scan of every profile for their late flags cost
-    // that pass 2.7-3.4 ms per iteration on C2 for a tenth of the profiles)
-    const RoundList rl(a.list, a.nctr, (long)P);
-    const size_t nitems = a.list ? (size_t)rl.n() : P;
-    for (size_t item = (size_t)blockIdx.x * WPB + wv; item < nitems; item += (size_t)gridDim.x * WPB) {
-        unsigned c, s;
-        size_t p;
-        if (a.list) {
-            p = (size_t)rl.at((long)item);
-            c = (unsigned)(p % nchan);
-            s = (unsigned)(p / nchan);
-        } else {
-            c = (unsigned)(item / nsub);
-            s = (unsigned)(item % nsub);
-            p = (size_t)s * nchan + c;
-        }
-        if (skip(p, s)) continue;
-        // the channel's f32 phasor row (8 bytes per harmonic)
-        const __amdgpu_buffer_rsrc_t phr = rot_rsrc(PP ? (const void *)a.tw : (const void *)(a.ph + 2 * (size_t)c * (M + 1)),
-                                                    8u * (M + 1));
-        const double dly = PP ? a.delay2[p] : 0.0;
-        // PP, N >= 256 (M a multiple of 64): the lane's harmonics k = t + u TB
-        // and M - k have the low parts lo1 = t mod 64 and lo2 = -t mod 64 in
-        // every round, and high parts that are the same across the wave: w0 + u
-        // TB for k, and M - 64 - w0 - u TB for M - k (M - w0 - u TB where lo1 =
-        // 0), w0 = t - lo1.  So a lane evaluates P0(lo1), P0(lo2) and one of
-        // the wave's 3 NK high parts (lane j), and every round reads its high
-        // parts from lanes u, NK + u, 2 NK + u (ic_phasor's product form: 3
-        // polynomials per lane instead of 2 NK)
-        constexpr bool PPX = PP && N >= 256;
-        const int lo1 = t & 63, w0 = t - lo1;
-        double2 A1{}, A2{}, Bh{};
-        if constexpr (PPX) {
-            const int lo2 = (64 - lo1) & 63, j = lo1;
-            int hv = j < NK ? w0 + j * TB : (j < 2 * NK ? M - 64 - w0 - (j - NK) * TB : M - w0 - (j - 2 * NK) * TB);
-            if (j >= 3 * NK || hv < 0) hv = 0;
-            A1 = ic_phasor0(lo1, dly, N);
-            A2 = ic_phasor0(lo2, dly, N);
-            Bh = ic_phasor0(hv, dly, N);
-        }
-        auto bcast = [&](int lane) {
-            return make_double2(__hiloint2double(__builtin_amdgcn_readlane(__double2hiint(Bh.x), lane),
-                                                 __builtin_amdgcn_readlane(__double2loint(Bh.x), lane)),
-                                __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(Bh.y), lane),
-                                                 __builtin_amdgcn_readlane(__double2loint(Bh.y), lane)));
-        };
-        // the post step's phasors one round ahead: the first round's are
-        // requested with the rows, each later round's before the round before it
-        // RM (N >= 256): the last round would hold k = H alone, in lane 0.  Lane
-        // 0 takes it in round 0 instead of the DC / Nyquist bins, which it
-        // finishes after the rounds: no round with one active lane and no
-        // divergent branch in round 0 (the schedule only: the same operations).
-        // Per-channel C2 46.8 -> 46.4 ms (f64 rotation); with per-profile
-        // delays it spilled in f64 (48.1 -> 48.6), in f32 it gains (39.8 -> 39.6)
-        constexpr bool RM = H % TB == 0;
-        constexpr int NR = RM ? NK - 1 : NK;
-        auto kof = [&](int u) { return (RM && u == 0 && t == 0) ? H : t + u * TB; };
-        // the phasors (f64, ic_phasor) rounded to f32 at the use; the table's are f32
-        auto ldph = [&](int u, rc2 (&pp)[2]) {
-            const int k = kof(u);
-            if constexpr (PPX) {
-                const double2 b1 = bcast(u), b2 = bcast(NK + u), b3 = bcast(2 * NK + u);
-                if (k <= H) {
-                    pp[0] = rc2_of(lo1 == 0 ? b1 : (w0 + u * TB == 0 ? A1 : ic_phasor_mul(A1, b1)));
-                    pp[1] = rc2_of(lo1 == 0 ? b3 : (M - 64 - w0 - u * TB == 0 ? A2 : ic_phasor_mul(A2, b2)));
-                }
-                if (RM && u == 0) {   // lane 0's k = H: P0(H) from the round NK - 1 parts
-                    const double2 bh = bcast(NK - 1), bh3 = bcast(3 * NK - 1);
-                    if (t == 0) {
-                        pp[0] = rc2_of(bh);
-                        pp[1] = rc2_of(bh3);
-                    }
-                }
-            } else if (k <= H) {
-                if constexpr (PP) {
-                    pp[0] = rc2_of(ic_phasor(k, dly, N));
-                    pp[1] = rc2_of(ic_phasor(M - k, dly, N));
-                } else {
-                    pp[0] = rot_ld2(phr, 8u * (unsigned)k, 0);
-                    pp[1] = rot_ld2(phr, 8u * (unsigned)(M - k), 0);
-                }
-            }
-        };
-        rc2 phn[2];
-        ldph(0, phn);
-        rc2 z[8];
-        static_assert(!ST || DIRECT, "the statistics epilogue needs the direct layout");
-        float wst = 1.0f;   // ST: the profile's weight, requested with the rows
-        if constexpr (ST) wst = a.w0[p];
-        if constexpr (DIRECT) {
-            const size_t k = p;
-            float2 x2[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-            {
-                // read once per rotation (non-temporal: C2 fft 39.25-39.42 -> 39.05-39.25 ms)
-                const rc2 xv =
-                    __builtin_nontemporal_load((const rc2 *)(a.in + d_ofs(k, 2 * (t + TB * q), (int)a.ld_in, a.in_tiled)));
-                x2[q] = make_float2(xv.x, xv.y);
-            }
-            if (a.amp) {
-                const __amdgpu_buffer_rsrc_t t64r = rot_rsrc(a.T64, 16u * M);
-                double2 tt[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) tt[q] = rot_ld(t64r, 16u * (unsigned)t, 16u * (unsigned)(TB * q));
-                const int st = a.info[p];
-                const bool ok = st >= 1 && st <= 4;
-                const double am = a.amp[p];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float r[2] = {0.0f, 0.0f};
-                    if (ok) {
-                        const float pv[2] = {x2[q].x, x2[q].y};
-                        const double tv[2] = {tt[q].x, tt[q].y};
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) {
-                            const int i = 2 * (t + TB * q) + e;
-                            const double uu = am * tv[e];
-                            double d = uu - (double)pv[e];
-                            if (a.pr_on && i >= a.pr_start && i < a.pr_end) d = d * a.pr_factor;
-                            r[e] = (float)d;
-                        }
-                    }
-                    z[q] = (rc2){r[0], r[1]};
-                }
-            } else {
-                const float b = a.base ? a.base[p] : 0.0f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) z[q] = (rc2){x2[q].x, x2[q].y} - (rc2){b, b};
-            }
-            rot_fft<N, 0, true, false>(v, tw, t, z);
-        } else {
-        float4 xin[NJ];
-        load_rows(p, xin);
-        if (a.amp) {
-            // the residual of the exact fit (k_residual's arithmetic), formed on the fly;
-            // the template is requested with the rows, before the status is known
-            // (behind the scattered amp / info loads it was a second latency)
-            const __amdgpu_buffer_rsrc_t t64r = rot_rsrc(a.T64, 16u * M);
-            double2 tt[NJ][2];
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j2 = t + u * TB;
-                if ((M / 2) % TB != 0 && j2 >= M / 2) break;
-                tt[u][0] = rot_ld(t64r, 32u * (unsigned)t, 32u * (unsigned)(u * TB));
-                tt[u][1] = rot_ld(t64r, 32u * (unsigned)t, 32u * (unsigned)(u * TB) + 16u);
-            }
-            const int st = a.info[p];
-            const bool ok = st >= 1 && st <= 4;
-            const double am = a.amp[p];
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j2 = t + u * TB;
-                if ((M / 2) % TB != 0 && j2 >= M / 2) break;
-                float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (ok) {
-                    const float pv[4] = {xin[u].x, xin[u].y, xin[u].z, xin[u].w};
-                    const double tv[4] = {tt[u][0].x, tt[u][0].y, tt[u][1].x, tt[u][1].y};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * j2 + e;
-                        const double uu = am * tv[e];
-                        double d = uu - (double)pv[e];
-                        if (a.pr_on && i >= a.pr_start && i < a.pr_end) d = d * a.pr_factor;
-                        r[e] = (float)d;
-                    }
-                }
-                v[rsl(2 * j2)] = (rc2){r[0], r[1]};
-                v[rsl(2 * j2 + 1)] = (rc2){r[2], r[3]};
-            }
-        } else {
-            const float b = a.base ? a.base[p] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j2 = t + u * TB;
-                if ((M / 2) % TB != 0 && j2 >= M / 2) break;
-                v[rsl(2 * j2)] = (rc2){xin[u].x, xin[u].y} - (rc2){b, b};
-                v[rsl(2 * j2 + 1)] = (rc2){xin[u].z, xin[u].w} - (rc2){b, b};
-            }
-        }
-        gsync<TB / 64>();
-        rot_fft<N>(v, tw, t);
-        }
-        // the post step's twiddles, at their use
-        // Re P(M) for the DC / Nyquist step after the rounds (RM); P(0) = (1, 0)
-        // exactly for every delay, so Y_0 = X_0 * 1 = X_0
-        float pmr = 0.0f;
-        if constexpr (RM) {
-            if constexpr (PPX) pmr = (float)bcast(2 * NK).x;   // P0(M), lane 2 NK of the wave's high parts
-            else pmr = rot_ld2(phr, 8u * (unsigned)M, 0).x;
-        }
-        const rc2 sgv = {1.0f, sg};
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            const int k = kof(u);
-            const rc2 wk = k <= H ? tw.post((unsigned)(k & (M - 1))) : (rc2){0.0f, 0.0f};
-            const rc2 pk = phn[0], pq = phn[1];
-            if (u + 1 < NR) ldph(u + 1, phn);
-            if (k <= H) {
-                if (!RM && k == 0) {
-                    const rc2 z0 = v[rsl(0)];
-                    const float X0 = z0.x + z0.y, XM = z0.x - z0.y;
-                    const float Y0 = X0 * pk.x, YM = XM * pq.x;
-                    v[rsl(0)] = (rc2){(Y0 + YM) * 0.5f, -((Y0 - YM) * 0.5f)};
-                } else {
-                    const int q = M - k;
-                    const rc2 zk = v[rsl(k)], zq = v[rsl(q)];
-                    rc2 Zk, Zq;   // conjugated
-                    rot_pair(zk, zq, wk, pk * sgv, pq * sgv, Zk, Zq);
-                    v[rsl(q)] = Zq;
-                    v[rsl(k)] = Zk;
-                }
-            }
-        }
-        if constexpr (RM) {
-            if (t == 0) {   // DC and Nyquist: X_0 = Z_0.r + Z_0.i, X_M = Z_0.r - Z_0.i
-                const rc2 z0 = v[rsl(0)];
-                const float X0 = z0.x + z0.y, XM = z0.x - z0.y;
-                const float Y0 = X0, YM = XM * pmr;
-                v[rsl(0)] = (rc2){(Y0 + YM) * 0.5f, -((Y0 - YM) * 0.5f)};
-            }
-        }
-        gsync<TB / 64>();
-        float *o = a.out + p * (size_t)a.ldo;
-        const rc2 scl = {inv, -inv};   // (r.re / M, -r.im / M): x (-1/M) = -(x) (1/M)
-        if constexpr (ST) {
-            rot_fft<N, 0, false, true>(v, tw, t, z);
-            rot_stats<N>(a, p, (double2 *)v, tws64, t, z, inv, wst);
-        } else if constexpr (DIRECT) {
-            rot_fft<N, 0, false, true>(v, tw, t, z);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int j = t + TB * q;
-                // written once, read by later kernels: non-temporal stores
-                // (C2 fft 39.71-39.95 -> 39.43-39.53 ms; only out2's: 39.56-39.75)
-                const rc2 yv = z[q] * scl;
-                __builtin_nontemporal_store(yv, (rc2 *)(o + 2 * j));
-                if (a.out2) __builtin_nontemporal_store(yv, (rc2 *)(a.out2 + d_ofs(p, 2 * j, (int)a.ldo2, a.out2_tiled)));
-            }
-        } else {
-            rot_fft<N>(v, tw, t);
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j2 = t + u * TB;
-                if ((M / 2) % TB != 0 && j2 >= M / 2) break;
-                const rc2 r0 = v[rsl(2 * j2)] * scl, r1 = v[rsl(2 * j2 + 1)] * scl;
-                const float4 y = make_float4(r0.x, r0.y, r1.x, r1.y);
-                const fv4 yv = {y.x, y.y, y.z, y.w};
-                __builtin_nontemporal_store(yv, (fv4 *)(o + 4 * j2));
-                if (a.out2) __builtin_nontemporal_store(yv, (fv4 *)(a.out2 + d_ofs(p, 4 * j2, (int)a.ldo2, a.out2_tiled)));
-            }
-        }
-        gsync<TB / 64>();   // v is reused by the block's next profile
-    }
-}
-
-// ---------------------------------------------------------------------------
-// k_rotate_mr: the same rotation for the mixed-radix lengths (mr_supported:
-// N = 2M, M = 2^a 3^b 5^c, N a multiple of 8, 64 .. 4096), N a runtime value.
-// One wave per profile, blockDim.x / 64 waves per block; a wave's M complex
-// points ping-pong between two LDS buffers (8 N bytes per wave), one Stockham
-// stage per trip, and the block shares the f32 twiddle table (tw[q], q < N: 8 N
-// bytes, staged once per block).  The host factors M (mr_plan: the stage order
-// of phase_rotation.py stage_radices) and passes the radices as 4-bit fields;
-// the kernel switches per stage to the radix-templated body.  Every complex
-// operation is the packed f32 arithmetic of k_rotate (each half one IEEE f32
-// operation of the definition), rows move as 16-byte accesses and every global
-// load of a profile is issued before the first stage.  NJ: float4 rows per lane
-// (N <= 256 NJ).  PP: per-profile delays (RotateArgs.delay2).
-// DFT_3 / DFT_5 in the written order of phase_rotation.py (_dft3, _dft5)
-__device__ __forceinline__ void rot_dft3(rc2 *b)
-{
-    constexpr float s3 = (float)0x1.bb67ae8584caap-1;   // f32(f64(sqrt(3)/2))
-    const rc2 t = b[1] + b[2], d = b[1] - b[2];
-    const rc2 m = b[0] - t * (rc2){0.5f, 0.5f};
-    const rc2 e = d * (rc2){s3, s3};
-    b[0] = b[0] + t;
-    b[1] = pk_mi(m, e);   // m - i e
-    b[2] = pk_pi(m, e);   // m + i e
-}
-__device__ __forceinline__ void rot_dft5(rc2 *b)
-{
-    constexpr float c1 = (float)0x1.3c6ef372fe950p-2;    // f32(f64(cos(2 pi/5)))
-    constexpr float c2 = (float)-0x1.9e3779b97f4a8p-1;   // f32(f64(cos(4 pi/5)))
-    constexpr float s1 = (float)0x1.e6f0e134454ffp-1;    // f32(f64(sin(2 pi/5)))
-    constexpr float s2 = (float)0x1.2cf2304755a5ep-1;    // f32(f64(sin(4 pi/5)))
-    const rc2 t1 = b[1] + b[4], t2 = b[2] + b[3], d1 = b[1] - b[4], d2 = b[2] - b[3];
-    const rc2 m1 = (b[0] + t1 * (rc2){c1, c1}) + t2 * (rc2){c2, c2};
-    const rc2 m2 = (b[0] + t1 * (rc2){c2, c2}) + t2 * (rc2){c1, c1};
-    const rc2 e1 = d1 * (rc2){s1, s1} + d2 * (rc2){s2, s2};
-    const rc2 e2 = d1 * (rc2){s2, s2} - d2 * (rc2){s1, s1};
-    b[0] = b[0] + (t1 + t2);
-    b[1] = pk_mi(m1, e1);
-    b[2] = pk_mi(m2, e2);
-    b[3] = pk_pi(m2, e2);
-    b[4] = pk_pi(m1, e1);
-}
-
-// One stage of radix R and span ns (the product of the earlier radices) of the
-// wave's FFT_M: butterfly j < G = M/R reads in[j + q G], multiplies by
-// tw[q k step] (k = j mod ns, step = N/(R ns); not in the first stage), and
-// writes DFT_R's y_p to out[(j - k) R + k + p ns].  magic = ceil(2^32 / ns):
-// j / ns = (j magic) >> 32 exactly for j, ns < 2^16.
-template <int R>
-__device__ __forceinline__ void mr_stage(const rc2 *in, rc2 *out, const rc2 *tw, int M, int step, int ns, int lane)
-{
-    const int G = M / R;
-    const unsigned magic = ns > 1 ? 0xffffffffu / (unsigned)ns + 1u : 0u;
-    for (int j = lane; j < G; j += 64) {
-        const int k = ns > 1 ? j - (int)__umulhi((unsigned)j, magic) * ns : 0;
-        rc2 u[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) u[q] = in[j + q * G];
-        if (ns > 1) {
-            rc2 w[R];
-#pragma unroll
-            for (int q = 1; q < R; ++q) w[q] = tw[q * k * step];
-#pragma unroll
-            for (int q = 1; q < R; ++q) u[q] = rot_cmul(u[q], w[q]);
-        }
-        if constexpr (R == 8) {
-            rot_dft8(u);
-        } else if constexpr (R == 5) {
-            rot_dft5(u);
-        } else if constexpr (R == 4) {
-            rot_dft4(u);
-        } else if constexpr (R == 3) {
-            rot_dft3(u);
-        } else {
-            const rc2 a = u[0], b = u[1];
-            u[0] = a + b;
-            u[1] = a - b;
-        }
-        rc2 *o = out + (j - k) * R + k;
-#pragma unroll
-        for (int p = 0; p < R; ++p) o[p * ns] = u[p];
-    }
-}
-
-// FFT_M of the wave's points in `a` (stages ping-pong between a and b);
-// returns the buffer that holds the result
-__device__ __forceinline__ rc2 *mr_fft(rc2 *a, rc2 *b, const rc2 *tw, int M, int N, unsigned long long radices,
-                                       int nst, int lane)
-{
-    int ns = 1, step = N;
-    for (int s = 0; s < nst; ++s) {
-        const int R = (int)((radices >> (4 * s)) & 15);
-        step /= R;
-        switch (R) {
-        case 8: mr_stage<8>(a, b, tw, M, step, ns, lane); break;
-        case 5: mr_stage<5>(a, b, tw, M, step, ns, lane); break;
-        case 4: mr_stage<4>(a, b, tw, M, step, ns, lane); break;
-        case 3: mr_stage<3>(a, b, tw, M, step, ns, lane); break;
-        default: mr_stage<2>(a, b, tw, M, step, ns, lane); break;
-        }
-        ns *= R;
-        rc2 *t = a;
-        a = b;
-        b = t;
-        wave_sync();
-    }
-    return a;
-}
-
-template <int NJ, bool PP>
-__global__ __launch_bounds__(256) void k_rotate_mr(RotateArgs a, unsigned long long radices, int nst)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char mr_sm[];
-    const int N = a.nbin, M = N >> 1, H = M >> 1, NQ = N >> 2;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    rc2 *tws = (rc2 *)mr_sm;                      // [N] f32 of tw
-    rc2 *v0 = tws + N + (size_t)wv * 2 * M;       // the wave's two buffers of M points
-    rc2 *v1 = v0 + M;
-    for (int i = threadIdx.x; i < N; i += blockDim.x) tws[i] = rc2_of(a.tw[i]);
-    __syncthreads();
-    const unsigned nsub = (unsigned)a.nsub, nchan = (unsigned)a.nchan;
-    const size_t P = (size_t)nsub * nchan;
-    const rc2 sgv = {1.0f, a.sign > 0 ? 1.0f : -1.0f};
-    const float inv = (float)(1.0 / (double)M);
-    const rc2 scl = {inv, -inv};   // (r.re / M, -r.im / M): x (-1/M) = -(x) (1/M)
-    const RoundList rl(a.list, a.nctr, (long)P);
-    const size_t nitems = a.list ? (size_t)rl.n() : P;
-    // items as k_rotate's: channel-major over every profile, or a round list
-    for (size_t item = (size_t)blockIdx.x * wpb + wv; item < nitems; item += (size_t)gridDim.x * wpb) {
-        unsigned c, s;
-        size_t p;
-        if (a.list) {
-            p = (size_t)rl.at((long)item);
-            c = (unsigned)(p % nchan);
-            s = (unsigned)(p / nchan);
-        } else {
-            c = (unsigned)(item / nsub);
-            s = (unsigned)(item % nsub);
-            p = (size_t)s * nchan + c;
-        }
-        if ((a.flags && a.flags[s] == 0) || (a.late && ((a.late[p] != 0) != (a.late_sel != 0)))) continue;
-        // every global load of the profile in flight at once
-        fv4 xin[NJ];
-#pragma unroll
-        for (int u = 0; u < NJ; ++u) {
-            const int j4 = lane + 64 * u;
-            if (j4 < NQ)
-                xin[u] = __builtin_nontemporal_load((const fv4 *)(a.in + d_ofs(p, 4 * j4, (int)a.ld_in, a.in_tiled)));
-        }
-        // PP: the profile's phasor parts (ic_phasor's product form): lane l holds
-        // the low part P0(l) and the high part P0(64 l) (64 l <= M), evaluated
-        // once per profile
-        double2 Alo{}, Bhi{};
-        const float *phc = nullptr;
-        if constexpr (PP) {
-            const double dly = a.delay2[p];
-            Alo = ic_phasor0(lane, dly, N);
-            Bhi = ic_phasor0(64 * lane <= M ? 64 * lane : 0, dly, N);
-        } else {
-            phc = a.ph + 2 * (size_t)c * (M + 1);
-        }
-        // f32(ic_phasor(k, delay, N)), k <= M; every lane of the wave calls it together
-        auto phasor = [&](int k) {
-            if constexpr (PP) {
-                const int lo = k & 63, hi = k >> 6;
-                const double2 A = make_double2(__shfl(Alo.x, lo), __shfl(Alo.y, lo));
-                const double2 B = make_double2(__shfl(Bhi.x, hi), __shfl(Bhi.y, hi));
-                return rc2_of(lo == 0 ? B : (hi == 0 ? A : ic_phasor_mul(A, B)));
-            } else {
-                return *(const rc2 *)(phc + 2 * k);
-            }
-        };
-        if (a.amp) {
-            // the residual of the exact fit (k_residual's arithmetic), formed on the fly
-            const int st = a.info[p];
-            const bool ok = st >= 1 && st <= 4;
-            const double am = a.amp[p];
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j4 = lane + 64 * u;
-                if (j4 >= NQ) break;
-                float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (ok) {
-                    const double2 ta = *(const double2 *)(a.T64 + 4 * j4), tb = *(const double2 *)(a.T64 + 4 * j4 + 2);
-                    const float pv[4] = {xin[u].x, xin[u].y, xin[u].z, xin[u].w};
-                    const double tv[4] = {ta.x, ta.y, tb.x, tb.y};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * j4 + e;
-                        const double uu = am * tv[e];
-                        double d = uu - (double)pv[e];
-                        if (a.pr_on && i >= a.pr_start && i < a.pr_end) d = d * a.pr_factor;
-                        r[e] = (float)d;
-                    }
-                }
-                *(fv4 *)(v0 + 2 * j4) = (fv4){r[0], r[1], r[2], r[3]};
-            }
-        } else {
-            const float b = a.base ? a.base[p] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < NJ; ++u) {
-                const int j4 = lane + 64 * u;
-                if (j4 >= NQ) break;
-                *(fv4 *)(v0 + 2 * j4) = xin[u] - (fv4){b, b, b, b};
-            }
-        }
-        wave_sync();
-        rc2 *z = mr_fft(v0, v1, tws, M, N, radices, nst, lane);
-        // pairs (k, M - k), k = 1 .. H, in place; lane 0's first slot is the DC /
-        // Nyquist step.  Uniform trip count: the shuffles of phasor() need every lane
-        for (int k0 = 0; k0 <= H; k0 += 64) {
-            const int k = k0 + lane, kc = k <= H ? k : H;
-            const rc2 pk = phasor(kc), pq = phasor(M - kc);
-            if (k == 0) {
-                const rc2 z0 = z[0];
-                const float X0 = z0.x + z0.y, XM = z0.x - z0.y;
-                const float Y0 = X0 * pk.x, YM = XM * pq.x;
-                z[0] = (rc2){(Y0 + YM) * 0.5f, -((Y0 - YM) * 0.5f)};
-            } else if (k <= H) {
-                const int q = M - k;
-                rc2 Zk, Zq;   // conjugated
-                rot_pair(z[k], z[q], tws[k], pk * sgv, pq * sgv, Zk, Zq);
-                z[q] = Zq;
-                z[k] = Zk;   // k = M/2 pairs with itself: the k values are stored last
-            }
-        }
-        wave_sync();
-        rc2 *r = mr_fft(z, z == v0 ? v1 : v0, tws, M, N, radices, nst, lane);
-        float *o = a.out + p * (size_t)a.ldo;
-#pragma unroll
-        for (int u = 0; u < NJ; ++u) {
-            const int j4 = lane + 64 * u;
-            if (j4 >= NQ) break;
-            const rc2 r0 = r[2 * j4] * scl, r1 = r[2 * j4 + 1] * scl;
-            const fv4 yv = {r0.x, r0.y, r1.x, r1.y};
-            __builtin_nontemporal_store(yv, (fv4 *)(o + 4 * j4));
-            if (a.out2) __builtin_nontemporal_store(yv, (fv4 *)(a.out2 + d_ofs(p, 4 * j4, (int)a.ldo2, a.out2_tiled)));
-        }
-        wave_sync();   // the buffers are reused by the wave's next profile
     }
 }
 
@@ -4854,722 +3279,7 @@ __global__ __launch_bounds__(64) void k_tnorm(const double *__restrict__ T64, co
     if (lane == 0) *TT = v;
 }
 
-// ============================================================ medians
-
-__device__ __forceinline__ unsigned long long key64(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unkey64(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
-// ---- per-line median / MAD: one wave per line, radix select ------------------
-// Lines: columns (length nsub) of each diagnostic, or rows (length nchan);
-// diag 0 std, 1 mean, 2 ptp (f32 arithmetic), 3 fft (plain: every entry valid).
-// The valid values of the line go to wave-private LDS as order-preserving
-// 64-bit keys (key64), compacted with a ballot.  Order statistics come from a
-// most-significant-digit radix select: 8-bit digits from the highest bit where min and max differ,
-// a 256-bin LDS histogram per digit, the target bin found by a DPP prefix scan.
-// Once the chosen bin holds a single key, one compare-only scan returns it.
-// numpy.ma median arithmetic: odd -> 0+mid, even -> ((0+lo)+hi)/2 in the
-// dtype; any NaN -> NaN.
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    return wave_tree<64>(v, OpAdd());
-}
-
-// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-// r-th smallest (0-based) of keys[0, n): uniform result
-__device__ unsigned long long wave_select(const unsigned long long *keys, int n, int r, unsigned *hist, int lane)
-{
-    unsigned long long lo = ~0ull, hi = 0ull;
-    for (int j = lane; j < n; j += 64) {
-        const unsigned long long k = keys[j];
-        lo = k < lo ? k : lo;
-        hi = k > hi ? k : hi;
-    }
-    lo = wave_min_u64(lo);
-    hi = wave_max_u64(hi);
-    if (lo == hi) return lo;
-    const int top = 63 - __clzll((long long)(lo ^ hi));
-    int shift = (top / 8) * 8;
-    unsigned long long prefix = shift + 8 >= 64 ? 0ull : (lo & (~0ull << (shift + 8)));
-    for (; shift >= 0; shift -= 8) {
-        const unsigned long long hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) hist[lane * 4 + q] = 0u;
-        wave_sync();
-        for (int j = lane; j < n; j += 64) {
-            const unsigned long long k = keys[j];
-            if ((k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-        }
-        wave_sync();
-        const uint4 c4 = *(const uint4 *)&hist[lane * 4];
-        const int sl = (int)(c4.x + c4.y + c4.z + c4.w);
-        const int incl = wave_incl_scan(sl);
-        const unsigned long long over = __ballot(incl > r);
-        const int L = __ffsll((long long)over) - 1;   // lane holding the target bin
-        int below = __shfl(incl - sl, L);
-        const uint4 cl = *(const uint4 *)&hist[L * 4];
-        int bin = L * 4;
-        unsigned cb = cl.x;   // keys in the chosen bin
-        if (r - below >= (int)cl.x) {
-            below += cl.x;
-            ++bin;
-            cb = cl.y;
-            if (r - below >= (int)cl.y) {
-                below += cl.y;
-                ++bin;
-                cb = cl.z;
-                if (r - below >= (int)cl.z) {
-                    below += cl.z;
-                    ++bin;
-                    cb = cl.w;
-                }
-            }
-        }
-        r -= below;
-        prefix |= (unsigned long long)bin << shift;
-        if (cb == 1u && shift > 0) {   // a single key holds the prefix: one compare-only scan
-            // one key left under the prefix: it is the answer, found in one
-            // compare-only scan instead of the remaining digit passes
-            const unsigned long long m = ~0ull << shift;
-            unsigned long long f = 0ull;
-            for (int j = lane; j < n; j += 64) {
-                const unsigned long long k = keys[j];
-                if ((k & m) == prefix) f = k;
-            }
-            return wave_max_u64(f);
-        }
-        wave_sync();
-    }
-    return prefix;
-}
-
-// median of keys[0, n) (n > 0, no NaN), dtype arithmetic
-__device__ double wave_median(const unsigned long long *keys, int n, bool f32, unsigned *hist, int lane)
-{
-    const int idx = n / 2;
-    if (n % 2) {
-        const double m = unkey64(wave_select(keys, n, idx, hist, lane));
-        return f32 ? (double)(0.0f + (float)m) : 0.0 + m;
-    }
-    const unsigned long long klo = wave_select(keys, n, idx - 1, hist, lane);
-    // hi = rank idx: klo again if it is repeated, else the next larger key
-    int le = 0;
-    unsigned long long nxt = ~0ull;
-    for (int j = lane; j < n; j += 64) {
-        const unsigned long long k = keys[j];
-        le += k <= klo;
-        if (k > klo && k < nxt) nxt = k;
-    }
-    le = wave_sum_i(le);
-    nxt = wave_min_u64(nxt);
-    const unsigned long long khi = le > idx ? klo : nxt;
-    const double lo = unkey64(klo), hi = unkey64(khi);
-    if (f32) {
-        const float t = (0.0f + (float)lo) + (float)hi;
-        return (double)(t / 2.0f);
-    }
-    const double t = (0.0 + lo) + hi;
-    return t / 2.0;
-}
-
-__global__ __launch_bounds__(256) void k_linestats(LineStatsArgs a, int rows, int len, int wpb, int per_wave)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int line = blockIdx.x * wpb + wave;
-    const int nl = 4 * (rows ? a.nsub : a.nchan);
-    if (line >= nl || wave >= wpb) return;
-    unsigned *hist = (unsigned *)(lsm + (size_t)wave * per_wave);
-    unsigned long long *keys = (unsigned long long *)(lsm + (size_t)wave * per_wave + 1024);
-    const int nline = rows ? a.nsub : a.nchan;
-    const int diag = line / nline, idx = line % nline;
-    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
-    // gather the valid values (ballot compaction keeps no particular order: the
-    // selection does not need one)
-    int cnt = 0, nan = 0;
-    for (int q0 = 0; q0 < len; q0 += 64) {
-        const int q = q0 + lane;
-        double d = 0.0;
-        bool v = false;
-        if (q < len) {
-            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
-            v = plain ? true : (a.valid[kk] != 0);
-            d = diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
-        }
-        const unsigned long long m = __ballot(v);
-        if (v) keys[cnt + __popcll(m & ((1ull << lane) - 1ull))] = key64(d);
-        nan |= v && isnan(d);
-        cnt += __popcll(m);
-    }
-    nan = __any(nan);
-    wave_sync();
-    double med = NAN, mad = NAN;
-    if (cnt > 0 && !nan) {
-        med = wave_median(keys, cnt, f32, hist, lane);
-        // |d - med| in the dtype, in place
-        int rnan = 0;
-        for (int j = lane; j < cnt; j += 64) {
-            const double d = unkey64(keys[j]);
-            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
-            rnan |= isnan(r);
-            keys[j] = key64(r);
-        }
-        rnan = __any(rnan);
-        wave_sync();
-        if (!rnan) mad = wave_median(keys, cnt, f32, hist, lane);
-    }
-    if (lane == 0) {
-        if (!rows) {
-            a.col_med[diag * a.nchan + idx] = med;
-            a.col_mad[diag * a.nchan + idx] = mad;
-        } else {
-            a.row_med[diag * a.nsub + idx] = med;
-            a.row_mad[diag * a.nsub + idx] = mad;
-        }
-    }
-}
-
-// ---- long lines: W waves per line -------------------------------------------
-// The rows (length nchan, a few thousand) are too few for one wave each to fill
-// the chip (4*nsub waves), and early radix digits put most keys of a wave in
-// one bin, so the LDS atomics serialise.  Here a block of W waves owns a line:
-// wave w gathers its own slice of the line into its own key segment, the 256
-// bins are shared by the block, and min/max/count/NaN flags are block
-// reductions.  Order statistics do not depend on where a key sits, so the
-// result is the one k_linestats computes.
-
-template <int W> struct GrpRed {
-    unsigned long long *s;   // 2*W slots
-    int wave, lane;
-    __device__ unsigned long long min_u64(unsigned long long v)
-    {
-        v = wave_min_u64(v);
-        if (lane == 0) s[wave] = v;
-        __syncthreads();
-        unsigned long long r = s[0];
-#pragma unroll
-        for (int i = 1; i < W; ++i) r = s[i] < r ? s[i] : r;
-        __syncthreads();
-        return r;
-    }
-    __device__ unsigned long long max_u64(unsigned long long v)
-    {
-        v = wave_max_u64(v);
-        if (lane == 0) s[wave] = v;
-        __syncthreads();
-        unsigned long long r = s[0];
-#pragma unroll
-        for (int i = 1; i < W; ++i) r = s[i] > r ? s[i] : r;
-        __syncthreads();
-        return r;
-    }
-    // min and max in one round trip
-    __device__ void minmax_u64(unsigned long long &lo, unsigned long long &hi)
-    {
-        lo = wave_min_u64(lo);
-        hi = wave_max_u64(hi);
-        if (lane == 0) {
-            s[wave] = lo;
-            s[W + wave] = hi;
-        }
-        __syncthreads();
-        lo = s[0];
-        hi = s[W];
-#pragma unroll
-        for (int i = 1; i < W; ++i) {
-            lo = s[i] < lo ? s[i] : lo;
-            hi = s[W + i] > hi ? s[W + i] : hi;
-        }
-        __syncthreads();
-    }
-    __device__ int sum_i(int v) { return sum_uniform(wave_sum_i(v)); }
-    // v already uniform across the wave
-    __device__ int sum_uniform(int v)
-    {
-        if (lane == 0) s[wave] = (unsigned long long)(unsigned)v;
-        __syncthreads();
-        int r = 0;
-#pragma unroll
-        for (int i = 0; i < W; ++i) r += (int)(unsigned)s[i];
-        __syncthreads();
-        return r;
-    }
-};
-
-// r-th smallest (0-based) over every wave's segment keys[0, n): uniform result
-template <int W>
-__device__ unsigned long long grp_select(GrpRed<W> &g, const unsigned long long *keys, int n, int r, unsigned *hist)
-{
-    const int lane = g.lane;
-    unsigned long long lo = ~0ull, hi = 0ull;
-    for (int j = lane; j < n; j += 64) {
-        const unsigned long long k = keys[j];
-        lo = k < lo ? k : lo;
-        hi = k > hi ? k : hi;
-    }
-    g.minmax_u64(lo, hi);
-    if (lo == hi) return lo;
-    const int top = 63 - __clzll((long long)(lo ^ hi));
-    int shift = (top / 8) * 8;
-    unsigned long long prefix = shift + 8 >= 64 ? 0ull : (lo & (~0ull << (shift + 8)));
-    for (; shift >= 0; shift -= 8) {
-        const unsigned long long hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
-        for (int t = threadIdx.x; t < 256; t += 64 * W) hist[t] = 0u;
-        __syncthreads();
-        for (int j = lane; j < n; j += 64) {
-            const unsigned long long k = keys[j];
-            if ((k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const uint4 c4 = *(const uint4 *)&hist[lane * 4];
-        const int sl = (int)(c4.x + c4.y + c4.z + c4.w);
-        const int incl = wave_incl_scan(sl);
-        const unsigned long long over = __ballot(incl > r);
-        const int L = __ffsll((long long)over) - 1;
-        int below = __shfl(incl - sl, L);
-        const uint4 cl = *(const uint4 *)&hist[L * 4];
-        int bin = L * 4;
-        unsigned cb = cl.x;   // keys in the chosen bin
-        if (r - below >= (int)cl.x) {
-            below += cl.x;
-            ++bin;
-            cb = cl.y;
-            if (r - below >= (int)cl.y) {
-                below += cl.y;
-                ++bin;
-                cb = cl.z;
-                if (r - below >= (int)cl.z) {
-                    below += cl.z;
-                    ++bin;
-                    cb = cl.w;
-                }
-            }
-        }
-        r -= below;
-        prefix |= (unsigned long long)bin << shift;
-        if (cb == 1u && shift > 0) {   // uniform: every wave read the same bins
-            const unsigned long long m = ~0ull << shift;
-            unsigned long long f = 0ull;
-            for (int j = lane; j < n; j += 64) {
-                const unsigned long long k = keys[j];
-                if ((k & m) == prefix) f = k;
-            }
-            return g.max_u64(f);   // its barriers also order the bin reads before any re-zeroing
-        }
-        __syncthreads();   // every wave has read the bins before the next zeroing
-    }
-    return prefix;
-}
-
-// median over the block's keys (ntot > 0 in total, no NaN), dtype arithmetic
-template <int W>
-__device__ double grp_median(GrpRed<W> &g, const unsigned long long *keys, int n, int ntot, bool f32, unsigned *hist)
-{
-    const int idx = ntot / 2;
-    if (ntot % 2) {
-        const double m = unkey64(grp_select<W>(g, keys, n, idx, hist));
-        return f32 ? (double)(0.0f + (float)m) : 0.0 + m;
-    }
-    const unsigned long long klo = grp_select<W>(g, keys, n, idx - 1, hist);
-    int le = 0;
-    unsigned long long nxt = ~0ull;
-    for (int j = g.lane; j < n; j += 64) {
-        const unsigned long long k = keys[j];
-        le += k <= klo;
-        if (k > klo && k < nxt) nxt = k;
-    }
-    le = g.sum_i(le);
-    nxt = g.min_u64(nxt);
-    const unsigned long long khi = le > idx ? klo : nxt;
-    const double lo = unkey64(klo), hi = unkey64(khi);
-    if (f32) {
-        const float t = (0.0f + (float)lo) + (float)hi;
-        return (double)(t / 2.0f);
-    }
-    const double t = (0.0 + lo) + hi;
-    return t / 2.0;
-}
-
-// one block of W waves per line; LDS: 256 bins, 2*W reduction slots, len keys
-template <int W> __global__ __launch_bounds__(64 * W) void k_linestats_grp(LineStatsArgs a, int rows, int len)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    unsigned *hist = (unsigned *)lsm;
-    GrpRed<W> g{(unsigned long long *)(lsm + 1024), wave, lane};
-    const int nline = rows ? a.nsub : a.nchan;
-    const int line = blockIdx.x;
-    const int diag = line / nline, idx = line % nline;
-    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
-    const int seg = (((len + W - 1) / W) + 63) & ~63;
-    const int q0w = wave * seg, q1w = min(len, q0w + seg);
-    unsigned long long *keys = (unsigned long long *)(lsm + 1024 + 16 * W) + q0w;
-    int cnt = 0, nan = 0;
-    for (int q0 = q0w; q0 < q1w; q0 += 64) {
-        const int q = q0 + lane;
-        double d = 0.0;
-        bool v = false;
-        if (q < q1w) {
-            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
-            v = plain ? true : (a.valid[kk] != 0);
-            d = diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
-        }
-        const unsigned long long m = __ballot(v);
-        if (v) keys[cnt + __popcll(m & ((1ull << lane) - 1ull))] = key64(d);
-        nan |= v && isnan(d);
-        cnt += __popcll(m);
-    }
-    nan = g.sum_uniform(__any(nan) ? 1 : 0);   // the barrier also publishes the keys
-    const int ntot = g.sum_uniform(cnt);
-    double med = NAN, mad = NAN;
-    if (ntot > 0 && !nan) {
-        med = grp_median<W>(g, keys, cnt, ntot, f32, hist);
-        int rnan = 0;
-        for (int j = lane; j < cnt; j += 64) {
-            const double d = unkey64(keys[j]);
-            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
-            rnan |= isnan(r);
-            keys[j] = key64(r);
-        }
-        rnan = g.sum_uniform(__any(rnan) ? 1 : 0);
-        if (!rnan) mad = grp_median<W>(g, keys, cnt, ntot, f32, hist);
-    }
-    if (threadIdx.x == 0) {
-        if (!rows) {
-            a.col_med[diag * a.nchan + idx] = med;
-            a.col_mad[diag * a.nchan + idx] = mad;
-        } else {
-            a.row_med[diag * a.nsub + idx] = med;
-            a.row_mad[diag * a.nsub + idx] = mad;
-        }
-    }
-}
-
-// ============================================================ combine
-
-__device__ __forceinline__ double scale_masked_d(double dv, bool valid, double med, double mad, double thr)
-{
-    if (!valid) return 0.0 + fabs(dv);
-    const double r = dv - med;
-    const double q = r / mad;
-    const bool dom = !isfinite(q) || (fabs(r) * DBL_MIN >= fabs(mad));
-    if (dom) return 0.0 + fabs(0.0 + r);
-    const double aq = fabs(q);
-    const double res = aq / thr;
-    if (!isfinite(res) || aq * DBL_MIN >= fabs(thr)) return 0.0 + aq;
-    return res;
-}
-
-__device__ __forceinline__ double scale_masked_f(float dv, bool valid, float med, float mad, double thr)
-{
-    if (!valid) return 0.0 + (double)fabsf(dv);
-    const float r = dv - med;
-    const float q = r / mad;
-    const bool dom = !isfinite(q) || ((double)fabsf(r) * DBL_MIN >= (double)fabsf(mad));
-    if (dom) return 0.0 + (double)fabsf(0.0f + r);
-    const float aq = fabsf(q);
-    const double res = (double)aq / thr;
-    if (!isfinite(res) || (double)aq * DBL_MIN >= fabs(thr)) return 0.0 + (double)aq;
-    return res;
-}
-
-__device__ __forceinline__ double scale_plain(double dv, double med, double mad, double thr)
-{
-    const double r = dv - med;
-    const double q = r / mad;
-    return fabs(q) / thr;
-}
-
-__device__ __forceinline__ double nanmax2(double a, double b)
-{
-    if (isnan(a) || isnan(b)) return NAN;
-    return a > b ? a : b;
-}
-
-// |test - 1| at or below this counts as a near tie (the fftmax tolerance of
-// the parity tests, DESIGN.md "Numerical semantics")
-constexpr double kNearTie = 1e-9;
-
-// counters: [0] changed vs hist[iter-1], [1] zero weights, [2] profiles whose
-// fit status is not 1-4 (info may be null: 0), [3] profiles whose test value
-// lies within kNearTie of the zap threshold 1.0 (where the last bits of fftmax,
-// not bit-identical to pocketfft, could decide), [4+h] != hist[h]
-
-__global__ __launch_bounds__(256) void k_combine(
-    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
-    const float *__restrict__ w0,
-    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
-    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
-    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
-    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
-    int32_t *__restrict__ counters)
-{
-    // grid-stride; the convergence counters are reduced per block (one atomic
-    // per counter per block: same-address atomics serialise at the memory side)
-    __shared__ int red[4][4];
-    __shared__ unsigned long long dred[4];
-    const size_t P = (size_t)nsub * nchan;
-    int changed = 0, zero = 0, bad = 0, near = 0;
-    unsigned long long diff = 0ull;   // bit h: W != hist[h] somewhere (h < 64)
-    const int hmax = iter < 64 ? iter : 64;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < P; k += (size_t)gridDim.x * blockDim.x) {
-        const int s = (int)(k / nchan), c = (int)(k % nchan);
-        const bool v = valid[k] != 0;
-        double S[4];
-        S[0] = nanmax2(scale_masked_d(std_d[k], v, col_med[c], col_mad[c], cth),
-                       scale_masked_d(std_d[k], v, row_med[s], row_mad[s], sth));
-        S[1] = nanmax2(scale_masked_d(mean_d[k], v, col_med[nchan + c], col_mad[nchan + c], cth),
-                       scale_masked_d(mean_d[k], v, row_med[nsub + s], row_mad[nsub + s], sth));
-        // ptp: numpy.ma in f32 for f32 data (Appendix A.5), f64 for f64 data
-        S[2] = ptp_f32 ? nanmax2(scale_masked_f((float)ptp_d[k], v, (float)col_med[2 * nchan + c],
-                                                (float)col_mad[2 * nchan + c], cth),
-                                 scale_masked_f((float)ptp_d[k], v, (float)row_med[2 * nsub + s],
-                                                (float)row_mad[2 * nsub + s], sth))
-                       : nanmax2(scale_masked_d(ptp_d[k], v, col_med[2 * nchan + c], col_mad[2 * nchan + c], cth),
-                                 scale_masked_d(ptp_d[k], v, row_med[2 * nsub + s], row_mad[2 * nsub + s], sth));
-        S[3] = nanmax2(scale_plain(fft_d[k], col_med[3 * nchan + c], col_mad[3 * nchan + c], cth),
-                       scale_plain(fft_d[k], row_med[3 * nsub + s], row_mad[3 * nsub + s], sth));
-        double t;
-        if (isnan(S[0]) || isnan(S[1]) || isnan(S[2]) || isnan(S[3])) {
-            t = NAN;
-        } else {
-            // sort 4
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3 - a; ++b)
-                    if (S[b] > S[b + 1]) {
-                        const double tmp = S[b];
-                        S[b] = S[b + 1];
-                        S[b + 1] = tmp;
-                    }
-            t = ((0.0 + S[1]) + S[2]) / 2.0;
-        }
-        test[k] = t;
-        near += fabs(t - 1.0) <= kNearTie;   // false for NaN
-        const float wn = (t >= 1.0) ? 0.0f : w0[k];
-        W[k] = wn;
-        hist[(size_t)iter * P + k] = wn;
-        changed += !(wn == hist[(size_t)(iter - 1) * P + k]);
-        zero += (wn == 0.0f);
-        if (info) {   // "Bad status for least squares fit" (iterative_cleaner.py:284-285)
-            const int st = info[k];
-            bad += (st < 1 || st > 4);
-        }
-        // history equality (iterative_cleaner.py:135-136)
-        for (int h = 0; h < hmax; ++h)
-            if (!(wn == hist[(size_t)h * P + k])) diff |= 1ull << h;
-        for (int h = 64; h < iter; ++h)
-            if (!(wn == hist[(size_t)h * P + k])) atomicOr(&counters[4 + h], 1);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        changed += __shfl_xor(changed, off);
-        zero += __shfl_xor(zero, off);
-        bad += __shfl_xor(bad, off);
-        near += __shfl_xor(near, off);
-        diff |= __shfl_xor(diff, off);
-    }
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = changed;
-        red[1][wave] = zero;
-        red[2][wave] = bad;
-        red[3][wave] = near;
-        dred[wave] = diff;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int ch = 0, ze = 0, bd = 0, nt = 0;
-        unsigned long long df = 0ull;
-        for (int w = 0; w < nw; ++w) {
-            ch += red[0][w];
-            ze += red[1][w];
-            bd += red[2][w];
-            nt += red[3][w];
-            df |= dred[w];
-        }
-        // counters[0..1] (changed, zero) as one u64 add: both < 2^32, no carry
-        if (ch || ze)
-            atomicAdd((unsigned long long *)counters, ((unsigned long long)(unsigned)ze << 32) | (unsigned)ch);
-        if (bd) atomicAdd(&counters[2], bd);
-        if (nt) atomicAdd(&counters[3], nt);
-        for (int h = 0; h < hmax; ++h)
-            if ((df >> h) & 1ull) atomicOr(&counters[4 + h], 1);
-    }
-}
-
-// ============================================================ shard exchanges
-
-// owner rank of subint row s / channel c (world <= 64: linear scan)
-__device__ __forceinline__ int geom_row_owner(const ShardGeom &g, int s)
-{
-    int r = 0;
-    while (r + 1 < g.world && s >= g.row0[r + 1]) ++r;
-    return r;
-}
-__device__ __forceinline__ int geom_chan_owner(const ShardGeom &g, int c)
-{
-    int r = 0;
-    while (r + 1 < g.world && c >= g.chan0[r + 1]) ++r;
-    return r;
-}
-
-// Send blocks to row owners.  Destination d receives, for its rows
-// [row0[d], row0[d+1]) x my nchan_loc channels, the fields back to back:
-// std, mean, fft (f64), ptp (f32)  — or, in valid mode, valid (u8).
-// Blocks are padded to 8 bytes (shard_block_bytes); d's block starts after
-// the blocks of d' < d.
-__global__ __launch_bounds__(256) void k_pack_rows(ShardGeom g, int nchan_loc, const double *__restrict__ std_d,
-                                                   const double *__restrict__ mean_d, const double *__restrict__ fft_d,
-                                                   const double *__restrict__ ptp_d, const uint8_t *__restrict__ valid,
-                                                   unsigned char *__restrict__ send)
-{
-    const size_t P = (size_t)g.nsub * nchan_loc;
-    const size_t esz = valid ? 1 : 32;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < P; k += (size_t)gridDim.x * blockDim.x) {
-        const int s = (int)(k / nchan_loc);
-        const int d = geom_row_owner(g, s);
-        const size_t n_d = (size_t)(g.row0[d + 1] - g.row0[d]) * nchan_loc;   // elements in d's block
-        const size_t e = k - (size_t)g.row0[d] * nchan_loc;                   // element within it
-        size_t off = 0;
-        for (int q = 0; q < d; ++q) off += shard_block_bytes((size_t)(g.row0[q + 1] - g.row0[q]) * nchan_loc, esz);
-        unsigned char *blk = send + off;
-        if (valid) {
-            blk[e] = valid[k];
-        } else {
-            ((double *)blk)[e] = std_d[k];
-            ((double *)blk)[n_d + e] = mean_d[k];
-            ((double *)blk)[2 * n_d + e] = fft_d[k];
-            ((double *)blk)[3 * n_d + e] = ptp_d[k];
-        }
-    }
-}
-
-// Owned rows from the per-source blocks (source p sent rows_own x nchan_p
-// elements per field, after the padded blocks of sources p' < p).
-__global__ __launch_bounds__(256) void k_assemble_rows(ShardGeom g, const unsigned char *__restrict__ recv,
-                                                       double *__restrict__ std_r, double *__restrict__ mean_r,
-                                                       double *__restrict__ fft_r, double *__restrict__ ptp_r,
-                                                       uint8_t *__restrict__ valid_r)
-{
-    const int rows = g.row0[g.rank + 1] - g.row0[g.rank];
-    const size_t n = (size_t)rows * g.nchan_g;
-    const size_t esz = valid_r ? 1 : 32;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
-        const int r = (int)(k / g.nchan_g), c = (int)(k % g.nchan_g);
-        const int p = geom_chan_owner(g, c);
-        const int np = g.chan0[p + 1] - g.chan0[p];
-        const size_t n_p = (size_t)rows * np;
-        const size_t e = (size_t)r * np + (c - g.chan0[p]);
-        size_t off = 0;
-        for (int q = 0; q < p; ++q) off += shard_block_bytes((size_t)rows * (g.chan0[q + 1] - g.chan0[q]), esz);
-        const unsigned char *blk = recv + off;
-        if (valid_r) {
-            valid_r[k] = blk[e];
-        } else {
-            std_r[k] = ((const double *)blk)[e];
-            mean_r[k] = ((const double *)blk)[n_p + e];
-            fft_r[k] = ((const double *)blk)[2 * n_p + e];
-            ptp_r[k] = ((const double *)blk)[3 * n_p + e];
-        }
-    }
-}
-
-// gathered row statistics: rank p's slot (8 * rows_pad doubles) holds med
-// [4][rows_p] then mad [4][rows_p] of its rows_p owned rows
-__global__ __launch_bounds__(256) void k_unpack_rowstats(ShardGeom g, int rows_pad, const double *__restrict__ recv,
-                                                         double *__restrict__ row_med, double *__restrict__ row_mad)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;   // q * nsub + s
-    if (k >= 4 * g.nsub) return;
-    const int q = k / g.nsub, s = k % g.nsub;
-    const int p = geom_row_owner(g, s);
-    const int rows_p = g.row0[p + 1] - g.row0[p];
-    const int r = s - g.row0[p];
-    const double *slot = recv + (size_t)p * 8 * rows_pad;
-    row_med[k] = slot[q * rows_p + r];
-    row_mad[k] = slot[4 * rows_p + q * rows_p + r];
-}
-
-// Window positions gathered from the row owners (blocks of `blk` ints per
-// rank) -> win[nsub] on every rank; flags (optional): moved per subint and the
-// moves counter flags[nsub], as k_window does unsharded.
-__global__ __launch_bounds__(256) void k_unpack_windows(ShardGeom g, int blk, const int32_t *__restrict__ recv,
-                                                        int32_t *__restrict__ win, int32_t *__restrict__ flags)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= g.nsub) return;
-    const int p = geom_row_owner(g, s);
-    const int w = recv[(size_t)p * blk + (s - g.row0[p])];
-    if (flags) {
-        const int moved = win[s] != w;
-        flags[s] = moved;
-        if (moved) atomicAdd(&flags[g.nsub], 1);
-    }
-    win[s] = w;
-}
-
-// fscrunch rows gathered from the row owners: rank p's block (blk floats) holds
-// F rows [rows_pad][nbin] then wf [rows_pad] -> F[nsub][nbin], wf[nsub]
-__global__ __launch_bounds__(256) void k_unpack_fscrunch(ShardGeom g, int rows_pad, long blk, int nbin,
-                                                         const float *__restrict__ recv, float *__restrict__ F,
-                                                         float *__restrict__ wf)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = blockIdx.y;
-    if (i >= nbin) return;
-    const int p = geom_row_owner(g, s);
-    const float *b = recv + (size_t)p * blk;
-    const int t = s - g.row0[p];
-    F[(size_t)s * nbin + i] = b[(size_t)t * nbin + i];
-    if (i == 0) wf[s] = b[(size_t)rows_pad * nbin + t];
-}
-
-__global__ void k_sum_i32(const int32_t *__restrict__ gathered, int world, int n, int32_t *__restrict__ buf)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int32_t a = 0;
-    for (int r = 0; r < world; ++r) a += gathered[(size_t)r * n + i];
-    buf[i] = a;
-}
-
 // ============================================================ launchers
-
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 hipError_t launch_chan_partials(hipStream_t st, int mode, const float *raw, const float *W, const int32_t *shift,
                                 const float *base, const int32_t *flags, int nsub, int nchan, int nbin,
@@ -5577,7 +3287,7 @@ hipError_t launch_chan_partials(hipStream_t st, int mode, const float *raw, cons
                                 uint8_t *exA, uint8_t *exF)
 {
     const int nsb = (nchan + kSuperBlock - 1) / kSuperBlock;
-    const int bs = nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64;
+    const int bs = bin_block(nbin);
     dim3 grid(cdiv(nbin, bs), nsb, nsub);
     if (mode == 3 && (!D || ldD < nbin || (dtiled && ldD % 32 != 0))) return hipErrorInvalidValue;
 #define IC_CP(M)                                                                                                  \
@@ -5728,7 +3438,7 @@ hipError_t launch_fscrunch(hipStream_t st, const double *part, long ss, long sl,
                            long wsl, const SbPlan &plan, int nsub, int nbin, float *F, float *wf)
 {
     if (plan.n < 1 || plan.n > kMaxSbLeaves) return hipErrorInvalidValue;
-    const int bs = nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64;
+    const int bs = bin_block(nbin);
     IC_GGL(k_fscrunch, dim3(cdiv(nbin, bs), nsub), dim3(bs), 0, st, part, ss, sl, wpart, wss, wsl, plan,
                        nbin, F, wf);
     return hipGetLastError();
@@ -5739,59 +3449,8 @@ hipError_t launch_sb_tree(hipStream_t st, const double *part, const double *wpar
 {
     if (plan.n < 1 || plan.n > kMaxSbLeaves) return hipErrorInvalidValue;
     if (ostr < nbin + (wpart ? 1 : 0)) return hipErrorInvalidValue;
-    const int bs = nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64;
+    const int bs = bin_block(nbin);
     IC_GGL(k_sb_tree, dim3(cdiv(nbin, bs), nsub), dim3(bs), 0, st, part, wpart, plan, nbin, ostr, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpack_windows(hipStream_t st, const ShardGeom &g, int blk, const int32_t *recv, int32_t *win,
-                                 int32_t *flags)
-{
-    IC_GGL(k_unpack_windows, dim3(cdiv(g.nsub, 256)), dim3(256), 0, st, g, blk, recv, win, flags);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpack_fscrunch(hipStream_t st, const ShardGeom &g, int rows_pad, long blk, int nbin,
-                                  const float *recv, float *F, float *wf)
-{
-    const int bs = nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64;
-    IC_GGL(k_unpack_fscrunch, dim3(cdiv(nbin, bs), g.nsub), dim3(bs), 0, st, g, rows_pad, blk, nbin,
-                       recv, F, wf);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_rows(hipStream_t st, const ShardGeom &g, int nchan_loc, const double *std_d,
-                            const double *mean_d, const double *fft_d, const double *ptp_d, const uint8_t *valid,
-                            unsigned char *send, int grid_cap)
-{
-    const size_t P = (size_t)g.nsub * nchan_loc;
-    if (P == 0) return hipSuccess;
-    const unsigned grid = cap_grid(std::min<unsigned>(cdiv(P, 256), 4096), grid_cap);
-    IC_GGL(k_pack_rows, dim3(grid), dim3(256), 0, st, g, nchan_loc, std_d, mean_d, fft_d, ptp_d, valid, send);
-    return hipGetLastError();
-}
-
-hipError_t launch_assemble_rows(hipStream_t st, const ShardGeom &g, const unsigned char *recv, double *std_r,
-                                double *mean_r, double *fft_r, double *ptp_r, uint8_t *valid_r, int grid_cap)
-{
-    const size_t n = (size_t)(g.row0[g.rank + 1] - g.row0[g.rank]) * g.nchan_g;
-    if (n == 0) return hipSuccess;
-    const unsigned grid = cap_grid(std::min<unsigned>(cdiv(n, 256), 4096), grid_cap);
-    IC_GGL(k_assemble_rows, dim3(grid), dim3(256), 0, st, g, recv, std_r, mean_r, fft_r, ptp_r, valid_r);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpack_rowstats(hipStream_t st, const ShardGeom &g, int rows_pad, const double *recv,
-                                  double *row_med, double *row_mad)
-{
-    IC_GGL(k_unpack_rowstats, dim3(cdiv(4 * (size_t)g.nsub, 256)), dim3(256), 0, st, g, rows_pad, recv,
-                       row_med, row_mad);
-    return hipGetLastError();
-}
-
-hipError_t launch_sum_i32(hipStream_t st, const int32_t *gathered, int world, int n, int32_t *buf)
-{
-    IC_GGL(k_sum_i32, dim3(cdiv(n, 64)), dim3(64), 0, st, gathered, world, n, buf);
     return hipGetLastError();
 }
 
@@ -5802,6 +3461,9 @@ hipError_t launch_tscrunch(hipStream_t st, const float *F, const float *wf, int 
     return hipGetLastError();
 }
 
+// sweep length: nbin rounded up to whole tile pairs (sweep_dma)
+static int sweep_len(int nbin) { return ((nbin + 2 * FIT_TB - 1) / (2 * FIT_TB)) * (2 * FIT_TB); }
+
 hipError_t launch_fit_init(hipStream_t st, const FitStateArrays &S, long P, int32_t *z32, int nz32, uint8_t *late)
 {
     IC_GGL(k_fit_init, dim3(cdiv(max(P, (long)nz32), 256)), dim3(256), 0, st, S, P, z32, nz32, late);
@@ -5810,7 +3472,7 @@ hipError_t launch_fit_init(hipStream_t st, const FitStateArrays &S, long P, int3
 
 hipError_t launch_fit_prep(hipStream_t st, const FitStateArrays &S, const double *T64, int nbin)
 {
-    const int nsw = ((nbin + 2 * FIT_TB - 1) / (2 * FIT_TB)) * (2 * FIT_TB);
+    const int nsw = sweep_len(nbin);
     IC_GGL(k_fit_prep, dim3(1), dim3(256), sizeof(double) * nsw, st, T64, nbin, nsw, S.U);
     return hipGetLastError();
 }
@@ -5821,9 +3483,7 @@ hipError_t launch_fit_pass(hipStream_t st, const float *D, const double *T64, lo
 {
     const long n = list ? bound : P;
     if (n <= 0) return hipSuccess;
-    // sweep length: nbin rounded up to whole tile pairs (sweep_dma); the row
-    // stride ldD may be longer (padding off the power-of-two stride)
-    const int nsw = ((nbin + 2 * FIT_TB - 1) / (2 * FIT_TB)) * (2 * FIT_TB);
+    const int nsw = sweep_len(nbin);   // the row stride ldD may be longer (padding off the power-of-two stride)
     if (ldD % 4 != 0 || ldD < nsw || (dtiled && ldD % 32 != 0)) return hipErrorInvalidValue;
     if (round0 && list) return hipErrorInvalidValue;
     if (round0)
@@ -5979,62 +3639,6 @@ hipError_t launch_tnorm(hipStream_t st, const double *T64, const PwPlan *plan, i
     return hipGetLastError();
 }
 
-hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
-{
-    // columns (length nsub), then rows (length nchan); wave-private LDS:
-    // 256-bin histogram + the line's keys
-    for (int rows = 0; rows < 2; ++rows) {
-        if (!((which >> rows) & 1)) continue;
-        const int len = rows ? a.nchan : a.nsub;
-        const int lines = 4 * (rows ? a.nsub : a.nchan);
-        if (lines == 0 || len == 0) continue;
-        // few long lines (the rows): W waves per line (a.grp_waves = W in {0, 4, 8},
-        // 0 = one wave per line; a.grp_minlen = the shortest line it takes)
-        if (lines < 8192 && len >= a.grp_minlen) {
-            const int W = a.grp_waves;
-            if (W == 4 || W == 8) {
-                const int seg = (((len + W - 1) / W) + 63) & ~63;
-                const size_t gshm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8;
-                if (gshm <= 160 * 1024) {
-                    if (W == 4)
-                        IC_GGL(k_linestats_grp<4>, dim3(lines), dim3(256), gshm, st, a, rows, len);
-                    else
-                        IC_GGL(k_linestats_grp<8>, dim3(lines), dim3(512), gshm, st, a, rows, len);
-                    const hipError_t e = hipGetLastError();
-                    if (e != hipSuccess) return e;
-                    continue;
-                }
-            }
-        }
-        const int per_wave = 1024 + ((len * 8 + 15) / 16) * 16;
-        int wpb = 4;
-        while (wpb > 1 && (size_t)wpb * per_wave > 64 * 1024) --wpb;
-        const size_t shm = (size_t)wpb * per_wave;
-        if (shm > 160 * 1024) return hipErrorInvalidValue;
-        IC_GGL(k_linestats, dim3(cdiv(lines, wpb)), dim3(64 * wpb), shm, st, a, rows, len, wpb,
-                           per_wave);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                          const float *w0,
-                          const double *std_d, const double *mean_d, const double *ptp_d, int ptp_f32,
-                          const double *fft_d, const double *col_med, const double *col_mad,
-                          const double *row_med, const double *row_mad, double chanthresh,
-                          double subintthresh, double *test, float *W, float *hist, int iter,
-                          int32_t *counters, int grid_cap)
-{
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d,
-                       mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh,
-                       test, W, hist, iter, counters);
-    return hipGetLastError();
-}
-
 hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, const float *base, const double *T64,
                            const double *amp, const int32_t *info, const int32_t *shift, int nsub, int nchan,
                            int nbin, int ldD, int dtiled, int pr_on, double pr_factor, int pr_start, int pr_end,
@@ -6045,130 +3649,6 @@ hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, con
     const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 4), 16384), grid_cap);
     IC_GGL(k_residual, dim3(grid), dim3(256), 0, st, D, raw, base, T64, amp, info, shift, P, nchan, nbin,
                        ldD, dtiled, pr_on, pr_factor, pr_start, pr_end, R);
-    return hipGetLastError();
-}
-
-bool rotate_supported(int nbin) { return p2_supported(nbin) || mr_supported(nbin); }
-
-// the Stockham stages of FFT_{nbin/2} in the definition's order
-// (phase_rotation.py stage_radices): radix 8 while three or more power-of-two
-// levels remain, then 4 or 2, then the 3s, then the 5s; 4 bits per stage
-static int mr_plan(int nbin, unsigned long long *radices)
-{
-    int m = nbin / 2, lg = 0, nst = 0;
-    unsigned long long r = 0;
-    const auto push = [&](int R) {
-        if (nst < kMrMaxStages) r |= (unsigned long long)R << (4 * nst);
-        ++nst;
-    };
-    while (m % 2 == 0) {
-        m /= 2;
-        ++lg;
-    }
-    for (; lg >= 3; lg -= 3) push(8);
-    if (lg) push(1 << lg);
-    const int odd[2] = {3, 5};
-    for (const int f : odd)
-        while (m % f == 0) {
-            m /= f;
-            push(f);
-        }
-    *radices = r;
-    return m == 1 && nst <= kMrMaxStages ? nst : 0;
-}
-
-// k_rotate_mr: waves per block from the LDS it needs, 8 nbin bytes for the
-// block's f32 twiddle table and 8 nbin per wave, within kMrLdsBytes
-static hipError_t launch_rotate_mr(hipStream_t st, const RotateArgs &a, size_t P)
-{
-    unsigned long long radices = 0;
-    const int nst = mr_plan(a.nbin, &radices);
-    if (!nst) return hipErrorInvalidValue;
-    const size_t unit = 8 * (size_t)a.nbin;
-    const int wpb = (int)std::min<size_t>(4, kMrLdsBytes / unit - 1);
-    if (wpb < 1) return hipErrorInvalidValue;
-    const size_t shm = unit * (size_t)(1 + wpb);
-    const dim3 grid(cap_grid(std::min<size_t>(cdiv(P, wpb), 2048), a.grid_cap)), block(64 * wpb);
-    const int rows = (a.nbin / 4 + 63) / 64;   // float4 rows per lane
-#define IC_ROT_MR(NJ)                                                                              \
-    if (rows <= NJ) {                                                                              \
-        if (a.delay2) IC_GGL((k_rotate_mr<NJ, true>), grid, block, shm, st, a, radices, nst);      \
-        else IC_GGL((k_rotate_mr<NJ, false>), grid, block, shm, st, a, radices, nst);              \
-        return hipGetLastError();                                                                  \
-    }
-    IC_ROT_MR(4)
-    IC_ROT_MR(8)
-    IC_ROT_MR(16)
-#undef IC_ROT_MR
-    return hipErrorInvalidValue;
-}
-
-bool rotate_stats_supported(int nbin, bool data_f64) { return nbin == 1024 && !data_f64; }
-
-// The identity "rotation" of an archive stored dedispersed (its dedisperse is a
-// no-op, archive.py dedisperse): out[p] = f32(in[p] - base[p]) (and out2), for
-// the subints flags selects; a wave per profile, 16-byte rows.
-__global__ __launch_bounds__(256) void k_rotate_identity(RotateArgs a)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t P = (size_t)a.nsub * a.nchan;
-    for (size_t p = (size_t)blockIdx.x * 4 + wave; p < P; p += (size_t)gridDim.x * 4) {
-        if (a.flags && a.flags[p / (unsigned)a.nchan] == 0) continue;
-        const float b = a.base ? a.base[p] : 0.0f;
-        for (int j = 4 * lane; j < a.nbin; j += 256) {
-            const float4 x = *(const float4 *)(a.in + d_ofs(p, j, (int)a.ld_in, a.in_tiled));
-            const float4 y = make_float4(x.x - b, x.y - b, x.z - b, x.w - b);
-            *(float4 *)(a.out + p * (size_t)a.ldo + j) = y;
-            if (a.out2) *(float4 *)(a.out2 + d_ofs(p, j, (int)a.ldo2, a.out2_tiled)) = y;
-        }
-    }
-}
-
-hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
-{
-    const size_t P = (size_t)a.nsub * a.nchan;
-    if (P == 0) return hipSuccess;
-    const bool stats = a.std_o != nullptr;
-    if (stats && (!rotate_stats_supported(a.nbin, false) || !a.amp || a.sign > 0 || a.out2 || !a.w0 || !a.mean_o ||
-                  !a.ptp_o || !a.fft_o))
-        return hipErrorInvalidValue;
-    const bool mr = mr_supported(a.nbin);
-    if (!rotate_supported(a.nbin) || !a.in || (!a.out && !stats) || !a.tw || (!mr && !a.tw_p2) || a.ld_in < a.nbin ||
-        (!stats && a.ldo < a.nbin) ||
-        (!a.ph && !a.delay2 && !a.identity) ||
-        (a.ld_in & 3) || (a.ldo & 3) || (a.out2 && (a.ldo2 < a.nbin || (a.ldo2 & 3))) ||
-        (a.amp && (!a.T64 || !a.info)) || (a.in_tiled && (a.ld_in & 31)) || (a.out2_tiled && (a.ldo2 & 31)) ||
-        (a.identity && (a.amp || a.late || a.list)) || (a.list && !a.nctr))
-        return hipErrorInvalidValue;
-    if (a.identity) {
-        const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 4), 16384), a.grid_cap);
-        IC_GGL(k_rotate_identity, dim3(grid), dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    if (mr) return launch_rotate_mr(st, a, P);
-#define IC_ROT(NN)                                                                                 \
-    case NN:                                                                                       \
-        if (a.delay2)                                                                              \
-            IC_GGL((k_rotate<NN, true>),                                                           \
-                   dim3(cap_grid(std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB), a.grid_cap)), \
-                   dim3(RotCfg<NN>::TB * RotCfg<NN>::WPB), 0, st, a);                              \
-        else                                                                                       \
-            IC_GGL((k_rotate<NN, false>),                                                          \
-                   dim3(cap_grid(std::min<size_t>(cdiv(P, RotCfg<NN>::WPB), 16384 / RotCfg<NN>::WPB), a.grid_cap)), \
-                   dim3(RotCfg<NN>::TB * RotCfg<NN>::WPB), 0, st, a);                              \
-        break;
-    if (stats) {   // nbin 1024 (rotate_stats_supported)
-        const dim3 grid(cap_grid(std::min<size_t>(cdiv(P, RotCfg<1024>::WPB), 16384 / RotCfg<1024>::WPB), a.grid_cap));
-        const dim3 block(RotCfg<1024>::TB * RotCfg<1024>::WPB);
-        if (a.delay2) IC_GGL((k_rotate<1024, true, true>), grid, block, 0, st, a);
-        else IC_GGL((k_rotate<1024, false, true>), grid, block, 0, st, a);
-        return hipGetLastError();
-    }
-    switch (a.nbin) {
-        IC_P2_SIZES(IC_ROT)
-    default: return hipErrorInvalidValue;
-    }
-#undef IC_ROT
     return hipGetLastError();
 }
 

@@ -1,0 +1,648 @@
+// ic_linestats.hip -- per channel / subint median and MAD (ic.py:229-256) and
+// the combine step (ic.py:221-225, :303-305, :127-141), with their launchers.
+// The non-inlined wave_* / grp_* selection functions live here with all
+// their callers.
+#include <algorithm>
+#include <float.h>
+#include <math.h>
+
+#include "ic_wave.h"
+
+namespace icgpu {
+
+// ============================================================ medians
+
+__device__ __forceinline__ unsigned long long key64(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double unkey64(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+// ---- per-line median / MAD: one wave per line, radix select ------------------
+// Lines: columns (length nsub) of each diagnostic, or rows (length nchan);
+// diag 0 std, 1 mean, 2 ptp (f32 arithmetic), 3 fft (plain: every entry valid).
+// The valid values of the line go to wave-private LDS as order-preserving
+// 64-bit keys (key64), compacted with a ballot.  Order statistics come from a
+// most-significant-digit radix select: 8-bit digits from the highest bit where min and max differ,
+// a 256-bin LDS histogram per digit, the target bin found by a DPP prefix scan.
+// Once the chosen bin holds a single key, one compare-only scan returns it.
+// numpy.ma median arithmetic: odd -> 0+mid, even -> ((0+lo)+hi)/2 in the
+// dtype; any NaN -> NaN.
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v)
+{
+    return wave_tree<64>(v, OpAdd());
+}
+
+// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts)
+__device__ __forceinline__ int wave_incl_scan(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+    return v;
+}
+
+// r-th smallest (0-based) of keys[0, n): uniform result
+__device__ unsigned long long wave_select(const unsigned long long *keys, int n, int r, unsigned *hist, int lane)
+{
+    unsigned long long lo = ~0ull, hi = 0ull;
+    for (int j = lane; j < n; j += 64) {
+        const unsigned long long k = keys[j];
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    }
+    lo = wave_min_u64(lo);
+    hi = wave_max_u64(hi);
+    if (lo == hi) return lo;
+    const int top = 63 - __clzll((long long)(lo ^ hi));
+    int shift = (top / 8) * 8;
+    unsigned long long prefix = shift + 8 >= 64 ? 0ull : (lo & (~0ull << (shift + 8)));
+    for (; shift >= 0; shift -= 8) {
+        const unsigned long long hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) hist[lane * 4 + q] = 0u;
+        wave_sync();
+        for (int j = lane; j < n; j += 64) {
+            const unsigned long long k = keys[j];
+            if ((k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+        }
+        wave_sync();
+        const uint4 c4 = *(const uint4 *)&hist[lane * 4];
+        const int sl = (int)(c4.x + c4.y + c4.z + c4.w);
+        const int incl = wave_incl_scan(sl);
+        const unsigned long long over = __ballot(incl > r);
+        const int L = __ffsll((long long)over) - 1;   // lane holding the target bin
+        int below = __shfl(incl - sl, L);
+        const uint4 cl = *(const uint4 *)&hist[L * 4];
+        int bin = L * 4;
+        unsigned cb = cl.x;   // keys in the chosen bin
+        if (r - below >= (int)cl.x) {
+            below += cl.x;
+            ++bin;
+            cb = cl.y;
+            if (r - below >= (int)cl.y) {
+                below += cl.y;
+                ++bin;
+                cb = cl.z;
+                if (r - below >= (int)cl.z) {
+                    below += cl.z;
+                    ++bin;
+                    cb = cl.w;
+                }
+            }
+        }
+        r -= below;
+        prefix |= (unsigned long long)bin << shift;
+        if (cb == 1u && shift > 0) {   // a single key holds the prefix: one compare-only scan
+            // one key left under the prefix: it is the answer, found in one
+            // compare-only scan instead of the remaining digit passes
+            const unsigned long long m = ~0ull << shift;
+            unsigned long long f = 0ull;
+            for (int j = lane; j < n; j += 64) {
+                const unsigned long long k = keys[j];
+                if ((k & m) == prefix) f = k;
+            }
+            return wave_max_u64(f);
+        }
+        wave_sync();
+    }
+    return prefix;
+}
+
+// median of keys[0, n) (n > 0, no NaN), dtype arithmetic
+__device__ double wave_median(const unsigned long long *keys, int n, bool f32, unsigned *hist, int lane)
+{
+    const int idx = n / 2;
+    if (n % 2) {
+        const double m = unkey64(wave_select(keys, n, idx, hist, lane));
+        return f32 ? (double)(0.0f + (float)m) : 0.0 + m;
+    }
+    const unsigned long long klo = wave_select(keys, n, idx - 1, hist, lane);
+    // hi = rank idx: klo again if it is repeated, else the next larger key
+    int le = 0;
+    unsigned long long nxt = ~0ull;
+    for (int j = lane; j < n; j += 64) {
+        const unsigned long long k = keys[j];
+        le += k <= klo;
+        if (k > klo && k < nxt) nxt = k;
+    }
+    le = wave_sum_i(le);
+    nxt = wave_min_u64(nxt);
+    const unsigned long long khi = le > idx ? klo : nxt;
+    const double lo = unkey64(klo), hi = unkey64(khi);
+    if (f32) {
+        const float t = (0.0f + (float)lo) + (float)hi;
+        return (double)(t / 2.0f);
+    }
+    const double t = (0.0 + lo) + hi;
+    return t / 2.0;
+}
+
+__global__ __launch_bounds__(256) void k_linestats(LineStatsArgs a, int rows, int len, int wpb, int per_wave)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int line = blockIdx.x * wpb + wave;
+    const int nl = 4 * (rows ? a.nsub : a.nchan);
+    if (line >= nl || wave >= wpb) return;
+    unsigned *hist = (unsigned *)(lsm + (size_t)wave * per_wave);
+    unsigned long long *keys = (unsigned long long *)(lsm + (size_t)wave * per_wave + 1024);
+    const int nline = rows ? a.nsub : a.nchan;
+    const int diag = line / nline, idx = line % nline;
+    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
+    // gather the valid values (ballot compaction keeps no particular order: the
+    // selection does not need one)
+    int cnt = 0, nan = 0;
+    for (int q0 = 0; q0 < len; q0 += 64) {
+        const int q = q0 + lane;
+        double d = 0.0;
+        bool v = false;
+        if (q < len) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            d = diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
+        }
+        const unsigned long long m = __ballot(v);
+        if (v) keys[cnt + __popcll(m & ((1ull << lane) - 1ull))] = key64(d);
+        nan |= v && isnan(d);
+        cnt += __popcll(m);
+    }
+    nan = __any(nan);
+    wave_sync();
+    double med = NAN, mad = NAN;
+    if (cnt > 0 && !nan) {
+        med = wave_median(keys, cnt, f32, hist, lane);
+        // |d - med| in the dtype, in place
+        int rnan = 0;
+        for (int j = lane; j < cnt; j += 64) {
+            const double d = unkey64(keys[j]);
+            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
+            rnan |= isnan(r);
+            keys[j] = key64(r);
+        }
+        rnan = __any(rnan);
+        wave_sync();
+        if (!rnan) mad = wave_median(keys, cnt, f32, hist, lane);
+    }
+    if (lane == 0) {
+        if (!rows) {
+            a.col_med[diag * a.nchan + idx] = med;
+            a.col_mad[diag * a.nchan + idx] = mad;
+        } else {
+            a.row_med[diag * a.nsub + idx] = med;
+            a.row_mad[diag * a.nsub + idx] = mad;
+        }
+    }
+}
+
+// ---- long lines: W waves per line -------------------------------------------
+// The rows (length nchan, a few thousand) are too few for one wave each to fill
+// the chip (4*nsub waves), and early radix digits put most keys of a wave in
+// one bin, so the LDS atomics serialise.  Here a block of W waves owns a line:
+// wave w gathers its own slice of the line into its own key segment, the 256
+// bins are shared by the block, and min/max/count/NaN flags are block
+// reductions.  Order statistics do not depend on where a key sits, so the
+// result is the one k_linestats computes.
+
+template <int W> struct GrpRed {
+    unsigned long long *s;   // 2*W slots
+    int wave, lane;
+    __device__ unsigned long long min_u64(unsigned long long v)
+    {
+        v = wave_min_u64(v);
+        if (lane == 0) s[wave] = v;
+        __syncthreads();
+        unsigned long long r = s[0];
+#pragma unroll
+        for (int i = 1; i < W; ++i) r = s[i] < r ? s[i] : r;
+        __syncthreads();
+        return r;
+    }
+    __device__ unsigned long long max_u64(unsigned long long v)
+    {
+        v = wave_max_u64(v);
+        if (lane == 0) s[wave] = v;
+        __syncthreads();
+        unsigned long long r = s[0];
+#pragma unroll
+        for (int i = 1; i < W; ++i) r = s[i] > r ? s[i] : r;
+        __syncthreads();
+        return r;
+    }
+    // min and max in one round trip
+    __device__ void minmax_u64(unsigned long long &lo, unsigned long long &hi)
+    {
+        lo = wave_min_u64(lo);
+        hi = wave_max_u64(hi);
+        if (lane == 0) {
+            s[wave] = lo;
+            s[W + wave] = hi;
+        }
+        __syncthreads();
+        lo = s[0];
+        hi = s[W];
+#pragma unroll
+        for (int i = 1; i < W; ++i) {
+            lo = s[i] < lo ? s[i] : lo;
+            hi = s[W + i] > hi ? s[W + i] : hi;
+        }
+        __syncthreads();
+    }
+    __device__ int sum_i(int v) { return sum_uniform(wave_sum_i(v)); }
+    // v already uniform across the wave
+    __device__ int sum_uniform(int v)
+    {
+        if (lane == 0) s[wave] = (unsigned long long)(unsigned)v;
+        __syncthreads();
+        int r = 0;
+#pragma unroll
+        for (int i = 0; i < W; ++i) r += (int)(unsigned)s[i];
+        __syncthreads();
+        return r;
+    }
+};
+
+// r-th smallest (0-based) over every wave's segment keys[0, n): uniform result
+template <int W>
+__device__ unsigned long long grp_select(GrpRed<W> &g, const unsigned long long *keys, int n, int r, unsigned *hist)
+{
+    const int lane = g.lane;
+    unsigned long long lo = ~0ull, hi = 0ull;
+    for (int j = lane; j < n; j += 64) {
+        const unsigned long long k = keys[j];
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    }
+    g.minmax_u64(lo, hi);
+    if (lo == hi) return lo;
+    const int top = 63 - __clzll((long long)(lo ^ hi));
+    int shift = (top / 8) * 8;
+    unsigned long long prefix = shift + 8 >= 64 ? 0ull : (lo & (~0ull << (shift + 8)));
+    for (; shift >= 0; shift -= 8) {
+        const unsigned long long hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
+        for (int t = threadIdx.x; t < 256; t += 64 * W) hist[t] = 0u;
+        __syncthreads();
+        for (int j = lane; j < n; j += 64) {
+            const unsigned long long k = keys[j];
+            if ((k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const uint4 c4 = *(const uint4 *)&hist[lane * 4];
+        const int sl = (int)(c4.x + c4.y + c4.z + c4.w);
+        const int incl = wave_incl_scan(sl);
+        const unsigned long long over = __ballot(incl > r);
+        const int L = __ffsll((long long)over) - 1;
+        int below = __shfl(incl - sl, L);
+        const uint4 cl = *(const uint4 *)&hist[L * 4];
+        int bin = L * 4;
+        unsigned cb = cl.x;   // keys in the chosen bin
+        if (r - below >= (int)cl.x) {
+            below += cl.x;
+            ++bin;
+            cb = cl.y;
+            if (r - below >= (int)cl.y) {
+                below += cl.y;
+                ++bin;
+                cb = cl.z;
+                if (r - below >= (int)cl.z) {
+                    below += cl.z;
+                    ++bin;
+                    cb = cl.w;
+                }
+            }
+        }
+        r -= below;
+        prefix |= (unsigned long long)bin << shift;
+        if (cb == 1u && shift > 0) {   // uniform: every wave read the same bins
+            const unsigned long long m = ~0ull << shift;
+            unsigned long long f = 0ull;
+            for (int j = lane; j < n; j += 64) {
+                const unsigned long long k = keys[j];
+                if ((k & m) == prefix) f = k;
+            }
+            return g.max_u64(f);   // its barriers also order the bin reads before any re-zeroing
+        }
+        __syncthreads();   // every wave has read the bins before the next zeroing
+    }
+    return prefix;
+}
+
+// median over the block's keys (ntot > 0 in total, no NaN), dtype arithmetic
+template <int W>
+__device__ double grp_median(GrpRed<W> &g, const unsigned long long *keys, int n, int ntot, bool f32, unsigned *hist)
+{
+    const int idx = ntot / 2;
+    if (ntot % 2) {
+        const double m = unkey64(grp_select<W>(g, keys, n, idx, hist));
+        return f32 ? (double)(0.0f + (float)m) : 0.0 + m;
+    }
+    const unsigned long long klo = grp_select<W>(g, keys, n, idx - 1, hist);
+    int le = 0;
+    unsigned long long nxt = ~0ull;
+    for (int j = g.lane; j < n; j += 64) {
+        const unsigned long long k = keys[j];
+        le += k <= klo;
+        if (k > klo && k < nxt) nxt = k;
+    }
+    le = g.sum_i(le);
+    nxt = g.min_u64(nxt);
+    const unsigned long long khi = le > idx ? klo : nxt;
+    const double lo = unkey64(klo), hi = unkey64(khi);
+    if (f32) {
+        const float t = (0.0f + (float)lo) + (float)hi;
+        return (double)(t / 2.0f);
+    }
+    const double t = (0.0 + lo) + hi;
+    return t / 2.0;
+}
+
+// one block of W waves per line; LDS: 256 bins, 2*W reduction slots, len keys
+template <int W> __global__ __launch_bounds__(64 * W) void k_linestats_grp(LineStatsArgs a, int rows, int len)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned *hist = (unsigned *)lsm;
+    GrpRed<W> g{(unsigned long long *)(lsm + 1024), wave, lane};
+    const int nline = rows ? a.nsub : a.nchan;
+    const int line = blockIdx.x;
+    const int diag = line / nline, idx = line % nline;
+    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
+    const int seg = (((len + W - 1) / W) + 63) & ~63;
+    const int q0w = wave * seg, q1w = min(len, q0w + seg);
+    unsigned long long *keys = (unsigned long long *)(lsm + 1024 + 16 * W) + q0w;
+    int cnt = 0, nan = 0;
+    for (int q0 = q0w; q0 < q1w; q0 += 64) {
+        const int q = q0 + lane;
+        double d = 0.0;
+        bool v = false;
+        if (q < q1w) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            d = diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
+        }
+        const unsigned long long m = __ballot(v);
+        if (v) keys[cnt + __popcll(m & ((1ull << lane) - 1ull))] = key64(d);
+        nan |= v && isnan(d);
+        cnt += __popcll(m);
+    }
+    nan = g.sum_uniform(__any(nan) ? 1 : 0);   // the barrier also publishes the keys
+    const int ntot = g.sum_uniform(cnt);
+    double med = NAN, mad = NAN;
+    if (ntot > 0 && !nan) {
+        med = grp_median<W>(g, keys, cnt, ntot, f32, hist);
+        int rnan = 0;
+        for (int j = lane; j < cnt; j += 64) {
+            const double d = unkey64(keys[j]);
+            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
+            rnan |= isnan(r);
+            keys[j] = key64(r);
+        }
+        rnan = g.sum_uniform(__any(rnan) ? 1 : 0);
+        if (!rnan) mad = grp_median<W>(g, keys, cnt, ntot, f32, hist);
+    }
+    if (threadIdx.x == 0) {
+        if (!rows) {
+            a.col_med[diag * a.nchan + idx] = med;
+            a.col_mad[diag * a.nchan + idx] = mad;
+        } else {
+            a.row_med[diag * a.nsub + idx] = med;
+            a.row_mad[diag * a.nsub + idx] = mad;
+        }
+    }
+}
+
+// ============================================================ combine
+
+__device__ __forceinline__ double scale_masked_d(double dv, bool valid, double med, double mad, double thr)
+{
+    if (!valid) return 0.0 + fabs(dv);
+    const double r = dv - med;
+    const double q = r / mad;
+    const bool dom = !isfinite(q) || (fabs(r) * DBL_MIN >= fabs(mad));
+    if (dom) return 0.0 + fabs(0.0 + r);
+    const double aq = fabs(q);
+    const double res = aq / thr;
+    if (!isfinite(res) || aq * DBL_MIN >= fabs(thr)) return 0.0 + aq;
+    return res;
+}
+
+__device__ __forceinline__ double scale_masked_f(float dv, bool valid, float med, float mad, double thr)
+{
+    if (!valid) return 0.0 + (double)fabsf(dv);
+    const float r = dv - med;
+    const float q = r / mad;
+    const bool dom = !isfinite(q) || ((double)fabsf(r) * DBL_MIN >= (double)fabsf(mad));
+    if (dom) return 0.0 + (double)fabsf(0.0f + r);
+    const float aq = fabsf(q);
+    const double res = (double)aq / thr;
+    if (!isfinite(res) || (double)aq * DBL_MIN >= fabs(thr)) return 0.0 + (double)aq;
+    return res;
+}
+
+__device__ __forceinline__ double scale_plain(double dv, double med, double mad, double thr)
+{
+    const double r = dv - med;
+    const double q = r / mad;
+    return fabs(q) / thr;
+}
+
+__device__ __forceinline__ double nanmax2(double a, double b)
+{
+    if (isnan(a) || isnan(b)) return NAN;
+    return a > b ? a : b;
+}
+
+// |test - 1| at or below this counts as a near tie (the fftmax tolerance of
+// the parity tests, DESIGN.md "Numerical semantics")
+constexpr double kNearTie = 1e-9;
+
+// counters: [0] changed vs hist[iter-1], [1] zero weights, [2] profiles whose
+// fit status is not 1-4 (info may be null: 0), [3] profiles whose test value
+// lies within kNearTie of the zap threshold 1.0 (where the last bits of fftmax,
+// not bit-identical to pocketfft, could decide), [4+h] != hist[h]
+
+__global__ __launch_bounds__(256) void k_combine(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters)
+{
+    // grid-stride; the convergence counters are reduced per block (one atomic
+    // per counter per block: same-address atomics serialise at the memory side)
+    __shared__ int red[4][4];
+    __shared__ unsigned long long dred[4];
+    const size_t P = (size_t)nsub * nchan;
+    int changed = 0, zero = 0, bad = 0, near = 0;
+    unsigned long long diff = 0ull;   // bit h: W != hist[h] somewhere (h < 64)
+    const int hmax = iter < 64 ? iter : 64;
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < P; k += (size_t)gridDim.x * blockDim.x) {
+        const int s = (int)(k / nchan), c = (int)(k % nchan);
+        const bool v = valid[k] != 0;
+        double S[4];
+        S[0] = nanmax2(scale_masked_d(std_d[k], v, col_med[c], col_mad[c], cth),
+                       scale_masked_d(std_d[k], v, row_med[s], row_mad[s], sth));
+        S[1] = nanmax2(scale_masked_d(mean_d[k], v, col_med[nchan + c], col_mad[nchan + c], cth),
+                       scale_masked_d(mean_d[k], v, row_med[nsub + s], row_mad[nsub + s], sth));
+        // ptp: numpy.ma in f32 for f32 data (Appendix A.5), f64 for f64 data
+        S[2] = ptp_f32 ? nanmax2(scale_masked_f((float)ptp_d[k], v, (float)col_med[2 * nchan + c],
+                                                (float)col_mad[2 * nchan + c], cth),
+                                 scale_masked_f((float)ptp_d[k], v, (float)row_med[2 * nsub + s],
+                                                (float)row_mad[2 * nsub + s], sth))
+                       : nanmax2(scale_masked_d(ptp_d[k], v, col_med[2 * nchan + c], col_mad[2 * nchan + c], cth),
+                                 scale_masked_d(ptp_d[k], v, row_med[2 * nsub + s], row_mad[2 * nsub + s], sth));
+        S[3] = nanmax2(scale_plain(fft_d[k], col_med[3 * nchan + c], col_mad[3 * nchan + c], cth),
+                       scale_plain(fft_d[k], row_med[3 * nsub + s], row_mad[3 * nsub + s], sth));
+        double t;
+        if (isnan(S[0]) || isnan(S[1]) || isnan(S[2]) || isnan(S[3])) {
+            t = NAN;
+        } else {
+            // sort 4
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3 - a; ++b)
+                    if (S[b] > S[b + 1]) {
+                        const double tmp = S[b];
+                        S[b] = S[b + 1];
+                        S[b + 1] = tmp;
+                    }
+            t = ((0.0 + S[1]) + S[2]) / 2.0;
+        }
+        test[k] = t;
+        near += fabs(t - 1.0) <= kNearTie;   // false for NaN
+        const float wn = (t >= 1.0) ? 0.0f : w0[k];
+        W[k] = wn;
+        hist[(size_t)iter * P + k] = wn;
+        changed += !(wn == hist[(size_t)(iter - 1) * P + k]);
+        zero += (wn == 0.0f);
+        if (info) {   // "Bad status for least squares fit" (iterative_cleaner.py:284-285)
+            const int st = info[k];
+            bad += (st < 1 || st > 4);
+        }
+        // history equality (iterative_cleaner.py:135-136)
+        for (int h = 0; h < hmax; ++h)
+            if (!(wn == hist[(size_t)h * P + k])) diff |= 1ull << h;
+        for (int h = 64; h < iter; ++h)
+            if (!(wn == hist[(size_t)h * P + k])) atomicOr(&counters[4 + h], 1);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        changed += __shfl_xor(changed, off);
+        zero += __shfl_xor(zero, off);
+        bad += __shfl_xor(bad, off);
+        near += __shfl_xor(near, off);
+        diff |= __shfl_xor(diff, off);
+    }
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wave] = changed;
+        red[1][wave] = zero;
+        red[2][wave] = bad;
+        red[3][wave] = near;
+        dred[wave] = diff;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int ch = 0, ze = 0, bd = 0, nt = 0;
+        unsigned long long df = 0ull;
+        for (int w = 0; w < nw; ++w) {
+            ch += red[0][w];
+            ze += red[1][w];
+            bd += red[2][w];
+            nt += red[3][w];
+            df |= dred[w];
+        }
+        // counters[0..1] (changed, zero) as one u64 add: both < 2^32, no carry
+        if (ch || ze)
+            atomicAdd((unsigned long long *)counters, ((unsigned long long)(unsigned)ze << 32) | (unsigned)ch);
+        if (bd) atomicAdd(&counters[2], bd);
+        if (nt) atomicAdd(&counters[3], nt);
+        for (int h = 0; h < hmax; ++h)
+            if ((df >> h) & 1ull) atomicOr(&counters[4 + h], 1);
+    }
+}
+
+// ============================================================ launchers
+
+hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
+{
+    // columns (length nsub), then rows (length nchan); wave-private LDS:
+    // 256-bin histogram + the line's keys
+    for (int rows = 0; rows < 2; ++rows) {
+        if (!((which >> rows) & 1)) continue;
+        const int len = rows ? a.nchan : a.nsub;
+        const int lines = 4 * (rows ? a.nsub : a.nchan);
+        if (lines == 0 || len == 0) continue;
+        // few long lines (the rows): W waves per line (a.grp_waves = W in {0, 4, 8},
+        // 0 = one wave per line; a.grp_minlen = the shortest line it takes)
+        if (lines < 8192 && len >= a.grp_minlen) {
+            const int W = a.grp_waves;
+            if (W == 4 || W == 8) {
+                const int seg = (((len + W - 1) / W) + 63) & ~63;
+                const size_t gshm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8;
+                if (gshm <= 160 * 1024) {
+                    if (W == 4)
+                        IC_GGL(k_linestats_grp<4>, dim3(lines), dim3(256), gshm, st, a, rows, len);
+                    else
+                        IC_GGL(k_linestats_grp<8>, dim3(lines), dim3(512), gshm, st, a, rows, len);
+                    const hipError_t e = hipGetLastError();
+                    if (e != hipSuccess) return e;
+                    continue;
+                }
+            }
+        }
+        const int per_wave = 1024 + ((len * 8 + 15) / 16) * 16;
+        int wpb = 4;
+        while (wpb > 1 && (size_t)wpb * per_wave > 64 * 1024) --wpb;
+        const size_t shm = (size_t)wpb * per_wave;
+        if (shm > 160 * 1024) return hipErrorInvalidValue;
+        IC_GGL(k_linestats, dim3(cdiv(lines, wpb)), dim3(64 * wpb), shm, st, a, rows, len, wpb,
+                           per_wave);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                          const float *w0,
+                          const double *std_d, const double *mean_d, const double *ptp_d, int ptp_f32,
+                          const double *fft_d, const double *col_med, const double *col_mad,
+                          const double *row_med, const double *row_mad, double chanthresh,
+                          double subintthresh, double *test, float *W, float *hist, int iter,
+                          int32_t *counters, int grid_cap)
+{
+    const size_t P = (size_t)nsub * nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
+    IC_GGL(k_combine, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d,
+                       mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh,
+                       test, W, hist, iter, counters);
+    return hipGetLastError();
+}
+
+}  // namespace icgpu

@@ -7,7 +7,7 @@ multiply harmonic k by exp(i 2 pi k s / nbin), inverse real FFT, 1/nbin).  The
 reference calls it through ``dedisperse()`` / ``dededisperse()``
 (iterative_cleaner.py:91, :100, :104).  psrchive is absent here, so real-data
 parity is unpinned; this module DEFINES the stand-in's rotation so that the
-GPU kernel (k_rotate, ic_kernels.hip), the C restatement the tests check
+GPU kernel (k_rotate, ic_rotate.hip), the C restatement the tests check
 against (orc_rotate in the oracle/ directory) and this numpy version agree bit for
 bit.
 

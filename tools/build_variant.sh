@@ -7,9 +7,9 @@ name=$1; shift
 here=$(cd "$(dirname "$0")/.." && pwd)
 obj=$(mktemp -d)
 cd "$here/iterative_cleaner_amd/csrc"
-for f in ic_kernels ic_session ic_comm; do
+for f in ic_*.hip; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
-        -I../../include "$@" -c $f.hip -o "$obj/$f.o"
+        -I../../include "$@" -c $f -o "$obj/${f%.hip}.o"
 done
 mkdir -p "$here/ab"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$here/ab/libicgpu_$name.so" "$obj"/*.o

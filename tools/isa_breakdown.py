@@ -1,5 +1,7 @@
 """Per-category instruction counts of one kernel in the gfx950 assembly
-(`make -C iterative_cleaner_amd/csrc asm` -> ic_kernels.s).
+(`make -C iterative_cleaner_amd/csrc asm` -> one .s per kernel unit; --asm
+picks the unit that holds the kernel: ic_kernels.s (template, codec, fit,
+diagnostics; the default), ic_rotate.s, ic_linestats.s or ic_shards.s).
 
     python tools/isa_breakdown.py KERNEL_SUBSTRING [--asm PATH] [--blocks]
 

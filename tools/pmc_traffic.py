@@ -19,14 +19,16 @@ from __future__ import annotations
 import argparse
 import collections
 import csv
+import glob
 import hashlib
 import json
 import os
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("iterative_cleaner_amd/csrc/ic_kernels.hip", "iterative_cleaner_amd/csrc/ic_session.hip",
-           "iterative_cleaner_amd/csrc/ic_internal.h", "iterative_cleaner_amd/csrc/ic_comm.hip",
-           "iterative_cleaner_amd/csrc/ic_comm.h")
+# every HIP source and header of the library, in a fixed order
+CSRC = "iterative_cleaner_amd/csrc"
+SOURCES = tuple(sorted(CSRC + "/" + os.path.basename(f)
+                       for ext in ("*.hip", "*.h") for f in glob.glob(os.path.join(REPO, CSRC, ext))))
 
 
 def source_sha() -> str:

@@ -1,0 +1,1164 @@
+// ic_diag.hip -- the diagnostics of the surgical-cleaning loop, with their
+// launchers.  The FFT pieces, the P2 / CLay layouts and the rules shared with
+// the rotation are in ic_fftdiag.h.
+//
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see Makefile).
+// -ffp-contract=off is load-bearing: every f64/f32 operation below must be an
+// individually rounded IEEE op in the order written, so that results equal
+// numpy / scipy (MINPACK) bit-for-bit.  Explicit fma() is never used on an
+// exact path.
+//
+// Kernels:
+//   k_diag           residual (ic.py:279-288), f32 store (:272), dededisperse
+//                    (:104), apply_weights (:296), diagnostics (:206-217); any
+//                    nbin, a wave per profile
+//   k_diag_p2        the same for the power-of-two nbin (IC_P2_SIZES)
+//   k_diag_cl        the chain layout at nbin 1024 / 2048 / 4096
+//   k_residual       the residual cube on request (ic_get_residual)
+//   k_tnorm          sum(T*T), fit_mode 1's denominator
+#include <algorithm>
+#include <math.h>
+
+#include <type_traits>
+
+#include "ic_fftdiag.h"
+
+namespace icgpu {
+
+// ============================================================ diagnostics
+
+// numpy pairwise sum of n values produced by get(i), in dtype Tp (one wave).
+// scratch: >= 8*nleaf + nleaf + nops slots of Tp in LDS.
+template <typename Tp, typename Get>
+__device__ Tp wave_pairwise(const PwPlan &pl, Get get, Tp *scratch, int lane)
+{
+    const int nl = pl.nleaf;
+    Tp *acc = scratch;             // [nl*8]
+    Tp *slot = scratch + nl * 8;   // [nl + nops]
+    for (int task = lane; task < nl * 8; task += 64) {
+        const int Lf = task >> 3, j = task & 7;
+        const int st = pl.leaf_start[Lf], len = pl.leaf_len[Lf];
+        if (len < 8) {
+            if (j == 0) {
+                Tp res = (Tp)0;
+                for (int q = 0; q < len; ++q) res = res + get(st + q);
+                acc[task] = res;
+            }
+            continue;
+        }
+        const int main = len - len % 8;
+        Tp r = get(st + j);
+        for (int q = 8; q < main; q += 8) r = r + get(st + q + j);
+        acc[task] = r;
+    }
+    wave_sync();
+    for (int Lf = lane; Lf < nl; Lf += 64) {
+        const int st = pl.leaf_start[Lf], len = pl.leaf_len[Lf];
+        const Tp *r = acc + Lf * 8;
+        Tp res;
+        if (len < 8) {
+            res = r[0];
+        } else {
+            const Tp a01 = r[0] + r[1], a23 = r[2] + r[3], a45 = r[4] + r[5], a67 = r[6] + r[7];
+            const Tp lo = a01 + a23, hi = a45 + a67;
+            res = lo + hi;
+            for (int q = len - len % 8; q < len; ++q) res = res + get(st + q);
+        }
+        slot[Lf] = res;
+    }
+    wave_sync();
+    Tp out = (Tp)0;
+    if (lane == 0) {
+        for (int o = 0; o < pl.nops; ++o) slot[nl + o] = slot[pl.op_a[o]] + slot[pl.op_b[o]];
+        out = (Tp)0 + slot[pl.root];
+        acc[0] = out;
+    }
+    wave_sync();
+    out = acc[0];
+    wave_sync();
+    return out;
+}
+
+// Persistent blocks of `wpb` independent waves; each wave cleans profiles
+// k = blockIdx.x*wpb + wave, += gridDim.x*wpb.  LDS: plan + twiddles (block-shared,
+// loaded once) | per wave: complex work [n/2] (pow2) | X f32 [n] | pairwise scratch.
+// Per profile: the f32 residual (iterative_cleaner.py:279-288, :272), dededispersion
+// (:104), the ORIGINAL weight (:296) and the four diagnostics (:206-217) with
+// numpy.ma data conventions.
+// exp(-2 pi i q/n) for 0 <= q < n from the half table tw[0..n/2)
+__device__ __forceinline__ double2 twid(const double2 *tw, int q, int half)
+{
+    if (q < half) return tw[q];
+    const double2 t = tw[q - half];
+    return make_double2(-t.x, -t.y);
+}
+
+// One radix-R Stockham stage over m points (src -> dst), Ns = product of earlier radices.
+// get(q) supplies src point q (lets the first stage read the real input directly).
+template <int R, typename Get>
+__device__ __forceinline__ void stockham_stage(Get get, double2 *dst, int m, int Ns, const double2 *tw, int n,
+                                               int lane)
+{
+    const int nb = m / R;
+    const int tmul = n / (R * Ns);
+    for (int b = lane; b < nb; b += 64) {
+        const int k = b & (Ns - 1);
+        double2 v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = get(b + r * nb);
+        if (Ns > 1) {
+#pragma unroll
+            for (int r = 1; r < R; ++r) v[r] = cmul(v[r], twid(tw, r * k * tmul, n / 2));
+        }
+        dft_small<R>(v);
+        const int idx = (b - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) dst[idx + r * Ns] = v[r];
+    }
+}
+
+struct DiagLayout {
+    int ntw;          // twiddles in LDS
+    size_t cw_off, x_off, p_off, scr_off, per_wave;
+};
+
+__host__ __device__ inline DiagLayout diag_layout(int n, int nleaf, int nops)
+{
+    DiagLayout L;
+    const bool pow2 = (n & (n - 1)) == 0 && n >= 4;
+    L.ntw = pow2 ? n / 2 : n;
+    L.cw_off = 0;                                            // buffer A: n/2 complex
+    const size_t cwb = (size_t)(pow2 ? n / 2 : 1) * 16;
+    L.x_off = cwb;                                           // buffer B (n/2 complex) aliases X (n f64)
+    const size_t xb = ((size_t)n * 8 + 15) & ~(size_t)15;
+    const size_t pb = ((size_t)n * 4 + 15) & ~(size_t)15;
+    L.p_off = L.x_off + (pow2 ? (cwb > xb ? cwb : xb) : xb);  // DIAG_CLOSED: the fit-cube row
+    L.scr_off = L.p_off + pb;
+    L.per_wave = L.scr_off + (size_t)(nleaf * 9 + nops + 8) * 8;
+    L.per_wave = (L.per_wave + 15) & ~(size_t)15;
+    return L;
+}
+
+__global__ __launch_bounds__(256) void k_diag(DiagArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ PwPlan pl;
+    const int n = a.nbin;
+    const int wpb = blockDim.x >> 6;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    {
+        const int32_t *src = (const int32_t *)a.plan;
+        int32_t *dst = (int32_t *)&pl;
+        for (int q = threadIdx.x; q < (int)(sizeof(PwPlan) / 4); q += blockDim.x) dst[q] = src[q];
+    }
+    const DiagLayout lay = diag_layout(n, a.plan->nleaf, a.plan->nops);
+    double2 *tw = (double2 *)smem;
+    for (int q = threadIdx.x; q < lay.ntw; q += blockDim.x) tw[q] = a.tw[q];
+    __syncthreads();
+    unsigned char *wb = smem + (size_t)lay.ntw * 16 + (size_t)wave * lay.per_wave;
+    double2 *cw = (double2 *)(wb + lay.cw_off);
+    double *X = (double *)(wb + lay.x_off);   // f32 values unless data_f64
+    float *Pr = (float *)(wb + lay.p_off);
+    double *scr = (double *)(wb + lay.scr_off);
+    const bool pow2 = (n & (n - 1)) == 0 && n >= 4;
+    const size_t P = (size_t)a.nsub * a.nchan;
+    const double *T64 = a.T64;
+    const int mode = a.mode;
+
+    for (size_t k = (size_t)blockIdx.x * wpb + wave; k < P; k += (size_t)gridDim.x * wpb) {
+        const int c = (int)((unsigned)k % (unsigned)a.nchan);
+        const float w = a.w0[k];
+        const bool valid = (w != 0.0f);
+        const int sh = mode == DIAG_STATS ? 0 : a.shift[c];
+        wave_sync();   // previous profile's LDS reads are done
+        double x = 0.0;
+        int stt = 0;
+        const float *p;
+        if (mode == DIAG_CLOSED) {
+            // the fit-cube row f32(ded - base0), dedispersed order, then the
+            // closed-form amplitude from numpy pairwise sums
+            const float *row = a.raw + k * (size_t)n;
+            const float b = a.base[k];
+            for (int j = lane; j < n; j += 64) {
+                int i = j - sh;
+                if (i < 0) i += n;
+                Pr[i] = row[j] - b;
+            }
+            wave_sync();
+            // the products in the stored (dispersed) order j: bin i = (j - sh) mod n
+            const double dot = wave_pairwise<double>(pl, [&](int q) {
+                int i = q - sh;
+                if (i < 0) i += n;
+                return T64[i] * (double)Pr[i];
+            }, scr, lane);
+            const double TT = *a.TT;
+            x = TT != 0.0 ? dot / TT : 0.0;
+            stt = isfinite(x) ? 1 : 5;
+            if (lane == 0) {
+                a.amp[k] = x;
+                a.info[k] = stt;
+            }
+            p = Pr;
+        } else {
+            if (mode == DIAG_EXACT) {
+                x = a.amp[k];
+                stt = a.info[k];
+            }
+            p = a.D + k * (size_t)a.ldD;
+        }
+        const bool tr = a.dtiled && mode == DIAG_EXACT;   // the tiled fit cube (dt_ofs)
+        auto prow = [&](int i) -> float { return tr ? a.D[dt_ofs(k, i, a.ldD)] : p[i]; };
+        const bool ok = fit_ok(stt);
+        // residual -> X (dispersed frame): X[j] = f32(f32(r[i]) * w), j = (i + sh) mod n
+        // (f64(f32(r[i])) * f64(w) for f64 data)
+        for (int i = lane; i < n; i += 64) {
+            float R = 0.0f;
+            if (mode == DIAG_STATS) {
+                R = p[i];
+            } else if (ok) {
+                R = residual_sample(x, T64[i], prow(i), i, a);
+            }
+            int j = i + sh;
+            if (j >= n) j -= n;
+            X[j] = a.data_f64 ? (double)R * (double)w : (double)(R * w);
+        }
+        wave_sync();
+        double mean = 0.0, sd = 0.0, ptp = ptp_fill(a.data_f64);
+        if (valid) {
+            if (a.data_f64)
+                mean = wave_pairwise<double>(pl, [&](int q) { return X[q]; }, scr, lane) / (double)n;
+            else
+                mean = (double)wave_pairwise<float>(pl, [&](int q) { return (float)X[q]; }, (float *)scr, lane) /
+                       (double)n;
+            const double mu = mean;
+            const double ss = wave_pairwise<double>(
+                pl,
+                [&](int q) {
+                    const double d = (double)X[q] - mu;
+                    return d * d;
+                },
+                scr, lane);
+            sd = sqrt(ss / (double)n);
+            double mx = -INFINITY, mn = INFINITY;
+            int nan = 0;
+            for (int q = lane; q < n; q += 64) {
+                const double v = X[q];
+                if (isnan(v)) nan = 1;
+                mx = fmax(mx, v);
+                mn = fmin(mn, v);
+            }
+            mx = wave_tree<64>(mx, OpMaxF());
+            mn = wave_tree<64>(mn, OpMinF());
+            nan = wave_tree<64>(nan, OpOr());
+            // max - min in the data dtype (exact widening of f32 values)
+            ptp = nan ? (double)NAN : (a.data_f64 ? mx - mn : (double)((float)mx - (float)mn));
+        }
+        // fftmax: max_k |rfft(v)_k|, v = f64(X) - mean (valid) or f64(X) (invalid)
+        const double mu = valid ? mean : 0.0;
+        double best = 0.0;
+        int nanf = 0;
+        if (pow2) {
+            const int m = n / 2;
+            double2 *bufA = cw;
+            double2 *bufB = (double2 *)X;    // X is dead once the first stage has read it
+            int lg = 0;
+            while ((1 << lg) < m) ++lg;
+            // stage radices: as many 8s as possible, then one 4 or 2
+            int Ns = 1, done = 0;
+            double2 *src = nullptr, *dst = bufA;
+            auto first = [&](int q) {
+                return valid ? make_double2((double)X[2 * q] - mu, (double)X[2 * q + 1] - mu)
+                             : make_double2((double)X[2 * q], (double)X[2 * q + 1]);
+            };
+            auto from = [&](int q) { return src[q]; };
+            while (done < lg) {
+                const int rem = lg - done;
+                const int rl = rem >= 3 ? 3 : rem;
+                if (Ns == 1) {
+                    if (rl == 3) stockham_stage<8>(first, dst, m, Ns, tw, n, lane);
+                    else if (rl == 2) stockham_stage<4>(first, dst, m, Ns, tw, n, lane);
+                    else stockham_stage<2>(first, dst, m, Ns, tw, n, lane);
+                } else {
+                    if (rl == 3) stockham_stage<8>(from, dst, m, Ns, tw, n, lane);
+                    else if (rl == 2) stockham_stage<4>(from, dst, m, Ns, tw, n, lane);
+                    else stockham_stage<2>(from, dst, m, Ns, tw, n, lane);
+                }
+                wave_sync();
+                Ns <<= rl;
+                done += rl;
+                src = dst;
+                dst = (dst == bufA) ? bufB : bufA;
+            }
+            const double2 *Z = (lg == 0) ? nullptr : src;
+            // X_k = (Z_k + conj(Z_{m-k}))/2 - i/2 W^k (Z_k - conj(Z_{m-k})), W = exp(-2 pi i/n)
+            for (int kk = lane; kk <= m; kk += 64) {
+                const double2 zk = Z[kk == m ? 0 : kk];
+                const double2 zm = Z[kk == 0 ? 0 : m - kk];
+                const double er = 0.5 * (zk.x + zm.x), ei = 0.5 * (zk.y - zm.y);
+                const double orr = 0.5 * (zk.y + zm.y), oi = -0.5 * (zk.x - zm.x);
+                double wr = -1.0, wi = 0.0;
+                if (kk < m) {
+                    const double2 wv = tw[kk];
+                    wr = wv.x;
+                    wi = wv.y;
+                }
+                const double re = er + (orr * wr - oi * wi);
+                const double im = ei + (orr * wi + oi * wr);
+                const double mag = hypot(re, im);
+                if (isnan(mag)) nanf = 1;
+                best = fmax(best, mag);
+            }
+        } else {
+            for (int kk = lane; kk <= n / 2; kk += 64) {
+                double sr = 0.0, si = 0.0;
+                int q = 0;
+                for (int j = 0; j < n; ++j) {
+                    const double v = valid ? (double)X[j] - mu : (double)X[j];
+                    const double2 wv = tw[q];
+                    sr += v * wv.x;
+                    si += v * wv.y;
+                    q += kk;
+                    if (q >= n) q -= n;
+                }
+                const double mag = hypot(sr, si);
+                if (isnan(mag)) nanf = 1;
+                best = fmax(best, mag);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            best = fmax(best, __shfl_xor(best, off));
+            nanf |= __shfl_xor(nanf, off);
+        }
+        if (lane == 0) {   // diag_store, restated: the call moved the epilogue's code
+            a.std_o[k] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
+            a.mean_o[k] = valid ? mean : 0.0;
+            a.ptp_o[k] = ptp;
+            a.fft_o[k] = nanf ? NAN : best;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_diag_p2<N>: the same diagnostics for power-of-two nbin = N (IC_P2_SIZES:
+// 64..8192).  A profile group of TPP = 64*WPP threads cleans one profile: one
+// wave for N <= 1024, N/1024 waves for N = 2048/4096/8192, so every thread holds
+// the same 16 samples and one pairwise chain at every N >= 1024 (at N = 4096 one
+// wave per profile needed a 32-KiB work array per wave: 1.25 waves/SIMD).  At
+// N = 8192 the group is 8 waves (512 threads) around a 64-KiB work array (68 KiB
+// for f64 data): two groups per CU, 4 waves per SIMD, and four radix-8 stages.
+// numpy's pairwise sum for N = 2^k is a balanced tree over leaves of
+// min(N,128) samples, each leaf 8 strided chains of min(N,128)/8 samples:
+// chain c = (leaf c/8, accumulator c%8) lives in thread c%TPP, slot c/TPP, and
+// the tree is reproduced exactly by xor-shuffles within a wave (IEEE add is
+// commutative), a balanced add of the group's waves and a balanced in-register
+// add of the slots.  X sits in LDS at idx + 8*(idx>>7) so the chain reads are
+// bank-conflict free.  The rFFT is an in-place mixed-radix Stockham FFT of
+// N/2 complex points (all of a stage's inputs are in registers before it
+// writes).
+// Modes (DiagArgs.mode):
+//   DIAG_EXACT   residual from the exact fit's amplitude / status (ic.py:279-288)
+//   DIAG_CLOSED  fit_mode 1: closed-form amplitude a = sum(T*p) / sum(T*T)
+//                (numpy pairwise f64 sums over the dedispersed profile, the
+//                fit cube row p = f32(ded - base0) formed from the raw cube),
+//                then the same residual; writes amp / info
+//   DIAG_STATS   comprehensive_stats alone (ic.py:181-226): X = f32(row * w)
+// occupancy floors (waves per SIMD, <= 128 VGPRs): 4 for the multi-wave groups
+// (the LDS allows 4 blocks of 4096 per CU and 2 of 8192, 16 waves either way)
+// and for N = 1024 (the LDS allows 4
+// waves/SIMD with 8-wave blocks), where the template is then read from L1
+// instead of being held in 32 VGPRs.  Measured on C2 (k_diag ms per clean):
+// 3 waves + template in registers 8.63, 4 waves + registers 8.10 (spills),
+// 4 waves + L1 template 7.95 (profiles/r02_c2_diag_ab.txt).
+template <int N>
+constexpr int p2_min_waves() { return N >= 2048 ? 4 : (N == 1024 ? 4 : 1); }
+
+// D64 (data_f64): psrchive's get_data returns f64, so apply_weights and the
+// masked statistics run in f64 (iterative_cleaner.py:111-112, :206-209): X =
+// f64(R) * f64(w), the mean's pairwise sum and ptp in f64.
+template <int N, int MODE, bool D64>
+__global__ __launch_bounds__(N >= 2048 ? P2<N>::TPP : 512, p2_min_waves<N>()) void k_diag_p2(DiagArgs a)
+{
+    using C = P2<N, D64>;
+    using XT = typename std::conditional<D64, double, float>::type;
+    constexpr int WPP = C::WPP, TPP = C::TPP, NPT = C::NPT;
+    // one-wave groups keep the template and the next row in registers; the
+    // multi-wave groups (N >= 2048) read both when needed and rely on occupancy
+    constexpr bool TREG = WPP == 1 && N != 1024, PREFETCH = WPP == 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // [M] post-processing twiddles, then the stage tables (LDS copy unless TWG)
+    const double2 *tw = C::TWG ? a.tw_p2 : (const double2 *)smem;
+    const double *T = a.T64;          // L1/L2-resident, read coalesced
+    constexpr int mode = MODE;
+    const int lane = threadIdx.x & 63;
+    // WPP == 1: independent waves (groups) per block; WPP > 1: the block is one group
+    const int group = WPP == 1 ? (int)(threadIdx.x >> 6) : 0;
+    const int gpb = WPP == 1 ? (int)(blockDim.x >> 6) : 1;
+    const int wave = WPP == 1 ? 0 : (int)(threadIdx.x >> 6);   // wave within the group
+    int t = WPP == 1 ? lane : (int)threadIdx.x;               // thread within the group
+    if (!C::TWG) {
+        for (int q = threadIdx.x; q < C::TW; q += blockDim.x) ((double2 *)smem)[q] = a.tw_p2[q];
+        __syncthreads();
+    }
+    unsigned char *gb = smem + (size_t)C::TW_LDS * 16 + (size_t)group * C::GROUP_BYTES;
+    XT *X = (XT *)gb;
+    double2 *Cb = (double2 *)gb;   // aliases X after the first FFT stage has read it
+    double *red = (double *)(gb + C::WORK_BYTES);   // 64 slots of 8 B (WPP > 1)
+    const unsigned P = (unsigned)a.nsub * (unsigned)a.nchan;
+    const unsigned stride = gridDim.x * gpb;
+    const int nchan = a.nchan;
+    // the template stays in registers, and each group loads the next profile's
+    // row while it works on the current one: every global load of the loop is
+    // issued ahead of its use (software pipelining)
+    double tv[TREG ? NPT : 1];
+    if (TREG) {
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) tv[u] = T[t + TPP * u];
+    }
+    constexpr bool closed = mode == DIAG_CLOSED || mode == DIAG_FIT;
+    const double TT = closed ? *a.TT : 0.0;
+    // DIAG_EXACT reads the raw row, not the fit cube: the cube's value is
+    // D_i = f32(raw_j - base0), j = (i + sh) mod N (k_chan_partials mode 3), and
+    // the raw rows are contiguous whatever the cube's layout (dt_ofs)
+    constexpr bool fromraw = mode == DIAG_CLOSED || mode == DIAG_EXACT;
+    const float *rows = fromraw ? a.raw : a.D;
+    const size_t ld = fromraw ? (size_t)N : (size_t)a.ldD;
+    float pv[NPT];
+    auto loadrow = [&](unsigned kk) {
+        const float *pn = rows + (size_t)kk * ld;
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) pv[u] = pn[t + TPP * u];
+    };
+    // profiles: all P, or the slots of a list, minus those with skip[k] != 0
+    // (the two passes of the exact fit's forked diagnostics)
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const unsigned nslot = (unsigned)rl.n();
+    const uint8_t *skip = a.skip;
+    auto next_slot = [&](unsigned sl) {   // the first slot >= sl this group measures (uniform)
+        if (skip)
+            while (sl < nslot && skip[rl.at(sl)]) sl += stride;
+        return sl;
+    };
+    unsigned slot = next_slot(__builtin_amdgcn_readfirstlane(blockIdx.x * gpb + group));
+    unsigned k = slot < nslot ? (unsigned)rl.at(slot) : 0u;
+    // per-profile scalars, loaded one profile ahead as well
+    double nx = 0.0;
+    int nst = 0, nsh = 0;
+    float nw = 0.0f, nb = 0.0f;
+    if (slot < nslot) {
+        if (PREFETCH) {
+            loadrow(k);
+        }
+        if (mode == DIAG_EXACT) {
+            nx = a.amp[k];
+            nst = a.info[k];
+        }
+        if (fromraw) nb = a.base[k];
+        nw = a.w0[k];
+        nsh = (mode == DIAG_STATS || mode == DIAG_FIT) ? 0 : a.shift[k % (unsigned)nchan];
+    }
+    for (unsigned snext = 0; slot < nslot; slot = snext, k = slot < nslot ? (unsigned)rl.at(slot) : 0u) {
+        snext = next_slot(slot + stride);
+        // opaque to the optimiser: the LDS addresses of the FFT stages derive
+        // from t, and hoisting all of them out of the loop costs ~100 VGPRs
+        // (spills at N >= 2048); recomputing them is a few VALU ops each
+        asm volatile("" : "+v"(t));
+        double x = nx;
+        int st = nst;
+        const float w = nw;
+        const bool valid = (w != 0.0f);
+        const int sh = nsh;
+        const float bk = nb;
+        if (!PREFETCH) {
+            loadrow(k);
+        }
+        gsync<WPP>();
+        if (closed) {
+            // fit cube row p_i = f32(ded_i - base0), i = (j - sh) mod N: to LDS in
+            // the dedispersed order, then a = sum(T*p)/sum(T*T) over the chains
+            // of the stored order (the products T_i p_i of j = i + sh)
+            const XWrap<N, TPP> xw((t - sh) & (N - 1));
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) X[xw(u)] = (XT)(pv[u] - bk);
+            gsync<WPP>();
+            double cs[C::CPL];
+            const bool act = C::ACT >= TPP || t < C::ACT;   // every thread holds a chain at N >= 512
+#pragma unroll
+            for (int sl = 0; sl < C::CPL; ++sl) {
+                const int ch = t + TPP * sl;
+                const int base = (ch >> 3) * C::LEAF + (ch & 7);
+                double r = 0.0;
+                if (act) {
+                    // the chain's stored (dispersed) samples j = base + 8 q pair
+                    // with the dedispersed bins i = (j - sh) mod N
+                    auto term = [&](int j) {
+                        const int i = (j - sh) & (N - 1);
+                        return T[i] * (double)X[xaddr(i)];
+                    };
+                    r = term(base);
+#pragma unroll
+                    for (int q = 1; q < C::CL; ++q) {
+                        const double pr = term(base + 8 * q);
+                        r = r + pr;
+                    }
+                }
+                cs[sl] = r;
+            }
+            const double dot = 0.0 + chain_total<N, double>(cs, red, wave, lane);
+            x = TT != 0.0 ? dot / TT : 0.0;
+            st = isfinite(x) ? 1 : 5;
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) pv[u] = (float)X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)];
+            if (t == 0) {
+                a.amp[k] = x;
+                a.info[k] = st;
+            }
+            gsync<WPP>();
+        }
+        if constexpr (mode == DIAG_FIT) {   // the amplitude is all this mode produces
+            if (PREFETCH && snext < nslot) loadrow((unsigned)rl.at(snext));
+            continue;
+        }
+        const bool ok = fit_ok(st);
+        // residual -> X (dispersed frame, padded addresses)
+        // X = apply_weights(R, w0): f32(R * w), or f64(R) * f64(w) for f64 data
+        auto weigh = [&](float R) -> XT {
+            if constexpr (D64) return (double)R * (double)w;
+            else return R * w;
+        };
+        if (mode == DIAG_STATS) {
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)] = weigh(pv[u]);
+        } else if (mode == DIAG_EXACT) {
+            // sample j = t + TPP u of the raw row (dispersed frame) is the
+            // dedispersed sample i = (j - sh) mod N: residual f32(x T_i - D_i)
+            // with D_i = f32(raw_j - base0), written to X[j]
+            const int i0 = (t - sh) & (N - 1);
+            double tg[NPT];   // the template gathered at i: all loads issued before the first use
+            {
+                // byte offsets (8 i0 + 8 TPP u) mod 8N through a buffer descriptor: two VALU per load
+                const __amdgpu_buffer_rsrc_t tr =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(T), 0, 8 * N, 0x00020000);
+                const unsigned b0 = 8u * (unsigned)i0;
+#pragma unroll
+                for (int u = 0; u < NPT; ++u)
+                    tg[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(
+                                                           tr, (b0 + 8u * TPP * u) & (8u * N - 1u), 0, 0));
+            }
+            if (a.pr_on) {
+#pragma unroll
+                for (int u = 0; u < NPT; ++u) {
+                    const int i = (i0 + TPP * u) & (N - 1);
+                    const float pj = pv[u] - bk;
+                    const float e = residual_sample(x, tg[u], pj, i, PulseRegion{true, a.pr_start, a.pr_end, a.pr_factor});
+                    const float R = ok ? e : 0.0f;
+                    X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)] = weigh(R);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < NPT; ++u) {
+                    const float pj = pv[u] - bk;
+                    const float e = residual_sample(x, tg[u], pj);
+                    const float R = ok ? e : 0.0f;
+                    X[TPP % 128 == 0 ? xaddr(t) + u * (TPP + TPP / 16) : xaddr(t + TPP * u)] = weigh(R);
+                }
+            }
+        } else if (a.pr_on) {
+            const XWrap<N, TPP> xw((t + sh) & (N - 1));
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) {
+                const int i = t + TPP * u;
+                // residual_sample, restated: either call changed some closed forms of this kernel
+                const double uu = x * (TREG ? tv[u] : T[i]);
+                double e = uu - (double)pv[u];
+                if (i >= a.pr_start && i < a.pr_end) e = e * a.pr_factor;
+                const float R = ok ? (float)e : 0.0f;
+                X[xw(u)] = weigh(R);
+            }
+        } else {
+            const XWrap<N, TPP> xw((t + sh) & (N - 1));
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) {
+                const int i = t + TPP * u;
+                const float e = residual_sample(x, TREG ? tv[u] : T[i], pv[u]);
+                const float R = ok ? e : 0.0f;
+                X[xw(u)] = weigh(R);
+            }
+        }
+        if (snext < nslot) {
+            const unsigned kn = (unsigned)rl.at(snext);
+            if (PREFETCH) loadrow(kn);
+            if (mode == DIAG_EXACT) {
+                nx = a.amp[kn];
+                nst = a.info[kn];
+            }
+            if (fromraw) nb = a.base[kn];
+            nw = a.w0[kn];
+            nsh = mode == DIAG_STATS ? 0 : a.shift[kn % (unsigned)nchan];
+        }
+        gsync<WPP>();
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(D64);
+        if (valid) {
+            // chain values -> registers
+            XT v[C::CPL][C::CL];
+            const bool act = C::ACT >= TPP || t < C::ACT;   // every thread holds a chain at N >= 512
+#pragma unroll
+            for (int sl = 0; sl < C::CPL; ++sl) {
+                const int ch = t + TPP * sl;
+                const int base = (ch >> 3) * C::LEAF + (ch & 7);
+#pragma unroll
+                for (int q = 0; q < C::CL; ++q) v[sl][q] = act ? X[xaddr(base) + 8 * q] : (XT)0;
+            }
+            // mean: pairwise sum in the data dtype (f32, or f64 for f64 data)
+            XT fs[C::CPL];
+#pragma unroll
+            for (int sl = 0; sl < C::CPL; ++sl) {
+                XT r = v[sl][0];
+#pragma unroll
+                for (int q = 1; q < C::CL; ++q) r = r + v[sl][q];
+                fs[sl] = r;
+            }
+            const XT s32 = (XT)0 + chain_total<N, XT>(fs, (XT *)(red + 16), wave, lane);
+            mean = (double)s32 / (double)N;
+            // var: f64 pairwise sum of (f64(X) - mean)^2
+            double ds[C::CPL];
+#pragma unroll
+            for (int sl = 0; sl < C::CPL; ++sl) {
+                double d0 = (double)v[sl][0] - mean;
+                double r = d0 * d0;
+#pragma unroll
+                for (int q = 1; q < C::CL; ++q) {
+                    const double d = (double)v[sl][q] - mean;
+                    const double sq = d * d;
+                    r = r + sq;
+                }
+                ds[sl] = r;
+            }
+            const double ss = 0.0 + chain_total<N, double>(ds, red + 24, wave, lane);
+            sd = sqrt(ss / (double)N);
+            // ptp (NaN-propagating), in the data dtype
+            XT mx = -INFINITY, mn = INFINITY;
+            if (act) {
+#pragma unroll
+                for (int sl = 0; sl < C::CPL; ++sl)
+#pragma unroll
+                    for (int q = 0; q < C::CL; ++q) {
+                        mx = OpMaxF()(mx, v[sl][q]);
+                        mn = OpMinF()(mn, v[sl][q]);
+                    }
+            }
+            mx = group_tree<WPP, 64>(mx, OpMaxF(), (XT *)(red + 32), wave, lane);
+            mn = group_tree<WPP, 64>(mn, OpMinF(), (XT *)(red + 40), wave, lane);
+            // a NaN sample makes the pairwise sum s32 NaN; a NaN s32 without one
+            // (inf - inf) is rare, and only then are the samples checked one by one
+            int nan = 0;
+            if (isnan(s32)) {   // group-uniform
+                if (act) {
+#pragma unroll
+                    for (int sl = 0; sl < C::CPL; ++sl)
+#pragma unroll
+                        for (int q = 0; q < C::CL; ++q) nan |= isnan(v[sl][q]);
+                }
+                nan = group_tree<WPP, 64>(nan, OpOr(), (int *)(red + 48), wave, lane);
+            }
+            ptp = nan ? (double)NAN : (double)(XT)(mx - mn);
+            // rFFT of f64(X) - mean: N/2-point complex Stockham, in place
+            p2_fft<C::M, TPP, C::LG, 0, 1, C::M, XT>(Cb, X, mean, tw, t);
+            // X_k = E_k + w^k O_k, computed as 2 X_k (the 1/2 factors are exact
+            // powers of two, applied once to the maximum).  Bins pair up: with
+            // E_k, O_k from Z_k and Z_(M-k), E_(M-k) = conj E_k, O_(M-k) = conj O_k
+            // and w^(M-k) = -conj w^k, so X_(M-k) = conj(E_k - w^k O_k): one
+            // product t = w^k O_k serves X_k = E + t and X_(M-k).  Pairs k = 0 ..
+            // M/2 cover every bin: k = 0 gives DC (E + O) and Nyquist (E - O), k = M/2
+            // pairs with itself.  NaN: the a2 are >= 0 or NaN, so their sum is NaN
+            // iff one of them is.
+            constexpr int H = C::M / 2;
+            constexpr int JF = H / TPP;   // pair tasks every thread holds
+            double best2 = 0.0, nsum = 0.0;
+#pragma unroll
+            for (int j = 0; j < JF; ++j) {
+                // kk = t + TPP j, M - kk = (TPP - t) + (M - TPP (j + 1)): 64-multiples apart
+                const int kk = t + TPP * j;
+                const double2 zk = Cb[cidx(t) + TPP * j];
+                const double2 zm = Cb[kk == 0 ? 0 : cidx(TPP - t) + (C::M - TPP * (j + 1))];
+                spec_pair_nan(zk, zm, tw[kk], best2, nsum);
+            }
+            {
+                const int kk = t + TPP * JF;   // the rest: kk <= M/2 (one thread at N >= 256)
+                if (kk <= H) spec_pair_nan(Cb[cidx(kk)], Cb[cidx(kk == 0 ? 0 : C::M - kk)], tw[kk], best2, nsum);
+            }
+            int nanf = isnan(nsum);
+            best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 52, wave, lane);
+            nanf = group_tree<WPP, 64>(nanf, OpOr(), (int *)(red + 60), wave, lane);
+            fftv = nanf ? NAN : 0.5 * sqrt(best2);
+        } else {
+            // invalid: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
+            int nanx = 0;
+            for (int i = t; i < N; i += TPP) nanx |= isnan(X[xaddr(i)]);
+            nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 48), wave, lane);
+            fftv = nanx ? NAN : 0.0;
+        }
+        if (t == 0) {   // diag_store, restated: the call changed three of this kernel's forms
+            a.std_o[k] = valid && isfinite(mean) ? sd : 0.0;   // numpy.ma: a non-finite mean is masked -> std 0
+            a.mean_o[k] = valid ? mean : 0.0;
+            a.ptp_o[k] = ptp;
+            a.fft_o[k] = fftv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_diag_cl<N, MODE>: DIAG_EXACT / DIAG_CLOSED diagnostics for N >= 1024 (f32
+// data, no pulse region), chain layout.  Same arithmetic and the same bits as
+// k_diag_p2 (ic.py:206-217, :272-288, :296); what changes is where the data
+// lives:
+// - Thread t of a profile group (L = N/16 threads: one wave at N = 1024) owns
+//   pairwise chain t = (leaf t/8, accumulator t%8), the dispersed-frame samples
+//   j = 128(t/8) + t%8 + 8q, q < 16, and loads them straight from the raw row
+//   (one 64-bit address per profile, immediate offsets 32q).
+// - The template is gathered at i = (j - sh) mod N from T2 = [T, T] (2N f64),
+//   so the wrap costs nothing: one address, immediate offsets 64q.
+// - mean / var / ptp run on the residual in registers (no LDS round trip), and
+//   the var pass stores d = f64(X) - mean, which IS the FFT's input, as f64
+//   into the complex work array in the first stage's gather order, so the FFT
+//   starts without conversions or subtractions.  The work array's input image
+//   is swizzled slot(p) = p ^ (((p >> 6) & 3) << 2): the chain stores (32
+//   lanes x 8 B per half-wave) and the stage-1 gathers (16-B points) are both
+//   bank-conflict free, and all addresses are per-thread bases + immediates.
+// - Profile-uniform conditions (fit status, w0 == 0 / 1) are scalar branches.
+// DIAG_CLOSED first forms the closed-form amplitude over the same chains (the
+// stored order: the products T_i p_i of the lane's samples j, i = (j - sh) mod
+// N, with the template gathered for the residual).
+template <int N, int MODE>
+__global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagArgs a)
+{
+    using C = CLay<N>;
+    constexpr int L = C::L, WPP = C::WPP, M = C::M;
+    constexpr bool closed = MODE == DIAG_CLOSED;
+    constexpr bool stats = MODE == DIAG_STATS;   // X = f32(D_row * w): the rows are the residual
+    constexpr bool twder = WPP > 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const double2 *tw = C::TWG ? a.tw_p2 : (const double2 *)smem;
+    const int lane = threadIdx.x & 63;
+    const int group = WPP == 1 ? (int)(threadIdx.x >> 6) : 0;
+    const int gpb = WPP == 1 ? (int)(blockDim.x >> 6) : 1;
+    const int wave = WPP == 1 ? 0 : (int)(threadIdx.x >> 6);
+    int t = WPP == 1 ? lane : (int)threadIdx.x;
+    if (!C::TWG) {
+        for (int q = threadIdx.x; q < C::TW_LDS; q += blockDim.x) ((double2 *)smem)[q] = a.tw_p2[q];
+        __syncthreads();
+    }
+    unsigned char *gb = smem + (size_t)C::TW_LDS * 16 + (size_t)group * C::GROUP_BYTES;
+    double2 *Cb = (double2 *)gb;
+    double *red = (double *)(gb + C::CBYTES);
+    const unsigned P = (unsigned)a.nsub * (unsigned)a.nchan;
+    const unsigned stride = gridDim.x * gpb;
+    const unsigned nchan = (unsigned)a.nchan;
+    // profiles: all P, or the slots of a list, minus those with skip[k] != 0
+    // (the two passes of the fit's forked diagnostics)
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const unsigned nslot = (unsigned)rl.n();
+    const uint8_t *skip = a.skip;
+    // The group's upcoming slots, 64 at a time: lane j of each wave holds the
+    // profile of slot wb0 + j stride (-1: past the end, or skipped), so the next
+    // profile is a ballot bit away and the list and skip reads are one batch per
+    // 64 profiles, where a dependent pair of reads per profile stalled the
+    // prefetch of the next row (list and skip passes of the fork).
+    unsigned wb0 = 0;
+    int wkk = -1;
+    unsigned long long wmask = 0;
+    auto fill = [&](unsigned b) {
+        wb0 = b;
+        const unsigned sl = b + (unsigned)lane * stride;
+        int kk = -1;
+        if (sl < nslot && sl >= b) {
+            kk = (int)rl.at(sl);
+            if (skip && skip[kk]) kk = -1;
+        }
+        wkk = kk;
+        wmask = __ballot(kk >= 0);
+    };
+    auto take = [&]() -> int {   // the next profile of the group (uniform), -1 when done
+        while (wmask == 0) {
+            const unsigned nb = wb0 + 64u * stride;
+            if (nb >= nslot || nb < wb0) return -1;
+            fill(nb);
+        }
+        const int j = __builtin_ctzll(wmask);
+        wmask &= wmask - 1;
+        return __builtin_amdgcn_readlane(wkk, j);
+    };
+    // a VGPR zero: the per-profile scalars of the next profile are read by
+    // vector loads (counted on vmcnt), not scalar ones, whose lgkmcnt would be
+    // waited on by the FFT's LDS waits
+    int zv;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zv));
+    const int ca = t >> 3, cc = t & 7;
+    const int jb = 128 * ca + cc;   // first sample of the thread's chain
+    // byte offsets in the work array: d of chain sample q at wb[q & 3] + 64 (q & ~3)
+    // (point p = jb/2 + 4q, part cc & 1); stage-1 point t + L r at rb[r & 3] + 16 L r
+    int wb[4], rb[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        wb[m] = 16 * (64 * ca + ((4 * m + (cc >> 1)) ^ (4 * (ca & 3)))) + 8 * (cc & 1);
+        rb[m] = 16 * (t ^ ((((t >> 6) + (L / 64) * m) & 3) << 2));
+    }
+    float pv[16];
+    auto loadrow = [&](unsigned kk) {
+        const float *pn = (stats ? a.D : a.raw) + (size_t)kk * N + jb;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) pv[q] = pn[8 * q];
+    };
+    fill(__builtin_amdgcn_readfirstlane(blockIdx.x * gpb + group));
+    int kq = take();
+    unsigned k = kq >= 0 ? (unsigned)kq : 0u;
+    double nx = 0.0;
+    int nst = 0, nsh = 0;
+    float nw = 0.0f, nb = 0.0f;
+    auto prefetch = [&](unsigned kk) {
+        loadrow(kk);
+        const unsigned kv = kk + (unsigned)zv;
+        if (!closed && !stats) {
+            nx = a.amp[kv];
+            nst = a.info[kv];
+        }
+        if (!stats) {
+            nb = a.base[kv];
+            nsh = a.shift[kk % nchan + (unsigned)zv];
+        }
+        nw = a.w0[kv];
+    };
+    if (kq >= 0) prefetch(k);
+    for (; kq >= 0;) {
+        // multi-wave groups: keep the FFT's LDS addresses inside the loop (hoisted,
+        // they spill at N >= 2048; k_diag_p2); one wave: hoisted, 118 VGPRs
+        if (WPP > 1) asm volatile("" : "+v"(t));
+        double x = ufirst(nx);
+        int st = ufirst(nst);
+        const float w = ufirst(nw);
+        const float bk = nb;
+        const int sh = ufirst(nsh);
+        // template at the dedispersed index of every chain sample
+        double tg[16];
+        if constexpr (!stats) {
+            const double *tb = a.T2 + ((unsigned)(jb - sh) & (unsigned)(N - 1));
+#pragma unroll
+            for (int q = 0; q < 16; ++q) tg[q] = tb[8 * q];
+        }
+        if constexpr (closed) {
+            // a = sum(T*p)/sum(T*T) over the chains of the stored (dispersed)
+            // order: the lane's samples j = jb + 8q with p = f32(raw_j - base),
+            // the dedispersed bin i = (j - sh) mod N, T_i = tg[q] (the
+            // residual's gather): no second read of the row (round 6; before,
+            // the dot ran over the dedispersed chains and gathered raw at
+            // (i + sh) mod N again)
+            double r = tg[0] * (double)(pv[0] - bk);
+#pragma unroll
+            for (int q = 1; q < 16; ++q) {
+                const double pr = tg[q] * (double)(pv[q] - bk);
+                r = r + pr;
+            }
+            double cs[1] = {r};
+            const double dot = 0.0 + chain_total<N, double>(cs, red, wave, lane);
+            const double TT = *a.TT;
+            x = ufirst(TT != 0.0 ? dot / TT : 0.0);
+            st = isfinite(x) ? 1 : 5;
+            if (t == 0) {
+                a.amp[k] = x;
+                a.info[k] = st;
+            }
+        }
+        // residual (ic.py:279-288) of the dispersed-frame sample j, f32 store
+        // (:272), apply_weights (:296): X_j = f32(f32(x T_i - D_i) * w), D_i = f32(raw_j - base0)
+        const bool ok = stats || (st >= 1 && st <= 4);   // fit_ok, restated: the call moved the closed mode's code
+        const bool valid = w != 0.0f;
+        float X[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            if constexpr (stats) {
+                X[q] = pv[q];
+            } else {
+                const float pj = pv[q] - bk;
+                const double e = x * tg[q] - (double)pj;
+                X[q] = (float)e;
+            }
+        }
+        if (w != 1.0f) {   // fractional weights (w * 1 = w exactly: skipped)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) X[q] = X[q] * w;
+        }
+        if (!ok) {   // a bad leastsq status zeroes the residual (ic.py:284-286)
+            asm volatile("");   // a rare branch, not 16 selects on every profile
+#pragma unroll
+            for (int q = 0; q < 16; ++q) X[q] = 0.0f * w;
+        }
+        const unsigned kc = k;   // this profile (the prefetch below moves k on)
+        kq = take();
+        if (kq >= 0) {
+            k = (unsigned)kq;
+            prefetch(k);
+        }
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(false);
+        if (valid) {
+            // mean: f32 chain, then the pairwise tree (ic.py:207)
+            // (this chain arithmetic is restated in rot_stats, ic_rotate.hip: edit both.  A
+            // shared helper changed the operand order of the adds in the machine code)
+            float s = X[0];
+#pragma unroll
+            for (int q = 1; q < 16; ++q) s = s + X[q];
+            float fs[1] = {s};
+            const float s32 = 0.0f + chain_total<N, float>(fs, (float *)(red + 16), wave, lane);
+            mean = (double)s32 / (double)N;
+            // the previous profile's spectrum reads are done before d overwrites the array
+            gsync<WPP>();
+            // var (ic.py:206): f64 pairwise sum of (f64(X) - mean)^2; d -> FFT input
+            double r = 0.0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const double d = (double)X[q] - mean;
+                const double sq = d * d;
+                r = q == 0 ? sq : r + sq;
+                *(double *)(gb + wb[q & 3] + 64 * (q & ~3)) = d;
+            }
+            double rs[1] = {r};
+            const double ss = 0.0 + chain_total<N, double>(rs, red + 24, wave, lane);
+            sd = sqrt(ss / (double)N);
+            // ptp (ic.py:208), NaN-propagating
+            float mx = -INFINITY, mn = INFINITY;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                mx = OpMaxF()(mx, X[q]);
+                mn = OpMinF()(mn, X[q]);
+            }
+            mx = group_tree<WPP, 64>(mx, OpMaxF(), (float *)(red + 32), wave, lane);
+            mn = group_tree<WPP, 64>(mn, OpMinF(), (float *)(red + 36), wave, lane);
+            int nan = 0;
+            if (isnan(s32)) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) nan |= isnan(X[q]);
+                nan = group_tree<WPP, 64>(nan, OpOr(), (int *)(red + 40), wave, lane);
+            }
+            ptp = nan ? (double)NAN : (double)(float)(mx - mn);
+            // rFFT of d (ic.py:210-212): stage 1 (radix 8, no twiddles) from the
+            // swizzled input image, then k_diag_p2's stages
+            gsync<WPP>();
+            double2 v[8];
+#pragma unroll
+            for (int r8 = 0; r8 < 8; ++r8) v[r8] = *(const double2 *)(gb + rb[r8 & 3] + 16 * L * r8);
+            gsync<WPP>();
+            dft_small<8>(v);
+            {
+                const int A = 8 * t + (t & 7);   // cidx(8t + r) = A ^ r
+#pragma unroll
+                for (int r8 = 0; r8 < 8; ++r8) Cb[A ^ r8] = v[r8];
+            }
+            gsync<WPP>();
+            p2_fft<M, L, C::LG, 3, 8, M, float, twder>(Cb, (const float *)nullptr, 0.0, tw, t);
+            // spectrum in conjugate bin pairs (k_diag_p2).  No NaN bookkeeping:
+            // a finite f32 sum s32 means every X is finite, and then every d,
+            // Z and |X_k|^2 is finite (|X_k|^2 < 1e85); a non-finite s32 (a NaN or
+            // Inf sample, or an f32 overflow: d = -Inf) makes some bin NaN in
+            // any FFT order, so numpy's max|rfft| is NaN (ic.py:210-212)
+            constexpr int H = M / 2;
+            constexpr int JF = H / L;
+            double best2 = 0.0;
+            static_assert(JF == 4 && 16 * L == N, "tw[t + L j] = tw[t] exp(-2 pi i j / 16)");
+            const double2 wt = tw[t];
+#pragma unroll
+            for (int j = 0; j < JF; ++j) {
+                const int kk = t + L * j;
+                const double2 zk = Cb[cidx(t) + L * j];
+                const double2 zm = Cb[kk == 0 ? 0 : cidx(L - t) + (M - L * (j + 1))];
+                if (twder) {
+                    // exp(-2 pi i j / 16), j = 0..3
+                    constexpr double c16[4] = {1.0, 0.92387953251128675613, 0.70710678118654752440,
+                                               0.38268343236508977173};
+                    constexpr double s16[4] = {0.0, 0.38268343236508977173, 0.70710678118654752440,
+                                               0.92387953251128675613};
+                    const double2 wj = make_double2(c16[j], -s16[j]);
+                    spec_pair(zk, zm, j == 0 ? wt : cmul_f(wt, wj), best2);
+                } else {
+                    spec_pair(zk, zm, tw[kk], best2);
+                }
+            }
+            spec_self_pair(Cb[cidx(H)], tw[H], best2);   // k = M/2 (one task, on every lane)
+            best2 = group_tree<WPP, 64>(best2, OpMaxF(), red + 44, wave, lane);
+            fftv = isfinite(s32) ? 0.5 * sqrt(best2) : (double)NAN;
+        } else {
+            // invalid: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
+            int nanx = 0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) nanx |= isnan(X[q]);
+            nanx = group_tree<WPP, 64>(nanx, OpOr(), (int *)(red + 52), wave, lane);
+            fftv = nanx ? NAN : 0.0;
+        }
+        if (t == 0) diag_store(a, kc, valid, mean, sd, ptp, fftv);
+    }
+}
+
+// residual cube on request (ic_get_residual): R (dispersed frame, unweighted).
+// D == nullptr (fit_mode 1 keeps no fit cube): the fit-cube row is formed from
+// raw and the w0 baseline as in k_chan_partials mode 3, f32(ded - base).
+__global__ __launch_bounds__(256) void k_residual(const float *__restrict__ D, const float *__restrict__ raw,
+                                                  const float *__restrict__ base, const double *__restrict__ T64,
+                                                  const double *__restrict__ amp, const int32_t *__restrict__ info,
+                                                  const int32_t *__restrict__ shift, size_t P, int nchan, int nbin,
+                                                  int ldD, int dtiled, int pr_on, double pr_factor, int pr_start,
+                                                  int pr_end, float *__restrict__ R)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (size_t k = (size_t)blockIdx.x * 4 + wave; k < P; k += (size_t)gridDim.x * 4) {
+        const int sh = shift[k % nchan];
+        const bool ok = fit_ok(info[k]);
+        const double a = amp[k];
+        const float b = D ? 0.0f : base[k];
+        for (int i = lane; i < nbin; i += 64) {
+            int j = i + sh;
+            if (j >= nbin) j -= nbin;
+            float v = 0.0f;
+            if (ok) {
+                const float p = D ? D[d_ofs(k, i, ldD, dtiled)] : raw[k * nbin + j] - b;
+                v = residual_sample(a, T64[i], p, i, PulseRegion{pr_on != 0, pr_start, pr_end, pr_factor});
+            }
+            R[k * nbin + j] = v;
+        }
+    }
+}
+
+// TT = numpy pairwise sum of T64[i]^2 (fit_mode 1's denominator), one wave
+__global__ __launch_bounds__(64) void k_tnorm(const double *__restrict__ T64, const PwPlan *__restrict__ plan,
+                                              double *__restrict__ TT)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char tsm[];
+    const int lane = threadIdx.x & 63;
+    const double v = wave_pairwise<double>(*plan, [&](int q) { return T64[q] * T64[q]; }, (double *)tsm, lane);
+    if (lane == 0) *TT = v;
+}
+
+// ============================================================ launchers
+
+template <int NN, bool D64>
+static hipError_t launch_p2(hipStream_t st, const DiagArgs &a, size_t P)
+{
+    using C = P2<NN, D64>;
+    const size_t fixed = (size_t)C::TW_LDS * 16;
+    int gpb = C::WPP > 1 ? 1 : 8;
+    while (gpb > 1 && fixed + gpb * (size_t)C::GROUP_BYTES > kLdsBudget) --gpb;
+    const size_t shm = fixed + gpb * (size_t)C::GROUP_BYTES;
+    const unsigned grid = cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap);
+    if (a.mode == DIAG_EXACT)
+        IC_GGL((k_diag_p2<NN, DIAG_EXACT, D64>), dim3(grid), dim3(C::TPP * gpb), shm, st, a);
+    else if (a.mode == DIAG_CLOSED)
+        IC_GGL((k_diag_p2<NN, DIAG_CLOSED, D64>), dim3(grid), dim3(C::TPP * gpb), shm, st, a);
+    else if (a.mode == DIAG_FIT)   // f32 rows either way (launch_diag passes D64 = false)
+        IC_GGL((k_diag_p2<NN, DIAG_FIT, false>), dim3(grid), dim3(C::TPP * gpb), shm, st, a);
+    else   // comprehensive_stats of given rows (f64 data: the fractional-dedispersion loop)
+        IC_GGL((k_diag_p2<NN, DIAG_STATS, D64>), dim3(grid), dim3(C::TPP * gpb), shm, st, a);
+    return hipGetLastError();
+}
+
+template <int NN>
+static hipError_t launch_cl(hipStream_t st, const DiagArgs &a, size_t P)
+{
+    using C = CLay<NN>;
+    const int gpb = C::GPB;
+    const size_t shm = (size_t)C::TW_LDS * 16 + gpb * (size_t)C::GROUP_BYTES;
+    const unsigned grid = cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap);
+    if (a.mode == DIAG_EXACT)
+        IC_GGL((k_diag_cl<NN, DIAG_EXACT>), dim3(grid), dim3(C::L * gpb), shm, st, a);
+    else if (a.mode == DIAG_STATS)
+        IC_GGL((k_diag_cl<NN, DIAG_STATS>), dim3(grid), dim3(C::L * gpb), shm, st, a);
+    else
+        IC_GGL((k_diag_cl<NN, DIAG_CLOSED>), dim3(grid), dim3(C::L * gpb), shm, st, a);
+    return hipGetLastError();
+}
+
+static bool uses_cl(const DiagArgs &a)
+{
+    if (!a.chain || a.data_f64 || !(a.nbin == 1024 || a.nbin == 2048 || a.nbin == 4096)) return false;
+    // STATS: row-major residual rows (the FFT mode's rotated residual; the
+    // pulse region was applied when they were formed)
+    if (a.mode == DIAG_STATS) return a.D && a.ldD == a.nbin && !a.dtiled;
+    return (a.mode == DIAG_EXACT || a.mode == DIAG_CLOSED) && a.T2 && a.raw && a.base && !a.pr_on;
+}
+
+// profile lists / skips: k_diag_cl, and k_diag_p2 in the exact mode and on
+// given rows (the FFT mode's rotated residuals)
+bool diag_list_supported(const DiagArgs &a)
+{
+    const int n = a.nbin;
+    return uses_cl(a) ||
+           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && p2_supported(n));
+}
+
+// the generic k_diag's LDS layout as the host sizes it: nleaf/nops upper bound
+// from nbin (leaves >= 64 samples except tiny n)
+static DiagLayout generic_layout(int nbin)
+{
+    const int nleaf_ub = nbin <= 128 ? 1 : (nbin / 64 + 1);
+    return diag_layout(nbin, nleaf_ub, nleaf_ub);
+}
+
+hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
+{
+    const int nbin = a.nbin;
+    const size_t P = (size_t)a.nsub * a.nchan;
+    if (P == 0) return hipSuccess;
+    if (a.mode == DIAG_CLOSED ? (!a.raw || !a.base || !a.TT || !a.amp || !a.info)
+                              : (!a.D || a.ldD < nbin || (a.mode != DIAG_STATS && (!a.amp || !a.info)) ||
+                                 (a.mode == DIAG_FIT && !a.TT)))
+        return hipErrorInvalidValue;
+    // the chain-layout kernel: exact / closed modes from the raw cube, f32 data, no pulse region
+    if (uses_cl(a)) {
+        if (nbin == 1024) return launch_cl<1024>(st, a, P);
+        if (nbin == 2048) return launch_cl<2048>(st, a, P);
+        if (nbin == 4096) return launch_cl<4096>(st, a, P);
+    }
+    if ((a.list || a.skip) && !diag_list_supported(a)) return hipErrorInvalidValue;
+#define IC_P2(NN)                                                                                  \
+    if (nbin == NN) {                                                                              \
+        if (a.data_f64 && a.mode != DIAG_FIT) return launch_p2<NN, true>(st, a, P);                \
+        return launch_p2<NN, false>(st, a, P);                                                     \
+    }
+    IC_P2_SIZES(IC_P2)
+#undef IC_P2
+    if (a.mode == DIAG_FIT) return hipErrorInvalidValue;   // power-of-two nbin only
+    const DiagLayout lay = generic_layout(nbin);
+    const size_t fixed = (size_t)lay.ntw * 16;
+    int wpb = 4;
+    while (wpb > 1 && fixed + wpb * lay.per_wave > kLdsBudget) --wpb;
+    const size_t shm = fixed + wpb * lay.per_wave;
+    if (shm > kLdsBlockMax) return hipErrorInvalidValue;
+    const unsigned grid = cap_grid(std::min<size_t>((P + wpb - 1) / wpb, 8192), a.grid_cap);
+    IC_GGL(k_diag, dim3(grid), dim3(64 * wpb), shm, st, a);
+    return hipGetLastError();
+}
+
+size_t diag_lds_bytes(int nbin)
+{
+    if (p2_supported(nbin)) return 0;
+    const DiagLayout lay = generic_layout(nbin);
+    return (size_t)lay.ntw * 16 + lay.per_wave;
+}
+
+hipError_t launch_tnorm(hipStream_t st, const double *T64, const PwPlan *plan, int nleaf_ub, double *TT)
+{
+    const size_t shm = (size_t)(nleaf_ub * 9 + nleaf_ub + 8) * 8;
+    IC_GGL(k_tnorm, dim3(1), dim3(64), shm, st, T64, plan, TT);
+    return hipGetLastError();
+}
+
+hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, const float *base, const double *T64,
+                           const double *amp, const int32_t *info, const int32_t *shift, int nsub, int nchan,
+                           int nbin, int ldD, int dtiled, int pr_on, double pr_factor, int pr_start, int pr_end,
+                           float *R, int grid_cap)
+{
+    const size_t P = (size_t)nsub * nchan;
+    if (!D && (!raw || !base)) return hipErrorInvalidValue;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 4), 16384), grid_cap);
+    IC_GGL(k_residual, dim3(grid), dim3(256), 0, st, D, raw, base, T64, amp, info, shift, P, nchan, nbin,
+                       ldD, dtiled, pr_on, pr_factor, pr_start, pr_end, R);
+    return hipGetLastError();
+}
+
+}  // namespace icgpu

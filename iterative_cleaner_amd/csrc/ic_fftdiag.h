@@ -1,4 +1,4 @@
-// ic_fftdiag.h -- device-only code that the diagnostics (ic_kernels.hip:
+// ic_fftdiag.h -- device-only code that the diagnostics (ic_diag.hip:
 // k_diag, k_diag_p2, k_diag_cl) and the rotation (ic_rotate.hip: k_rotate,
 // whose fused statistics rot_stats are k_diag_cl's, and k_rotate_mr) share:
 // the f64 FFT pieces, the P2 / CLay profile-group layouts with their LDS

@@ -1,6 +1,7 @@
 // ic_internal.h — shared declarations between the host session (ic_session.hip)
-// and the gfx950 kernel units (ic_kernels.hip, ic_rotate.hip, ic_linestats.hip,
-// ic_shards.hip).  Not part of the public C-ABI.
+// and the gfx950 kernel units (ic_template.hip, ic_codec.hip, ic_fit.hip,
+// ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip).  Not part of the
+// public C-ABI.
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -34,8 +35,11 @@ extern thread_local PendingTiming g_timing;
     } while (0)
 
 constexpr int kSuperBlock = 256;    // canonical channel super-block (archive.py SUPER_BLOCK)
+inline int super_blocks(int nchan) { return (nchan + kSuperBlock - 1) / kSuperBlock; }
 constexpr int kMaxLeaves = 256;     // pairwise-sum leaves (nbin <= 32768)
 constexpr int kFitTile = 32;        // bins per k_fit_pass LDS tile (fit cube row padding)
+constexpr size_t kLdsBlockMax = 160 * 1024;   // dynamic LDS one block may ask for: all of a gfx950 CU's
+constexpr size_t kLdsBudget = 150 * 1024;     // launchers shrink groups per block to fit this: the static LDS (k_diag's PwPlan) comes on top
 
 // Tiled fit cube (dtiled): profiles in groups of 64 (one k_fit_pass wave),
 // each group stored as ldD/32 tiles of [64 profiles][32 bins] (8 KiB), so a
@@ -154,8 +158,10 @@ inline unsigned cap_grid(size_t grid, int grid_cap)
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 inline int bin_block(int nbin) { return nbin >= 256 ? 256 : ((nbin + 63) / 64) * 64; }
 
-// ---- launch wrappers (each below its kernels: ic_kernels.hip, ic_rotate.hip,
-// ic_linestats.hip, ic_shards.hip); all asynchronous on `st` ----
+// ---- launch wrappers (each below its kernels, in the unit of its stage); all
+// asynchronous on `st` ----
+// valid[k] = (w0[k] != 0), W[k] = hist0[k] = w0[k]: once per run (k_valid)
+hipError_t launch_valid(hipStream_t st, const float *w0, uint8_t *valid, float *W, float *hist0, size_t P);
 // mode 0: part = sum W*ded; 1: part2 = sum W*f32(ded-base) + wpart; 2: both;
 // 3: mode 1 + the fit cube D[k][i] = f32(ded-base) (row stride ldD).
 // flags: only subints with flags[s] != 0 (nullptr: all)

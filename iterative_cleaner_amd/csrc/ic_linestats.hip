@@ -605,7 +605,7 @@ hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
             if (W == 4 || W == 8) {
                 const int seg = (((len + W - 1) / W) + 63) & ~63;
                 const size_t gshm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8;
-                if (gshm <= 160 * 1024) {
+                if (gshm <= kLdsBlockMax) {
                     if (W == 4)
                         IC_GGL(k_linestats_grp<4>, dim3(lines), dim3(256), gshm, st, a, rows, len);
                     else
@@ -620,7 +620,7 @@ hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
         int wpb = 4;
         while (wpb > 1 && (size_t)wpb * per_wave > 64 * 1024) --wpb;
         const size_t shm = (size_t)wpb * per_wave;
-        if (shm > 160 * 1024) return hipErrorInvalidValue;
+        if (shm > kLdsBlockMax) return hipErrorInvalidValue;
         IC_GGL(k_linestats, dim3(cdiv(lines, wpb)), dim3(64 * wpb), shm, st, a, rows, len, wpb,
                            per_wave);
         const hipError_t e = hipGetLastError();

@@ -1,6 +1,7 @@
 // ic_rotate.hip -- fractional dedispersion: the FFT phase rotation at
 // power-of-two (k_rotate, with the fused statistics rot_stats) and mixed-radix
-// (k_rotate_mr) profile lengths, the identity rotation, and their launchers.
+// (k_rotate_mr) profile lengths, the identity rotation, the channel phasor
+// table they read (k_phasor_table), and their launchers.
 #include <algorithm>
 #include <float.h>
 #include <math.h>
@@ -443,7 +444,7 @@ __device__ __forceinline__ void rot_stats(const RotateArgs &a, size_t p, double2
 #pragma unroll
             for (int q = 0; q < 16; ++q) X[q] = xc[8 * q];
         }
-        // (k_diag_cl's chain arithmetic, ic_kernels.hip, restated: edit both)
+        // (k_diag_cl's chain arithmetic, ic_diag.hip, restated: edit both)
         float s = X[0];
 #pragma unroll
         for (int q = 1; q < 16; ++q) s = s + X[q];
@@ -1069,7 +1070,36 @@ __global__ __launch_bounds__(256) void k_rotate_mr(RotateArgs a, unsigned long l
     }
 }
 
+// The channel phasor table of the FFT dedispersion (RotateArgs.ph) from the
+// channels' delays on the device: ph[c][k] = f32(ic_phasor(k, delay[c], nbin)),
+// k <= nbin/2.  One element per thread, k fastest (a wave stores 512
+// contiguous bytes), grid-stride.  ic_phasor is the function the host's table
+// (make_phasors) and k_rotate's per-profile path evaluate; with
+// -ffp-contract=off its separately rounded f64 operations give the same bits
+// here.  n < 2^31 (launch_phasor_table).
+__global__ __launch_bounds__(256) void k_phasor_table(const double *__restrict__ delay, float2 *__restrict__ ph,
+                                                      uint32_t n, uint32_t row, int nbin)
+{
+    const uint32_t step = gridDim.x * blockDim.x;
+    // i + step cannot wrap: n < 2^31 and step <= 65536 * 256
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const uint32_t c = i / row, k = i - c * row;
+        const double2 v = ic_phasor((int)k, delay[c], nbin);
+        ph[i] = make_float2((float)v.x, (float)v.y);
+    }
+}
+
 // ============================================================ launchers
+
+hipError_t launch_phasor_table(hipStream_t st, const double *delay, int nchan, int nbin, float *ph, int grid_cap)
+{
+    if (nchan < 1 || nbin < 2 || !delay || !ph) return hipErrorInvalidValue;
+    const size_t row = (size_t)nbin / 2 + 1, n = (size_t)nchan * row;
+    if (n >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(n, 256), 65536), grid_cap);
+    IC_GGL(k_phasor_table, dim3(grid), dim3(256), 0, st, delay, (float2 *)ph, (uint32_t)n, (uint32_t)row, nbin);
+    return hipGetLastError();
+}
 
 bool rotate_supported(int nbin) { return p2_supported(nbin) || mr_supported(nbin); }
 

@@ -534,17 +534,6 @@ void free_all(Session *s)
     if (s->stream) (void)hipStreamDestroy(s->stream);
 }
 
-__global__ void k_valid(const float *w0, uint8_t *valid, float *W, float *hist0, size_t P)
-{
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < P) {
-        const float w = w0[k];
-        valid[k] = (w != 0.0f);
-        W[k] = w;
-        hist0[k] = w;
-    }
-}
-
 #define CM(S, call, what)                                                                         \
     do {                                                                                          \
         Timed t_{K_EXCHANGE, nullptr, nullptr};                                                   \
@@ -590,7 +579,7 @@ const char *shard_layout(int nsub, int nchan, int world, int32_t *chan0, int32_t
 {
     if (world < 1 || (world & (world - 1))) return "world size must be a power of two";
     if (world > kMaxShards) return "world size too large";
-    const int nsb = (nchan + kSuperBlock - 1) / kSuperBlock;
+    const int nsb = super_blocks(nchan);
     if (nsb < world) return "fewer 256-channel super-blocks than shards";
     int depth = 0;
     while ((1 << depth) < world) ++depth;
@@ -742,9 +731,7 @@ void with_stats(Session *s, RotateArgs &a)
 int prepare(Session *s)
 {
     const int nsub = s->p.nsub, nchan = s->nchan, nbin = s->p.nbin;
-    IC_GGL(k_valid, dim3((unsigned)((s->P + 255) / 256)), dim3(256), 0, s->stream, s->w0,
-                       s->valid, s->W, s->hist, s->P);
-    CK(hipGetLastError());
+    CK(launch_valid(s->stream, s->w0, s->valid, s->W, s->hist, s->P));
     if (s->comm) {
         LAUNCH(s, K_SHARD_PACK,
                launch_pack_rows(s->stream, s->geom, nchan, nullptr, nullptr, nullptr, nullptr, s->valid, s->xd_send,
@@ -1089,10 +1076,10 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
         return fail(IC_EINVAL,
                     "fit_mode IC_FIT_CLOSED with fractional dedispersion needs a power-of-two nbin in %d..%d; "
                     "a mixed-radix nbin takes IC_FIT_EXACT (nbin=%d)", kP2Min, kP2Max, p.nbin);
-    if (diag_lds_bytes(p.nbin) > 160 * 1024)
+    if (diag_lds_bytes(p.nbin) > kLdsBlockMax)
         return fail(IC_EINVAL, "nbin=%d needs %zu bytes of LDS for the diagnostics (> 160 KiB)", p.nbin,
                     diag_lds_bytes(p.nbin));
-    if (window_lds_bytes(p.nbin) > 160 * 1024)
+    if (window_lds_bytes(p.nbin) > kLdsBlockMax)
         return fail(IC_EINVAL, "nbin=%d needs %zu bytes of LDS for the baseline window (> 160 KiB)", p.nbin,
                     window_lds_bytes(p.nbin));
     if (world < 1 || rank < 0 || rank >= world) return fail(IC_EINVAL, "bad rank %d / world %d", rank, world);
@@ -1109,7 +1096,7 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     s->nchan = cr[2 * rank + 1] - cr[2 * rank];
     s->P = (size_t)p.nsub * s->nchan;
     s->N = s->P * (size_t)p.nbin;
-    s->nsb = (s->nchan + kSuperBlock - 1) / kSuperBlock;
+    s->nsb = super_blocks(s->nchan);
     s->plan_sb = make_sb_plan(s->nsb);
     s->plan_top = make_sb_plan(world);
     s->geom.world = world;
@@ -2399,7 +2386,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     if (rowstat_minlen < 1) return fail(IC_EINVAL, "rowstat_minlen=%d < 1", rowstat_minlen);
     if (nsub <= 0 || nchan <= 0 || nbin <= 0 || nsub > 16384 || nchan > 16384 || nbin > 32768)
         return fail(IC_EINVAL, "bad shape nsub=%d nchan=%d nbin=%d", nsub, nchan, nbin);
-    if (diag_lds_bytes(nbin) > 160 * 1024) return fail(IC_EINVAL, "nbin=%d unsupported", nbin);
+    if (diag_lds_bytes(nbin) > kLdsBlockMax) return fail(IC_EINVAL, "nbin=%d unsupported", nbin);
     if (int rc = select_device(device)) return rc;
     const size_t P = (size_t)nsub * nchan, N = P * (size_t)nbin;
     PwPlan plan;
@@ -2430,8 +2417,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     if (!tw2.empty()) CK(hipMemcpyAsync(dtw2, tw2.data(), 16 * tw2.size(), hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dplan, &plan, sizeof plan, hipMemcpyHostToDevice, st));
     CK(hipMemsetAsync(cnt, 0, 4 * 8, st));
-    IC_GGL(k_valid, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, w0, valid, W, hist, P);
-    CK(hipGetLastError());
+    CK(launch_valid(st, w0, valid, W, hist, P));
     DiagArgs a{};
     a.mode = DIAG_STATS;
     a.D = D;

@@ -1,5 +1,6 @@
 // ic_wave.h -- device-only wave primitives, included by every kernel unit
-// (ic_kernels.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip): the
+// (ic_template.hip, ic_codec.hip, ic_fit.hip, ic_diag.hip, ic_rotate.hip,
+// ic_linestats.hip, ic_shards.hip): the
 // wave-level LDS ordering, the DPP / readlane trees and their functors, the
 // round list of the exact fit (read by the fit, the diagnostics and the
 // rotation), the LDS address cast and the 4-float vector type of the 16-byte

@@ -1,7 +1,7 @@
 """Per-category instruction counts of one kernel in the gfx950 assembly
 (`make -C iterative_cleaner_amd/csrc asm` -> one .s per kernel unit; --asm
-picks the unit that holds the kernel: ic_kernels.s (template, codec, fit,
-diagnostics; the default), ic_rotate.s, ic_linestats.s or ic_shards.s).
+picks the unit that holds the kernel: ic_diag.s (the default), ic_template.s,
+ic_codec.s, ic_fit.s, ic_rotate.s, ic_linestats.s or ic_shards.s).
 
     python tools/isa_breakdown.py KERNEL_SUBSTRING [--asm PATH] [--blocks]
 
@@ -84,7 +84,7 @@ def parse(asm: str, kernel: str):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("kernel")
-    ap.add_argument("--asm", default="iterative_cleaner_amd/csrc/ic_kernels.s")
+    ap.add_argument("--asm", default="iterative_cleaner_amd/csrc/ic_diag.s")
     ap.add_argument("--blocks", action="store_true")
     ap.add_argument("--path", default="", help="comma-separated block label suffixes to sum")
     a = ap.parse_args()

@@ -1,8 +1,12 @@
 """Is every function of one gfx950 assembly the same in another?
 
-    python tools/isa_same.py --old OLD/ic_kernels.s --new NEW/ic_kernels.s [NEW/ic_other_unit.s ...]
+    python tools/isa_same.py --old OLD/*.s --new NEW/*.s [--rename OLD_SYMBOL=NEW_SYMBOL ...]
 
-Both sides come from `make -C iterative_cleaner_amd/csrc asm` (of two trees).
+Both sides come from `make -C iterative_cleaner_amd/csrc asm` (of two trees);
+either side may be any number of units, so code may move between files (a
+kernel of the host file: `make ic_session.s`).  --rename compares a symbol of
+the old side under another name (a kernel that left an anonymous namespace):
+the name is replaced in its own text, nothing else about it is excused.
 Each side is split by function symbol (kernels and non-inlined device
 functions); comments and .loc / .file / .cfi lines are dropped and the function
 index in .LBB<n>_ / .Ltmp<n> / .Lfunc_end<n> labels is normalised, since it
@@ -53,8 +57,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args()
     (old, otw), (new, ntw) = functions(a.old), functions(a.new)
+    for was, now in (r.split("=", 1) for r in a.rename):
+        if was not in old or now in old:
+            sys.exit("--rename %s=%s: %s" % (was, now, "not on the old side" if was not in old else "new name taken"))
+        body, desc = old.pop(was)
+        old[now] = ([s.replace(was, now) for s in body], desc)
+        if was in otw:
+            otw.add(now)
     bad = 0
     for sym in sorted(set(old) | set(new)):
         kind = "kernel" if (old.get(sym) or new.get(sym))[1] else "function"

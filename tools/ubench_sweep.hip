@@ -2,7 +2,7 @@
 // (f = RN(RN(x t) - p), J = RN(d / h) by the four-op division, sum f^2 and J^2
 // in sample order: FastBody<true, false>'s arithmetic) of every profile of a
 // C2-sized fit cube (1 152 000 profiles x 1024 bins, 4.7 GB), one wave per 64
-// profiles, 16-bin LDS-DMA tiles double-buffered as in ic_kernels.hip.
+// profiles, 16-bin LDS-DMA tiles double-buffered as in ic_fit.hip.
 // Variants (times per full round, hipEvents, best of 5):
 //   dma     the sweep's data movement alone (tiles read from LDS, xor-folded)
 //   alu     the arithmetic alone on LDS tiles that are never refilled

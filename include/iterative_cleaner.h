@@ -115,8 +115,8 @@ typedef struct {
  *                    the prime factors 2, 3 and 5 (72, 96, 120, 200, 1000, 1200,
  *                    1536, 2000, 3000, 4000, ...: IC_FIT_EXACT only, f32 or f64
  *                    data, either kind of delays; the statistics of these
- *                    lengths run in the generic diagnostics kernel, whose
- *                    direct DFT dominates the clean).  Any other length, and
+ *                    lengths run in a mixed-radix diagnostics kernel of their
+ *                    own, in both dedispersion modes).  Any other length, and
  *                    IC_FIT_CLOSED at a mixed-radix length, is refused with
  *                    IC_EINVAL by ic_session_create.  The shift arrays of the
  *                    uploads are then unused (pass zeros). */

@@ -14,6 +14,7 @@
 //                    nbin, a wave per profile
 //   k_diag_p2        the same for the power-of-two nbin (IC_P2_SIZES)
 //   k_diag_cl        the chain layout at nbin 1024 / 2048 / 4096
+//   k_diag_mr        the same for the mixed-radix nbin (mr_supported)
 //   k_residual       the residual cube on request (ic_get_residual)
 //   k_tnorm          sum(T*T), fit_mode 1's denominator
 #include <algorithm>
@@ -996,6 +997,370 @@ __global__ __launch_bounds__(CLay<N>::L * CLay<N>::GPB, 4) void k_diag_cl(DiagAr
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_diag_mr: k_diag's diagnostics for the mixed-radix lengths (mr_supported:
+// n = 2M, M = 2^a 3^b 5^c, n a multiple of 8, 64 .. 4096), n a runtime value.
+// A profile group of W = ceil(n / 1024) waves cleans one profile: MW = false,
+// one wave per profile and independent waves in a block that share the f64
+// twiddle table in LDS; MW = true, the block is one group of 2 .. 4 waves and
+// the table is read through L1/L2 (k_diag_p2's two forms).  PPT: complex points
+// a thread holds (M <= 64 W PPT), so a thread has 2 PPT samples of the row.
+// Per group the LDS holds one work array: the X image (f32, or f64 for f64
+// data) that the statistics read, then, in place, the M complex points of the
+// rFFT at pad(q) = q + q/8 (a radix-R first stage scatters at a stride of R
+// points: unpadded, the lanes of a 16-byte store share 2 or 4 bank groups);
+// every input of a stage is in registers before the group writes.  DIAG_CLOSED
+// adds the f32 fit-cube row.
+// mean / std / ptp / amp: k_diag's arithmetic, bit for bit: the numpy pairwise
+// order of the PwPlan (wave_pairwise's chains and leaf sums, spread over the
+// group), whose post-order adds run in registers: every MR length has at most
+// 32 leaves, so slot s of the plan lives in lane s of the group's first wave
+// and an add is two lane reads.  fftmax: Stockham stages in mr_plan's order
+// (FMA allowed, as in k_diag_p2), then the conjugate-pair step (spec_pair_nan;
+// k = 0 is the DC / Nyquist pair, k = M/2 pairs with itself).  Nothing depends
+// on the launch: a profile's four values are the same bits from a full pass, a
+// list, a skip pass or any grid.
+struct MrLayout {
+    size_t tw_bytes, plan_off, groups_off;       // block: twiddles (MW = false), leaf table, groups
+    size_t p_off, acc_off, red_off, per_group;   // group: work array at 0, closed-mode row, pairwise, partials
+};
+
+__host__ __device__ inline MrLayout mr_layout(int n, bool mw, bool d64, bool closed)
+{
+    MrLayout L;
+    const int M = n / 2, nlub = n / 64 + 1;   // leaves hold >= 64 samples
+    L.tw_bytes = mw ? 0 : (size_t)n * 16;
+    L.plan_off = L.tw_bytes;
+    L.groups_off = L.plan_off + (((size_t)nlub * 8 + 15) & ~(size_t)15);
+    const size_t cb = (size_t)(M + M / 8 + 1) * 16, xb = (size_t)n * (d64 ? 8 : 4);
+    const size_t work = ((cb > xb ? cb : xb) + 15) & ~(size_t)15;
+    L.p_off = work;
+    L.acc_off = L.p_off + (closed ? (((size_t)n * 4 + 15) & ~(size_t)15) : 0);
+    L.red_off = L.acc_off + (size_t)nlub * 64;   // 8 chain sums of 8 B per leaf
+    L.per_group = L.red_off + 32 * 8;
+    return L;
+}
+
+__device__ __forceinline__ int mr_pad(int q) { return q + (q >> 3); }
+
+// the PwPlan as the kernel keeps it: leaf starts / lengths in LDS, the adds
+// packed op_a | op_b << 16 in lane o of every wave
+struct MrPlan {
+    const int32_t *ls, *ll;
+    int nl, nops, root, opv;
+};
+
+// wave_pairwise over a group of tpp threads (t: thread of the group): the same
+// chains, leaf sums and post-order adds, so the same bits.  acc: 8 nl slots of
+// Tp; res: one slot (MW).  Leaves of an MR length hold >= 8 samples.
+template <bool MW, typename Tp, typename Get>
+__device__ __forceinline__ Tp mr_pairwise(const MrPlan &pl, Get get, Tp *acc, Tp *res, int t, int tpp)
+{
+    const int nl = pl.nl;
+    for (int task = t; task < nl * 8; task += tpp) {
+        const int Lf = task >> 3, j = task & 7;
+        const int st = pl.ls[Lf], len = pl.ll[Lf];
+        const int main = len - len % 8;
+        Tp r = get(st + j);
+        for (int q = 8; q < main; q += 8) r = r + get(st + q + j);
+        acc[task] = r;
+    }
+    gsync<MW ? 2 : 1>();
+    Tp v = (Tp)0;
+    if (t < nl) {
+        const int st = pl.ls[t], len = pl.ll[t];
+        const Tp *r = acc + t * 8;
+        const Tp a01 = r[0] + r[1], a23 = r[2] + r[3], a45 = r[4] + r[5], a67 = r[6] + r[7];
+        const Tp lo = a01 + a23, hi = a45 + a67;
+        v = lo + hi;
+        for (int q = len - len % 8; q < len; ++q) v = v + get(st + q);
+    }
+    Tp out = (Tp)0;
+    if (!MW || t < 64) {   // slot s in lane s: slot[nl + o] = slot[op_a[o]] + slot[op_b[o]]
+        for (int o = 0; o < pl.nops; ++o) {
+            const int ab = __builtin_amdgcn_readlane(pl.opv, o);
+            const Tp s = lane_read(v, ab & 0xffff) + lane_read(v, ab >> 16);
+            if (t == nl + o) v = s;
+        }
+        out = (Tp)0 + lane_read(v, pl.root);
+    }
+    if constexpr (MW) {
+        if (t == 0) res[0] = out;
+        __syncthreads();
+        out = res[0];
+    }
+    return out;
+}
+
+// group-uniform reduction of a per-thread value (max / min / or: any order)
+template <bool MW, typename T, typename Op>
+__device__ __forceinline__ T mr_tree(T v, Op op, T *red, int t, int tpp)
+{
+    const T w = wave_tree<64>(v, op);
+    if constexpr (MW) {
+        if ((t & 63) == 0) red[t >> 6] = w;
+        __syncthreads();
+        T r = red[0];
+        for (int i = 1; i < (tpp >> 6); ++i) r = op(r, red[i]);
+        __syncthreads();
+        return r;
+    } else {
+        return w;
+    }
+}
+
+// One Stockham stage of radix R and span ns (the product of the earlier
+// radices) of the group's FFT_M, in place: butterfly j < G = M/R reads point
+// j + q G, multiplies by tw[q k step] (k = j mod ns by a multiply with
+// ceil(2^32 / ns), step = n/(R ns); not in the first stage) and writes DFT_R's
+// y_p to point (j - k) R + k + p ns.  FIRST: the points are the pairs of the
+// real row X minus mu.
+template <int R, bool FIRST, int PPT, bool MW, typename XT>
+__device__ __forceinline__ void mr_diag_stage(double2 *C, const XT *X, double mu, const double2 *tw, int M, int step,
+                                              int ns, int t, int tpp)
+{
+    constexpr int BPT = (PPT + R - 1) / R;   // butterflies a thread holds
+    const int G = M / R;
+    const unsigned magic = ns > 1 ? 0xffffffffu / (unsigned)ns + 1u : 0u;
+    double2 v[BPT][R];
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const int j = t + tpp * u;
+        if (j < G) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int pt = j + q * G;
+                if constexpr (FIRST) {
+                    if constexpr (sizeof(XT) == 8) {
+                        const double2 xv = *(const double2 *)(X + 2 * pt);
+                        v[u][q] = make_double2(xv.x - mu, xv.y - mu);
+                    } else {
+                        const float2 xv = *(const float2 *)(X + 2 * pt);
+                        v[u][q] = make_double2((double)xv.x - mu, (double)xv.y - mu);
+                    }
+                } else {
+                    v[u][q] = C[mr_pad(pt)];
+                }
+            }
+        }
+    }
+    gsync<MW ? 2 : 1>();
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const int j = t + tpp * u;
+        if (j < G) {
+            const int k = ns > 1 ? j - (int)__umulhi((unsigned)j, magic) * ns : 0;
+            if (!FIRST) {
+                double2 w[R];
+#pragma unroll
+                for (int q = 1; q < R; ++q) w[q] = tw[q * k * step];
+#pragma unroll
+                for (int q = 1; q < R; ++q) v[u][q] = cmul_f(v[u][q], w[q]);
+            }
+            dft_small<R>(v[u]);
+            const int o = (j - k) * R + k;
+#pragma unroll
+            for (int p = 0; p < R; ++p) C[mr_pad(o + p * ns)] = v[u][p];
+        }
+    }
+    gsync<MW ? 2 : 1>();
+}
+
+template <int PPT, bool MW, bool D64>
+__global__ __launch_bounds__(MW ? 256 : 512, PPT > 2 ? 3 : 4) void k_diag_mr(DiagArgs a, unsigned long long radices, int nst)
+{
+    using XT = typename std::conditional<D64, double, float>::type;
+    constexpr int SPT = 2 * PPT;   // samples of the row a thread holds
+    extern __shared__ __attribute__((aligned(16))) unsigned char mr_sm[];
+    const int n = a.nbin, M = n >> 1, H = M >> 1;
+    const int mode = a.mode;
+    const int lane = threadIdx.x & 63;
+    const int tpp = MW ? (int)blockDim.x : 64;
+    int t = MW ? (int)threadIdx.x : lane;
+    const int group = MW ? 0 : (int)(threadIdx.x >> 6);
+    const int gpb = MW ? 1 : (int)(blockDim.x >> 6);
+    const MrLayout lay = mr_layout(n, MW, D64, mode == DIAG_CLOSED);
+    const double2 *tw = MW ? a.tw : (const double2 *)mr_sm;
+    MrPlan pl;
+    {
+        int32_t *ls = (int32_t *)(mr_sm + lay.plan_off);
+        const int nl = a.plan->nleaf;
+        int32_t *ll = ls + nl;
+        if (!MW)
+            for (int q = threadIdx.x; q < n; q += blockDim.x) ((double2 *)mr_sm)[q] = a.tw[q];
+        for (int q = threadIdx.x; q < nl; q += blockDim.x) {
+            ls[q] = a.plan->leaf_start[q];
+            ll[q] = a.plan->leaf_len[q];
+        }
+        pl.ls = ls;
+        pl.ll = ll;
+        pl.nl = nl;
+        pl.nops = a.plan->nops;
+        pl.root = a.plan->root;
+        pl.opv = lane < pl.nops ? (a.plan->op_a[lane] | (a.plan->op_b[lane] << 16)) : 0;
+        __syncthreads();
+    }
+    unsigned char *gb = mr_sm + lay.groups_off + (size_t)group * lay.per_group;
+    XT *X = (XT *)gb;
+    double2 *C = (double2 *)gb;   // takes X's place once the first stage has read it
+    float *Pr = (float *)(gb + lay.p_off);
+    double *acc = (double *)(gb + lay.acc_off);
+    double *red = (double *)(gb + lay.red_off);
+    const unsigned P = (unsigned)a.nsub * (unsigned)a.nchan;
+    const unsigned stride = gridDim.x * gpb;
+    const double *T64 = a.T64;
+    // profiles: all P, or the slots of a list, minus those with skip[k] != 0
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const unsigned nslot = (unsigned)rl.n();
+    const uint8_t *skip = a.skip;
+    for (unsigned slot = blockIdx.x * gpb + group; slot < nslot; slot += stride) {
+        const unsigned k = (unsigned)rl.at(slot);
+        if (skip && skip[k]) continue;   // group-uniform
+        // opaque to the optimiser: hoisting the stages' LDS addresses, which
+        // derive from t, out of the loop costs ~100 VGPRs (k_diag_p2)
+        asm volatile("" : "+v"(t));
+        const float w = a.w0[k];
+        const bool valid = (w != 0.0f);
+        const int sh = mode == DIAG_STATS ? 0 : a.shift[k % (unsigned)a.nchan];
+        const bool tr = a.dtiled && mode == DIAG_EXACT;   // the tiled fit cube (dt_ofs)
+        // every global load of the row in flight at once: CLOSED the raw row
+        // (dispersed order j), otherwise the fit cube / given row (order i)
+        float pv[SPT];
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const int i = t + tpp * u;
+            pv[u] = 0.0f;
+            if (i < n) {
+                if (mode == DIAG_CLOSED) pv[u] = a.raw[(size_t)k * n + i];
+                else pv[u] = a.D[d_ofs(k, i, a.ldD, tr)];
+            }
+        }
+        double x = 0.0;
+        int stt = 0;
+        gsync<MW ? 2 : 1>();   // the previous profile's LDS reads are done
+        if (mode == DIAG_CLOSED) {
+            // the fit-cube row f32(ded - base0), dedispersed order, then the
+            // closed-form amplitude from numpy pairwise sums over the stored
+            // (dispersed) order j: bin i = (j - sh) mod n
+            const float b = a.base[k];
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                const int j = t + tpp * u;
+                if (j < n) {
+                    int i = j - sh;
+                    if (i < 0) i += n;
+                    Pr[i] = pv[u] - b;
+                }
+            }
+            gsync<MW ? 2 : 1>();
+            const double dot = mr_pairwise<MW, double>(pl, [&](int q) {
+                int i = q - sh;
+                if (i < 0) i += n;
+                return T64[i] * (double)Pr[i];
+            }, acc, red, t, tpp);
+            const double TT = *a.TT;
+            x = TT != 0.0 ? dot / TT : 0.0;
+            stt = isfinite(x) ? 1 : 5;
+            if (t == 0) {
+                a.amp[k] = x;
+                a.info[k] = stt;
+            }
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                const int i = t + tpp * u;
+                if (i < n) pv[u] = Pr[i];
+            }
+        } else if (mode == DIAG_EXACT) {
+            x = a.amp[k];
+            stt = a.info[k];
+        }
+        const bool ok = fit_ok(stt);
+        // residual -> X (dispersed frame): X[j] = f32(f32(r[i]) * w), j = (i + sh) mod n
+        // (f64(f32(r[i])) * f64(w) for f64 data); the thread keeps its values for the ptp
+        XT xv[SPT];
+#pragma unroll
+        for (int u = 0; u < SPT; ++u) {
+            const int i = t + tpp * u;
+            xv[u] = (XT)0;
+            if (i < n) {
+                float R = 0.0f;
+                if (mode == DIAG_STATS) R = pv[u];
+                else if (ok) R = residual_sample(x, T64[i], pv[u], i, a);
+                int j = i + sh;
+                if (j >= n) j -= n;
+                if constexpr (D64) xv[u] = (double)R * (double)w;
+                else xv[u] = R * w;
+                X[j] = xv[u];
+            }
+        }
+        gsync<MW ? 2 : 1>();
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(D64);
+        if (valid) {
+            // mean: pairwise sum in the data dtype; var: f64 pairwise sum of (f64(X) - mean)^2
+            const XT s = mr_pairwise<MW, XT>(pl, [&](int q) { return X[q]; }, (XT *)acc, (XT *)red, t, tpp);
+            mean = (double)s / (double)n;
+            const double mu = mean;
+            const double ss = mr_pairwise<MW, double>(pl, [&](int q) {
+                const double d = (double)X[q] - mu;
+                return d * d;
+            }, acc, red + 1, t, tpp);
+            sd = sqrt(ss / (double)n);
+            // ptp (NaN-propagating), max - min in the data dtype
+            XT mx = -INFINITY, mn = INFINITY;
+            int nan = 0;
+#pragma unroll
+            for (int u = 0; u < SPT; ++u) {
+                if (t + tpp * u < n) {
+                    nan |= isnan(xv[u]);
+                    mx = OpMaxF()(mx, xv[u]);
+                    mn = OpMinF()(mn, xv[u]);
+                }
+            }
+            mx = mr_tree<MW>(mx, OpMaxF(), (XT *)(red + 4), t, tpp);
+            mn = mr_tree<MW>(mn, OpMinF(), (XT *)(red + 8), t, tpp);
+            nan = mr_tree<MW>(nan, OpOr(), (int *)(red + 12), t, tpp);
+            ptp = nan ? (double)NAN : (double)(XT)(mx - mn);
+            // rFFT of f64(X) - mean: FFT_M in place over the work array
+            int ns = 1, step = n;
+            for (int st = 0; st < nst; ++st) {
+                const int R = (int)((radices >> (4 * st)) & 15);
+                step /= R;
+                if (st == 0) {   // M is a multiple of 4: the first radix is 8 or 4
+                    if (R == 8) mr_diag_stage<8, true, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp);
+                    else mr_diag_stage<4, true, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp);
+                } else {
+                    switch (R) {
+                    case 8: mr_diag_stage<8, false, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp); break;
+                    case 5: mr_diag_stage<5, false, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp); break;
+                    case 4: mr_diag_stage<4, false, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp); break;
+                    case 3: mr_diag_stage<3, false, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp); break;
+                    default: mr_diag_stage<2, false, PPT, MW, XT>(C, X, mu, tw, M, step, ns, t, tpp); break;
+                    }
+                }
+                ns *= R;
+            }
+            // the real spectrum in conjugate bin pairs (k_diag_p2): 2 X_k and
+            // 2 X_(M-k) from Z_k, Z_(M-k) and w^k = tw[k], k = 0 .. M/2
+            double best2 = 0.0, nsum = 0.0;
+            for (int kk = t; kk <= H; kk += tpp)
+                spec_pair_nan(C[mr_pad(kk)], C[mr_pad(kk == 0 ? 0 : M - kk)], tw[kk], best2, nsum);
+            int nanf = isnan(nsum);
+            best2 = mr_tree<MW>(best2, OpMaxF(), red + 16, t, tpp);
+            nanf = mr_tree<MW>(nanf, OpOr(), (int *)(red + 20), t, tpp);
+            fftv = nanf ? NAN : 0.5 * sqrt(best2);
+        } else {
+            // invalid: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
+            int nanx = 0;
+#pragma unroll
+            for (int u = 0; u < SPT; ++u)
+                if (t + tpp * u < n) nanx |= isnan(xv[u]);
+            nanx = mr_tree<MW>(nanx, OpOr(), (int *)(red + 12), t, tpp);
+            fftv = nanx ? NAN : 0.0;
+        }
+        if (t == 0) diag_store(a, k, valid, mean, sd, ptp, fftv);
+    }
+}
+
 // residual cube on request (ic_get_residual): R (dispersed frame, unweighted).
 // D == nullptr (fit_mode 1 keeps no fit cube): the fit-cube row is formed from
 // raw and the w0 baseline as in k_chan_partials mode 3, f32(ded - base).
@@ -1073,6 +1438,59 @@ static hipError_t launch_cl(hipStream_t st, const DiagArgs &a, size_t P)
     return hipGetLastError();
 }
 
+// k_diag_mr serves the mixed-radix lengths in every mode but DIAG_FIT
+static bool uses_mr(const DiagArgs &a)
+{
+    return mr_supported(a.nbin) && (a.mode == DIAG_EXACT || a.mode == DIAG_CLOSED || a.mode == DIAG_STATS);
+}
+
+// leaves of numpy's pairwise sum of n values (make_plan's recursion)
+static int pairwise_leaves(int n) { return n <= 128 ? 1 : pairwise_leaves(n / 2 - (n / 2) % 8) + pairwise_leaves(n - (n / 2 - (n / 2) % 8)); }
+
+// groups per block of the one-wave form: the count (<= 8) that puts the most
+// waves on a CU, whole blocks within its 160 KiB of LDS and within `cap` waves
+// (what the kernel's registers allow); the larger block on a tie (fewer copies
+// of the twiddle table)
+static int mr_groups_per_block(const MrLayout &L, int cap)
+{
+    int best = 1, best_waves = 0;
+    for (int g = 1; g <= 8; ++g) {
+        const size_t shm = L.groups_off + g * L.per_group;
+        if (shm > kLdsBudget) break;
+        const int waves = (int)std::min<size_t>(kLdsBlockMax / shm, (size_t)(cap / g)) * g;
+        if (waves >= best_waves) {
+            best = g;
+            best_waves = waves;
+        }
+    }
+    return best;
+}
+
+static hipError_t launch_mr(hipStream_t st, const DiagArgs &a, size_t P)
+{
+    unsigned long long radices = 0;
+    const int n = a.nbin, nst = mr_plan(n, &radices);
+    // the pairwise adds run in the lanes of one wave (mr_pairwise)
+    if (!nst || 2 * pairwise_leaves(n) > 64) return hipErrorInvalidValue;
+    const int W = (n + 1023) / 1024;
+    const bool mw = W > 1, d64 = a.data_f64 != 0;
+    const MrLayout L = mr_layout(n, mw, d64, a.mode == DIAG_CLOSED);
+    const int gpb = mw ? 1 : mr_groups_per_block(L, n <= 256 ? 16 : 12);   // __launch_bounds__: 4 / 3 waves per SIMD
+    const size_t shm = L.groups_off + gpb * L.per_group;
+    if (shm > kLdsBlockMax) return hipErrorInvalidValue;
+    const dim3 grid(cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap)), block(64 * (mw ? W : gpb));
+#define IC_DIAG_MR(PPT, MW)                                                                        \
+    do {                                                                                           \
+        if (d64) IC_GGL((k_diag_mr<PPT, MW, true>), grid, block, shm, st, a, radices, nst);        \
+        else IC_GGL((k_diag_mr<PPT, MW, false>), grid, block, shm, st, a, radices, nst);           \
+        return hipGetLastError();                                                                  \
+    } while (0)
+    if (mw) IC_DIAG_MR(8, true);
+    if (n <= 256) IC_DIAG_MR(2, false);
+    IC_DIAG_MR(8, false);
+#undef IC_DIAG_MR
+}
+
 static bool uses_cl(const DiagArgs &a)
 {
     if (!a.chain || a.data_f64 || !(a.nbin == 1024 || a.nbin == 2048 || a.nbin == 4096)) return false;
@@ -1082,13 +1500,13 @@ static bool uses_cl(const DiagArgs &a)
     return (a.mode == DIAG_EXACT || a.mode == DIAG_CLOSED) && a.T2 && a.raw && a.base && !a.pr_on;
 }
 
-// profile lists / skips: k_diag_cl, and k_diag_p2 in the exact mode and on
-// given rows (the FFT mode's rotated residuals)
+// profile lists / skips: k_diag_cl, and k_diag_p2 / k_diag_mr in the exact
+// mode and on given rows (the FFT mode's rotated residuals)
 bool diag_list_supported(const DiagArgs &a)
 {
     const int n = a.nbin;
     return uses_cl(a) ||
-           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && p2_supported(n));
+           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && (p2_supported(n) || mr_supported(n)));
 }
 
 // the generic k_diag's LDS layout as the host sizes it: nleaf/nops upper bound
@@ -1115,6 +1533,7 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
         if (nbin == 4096) return launch_cl<4096>(st, a, P);
     }
     if ((a.list || a.skip) && !diag_list_supported(a)) return hipErrorInvalidValue;
+    if (uses_mr(a)) return launch_mr(st, a, P);
 #define IC_P2(NN)                                                                                  \
     if (nbin == NN) {                                                                              \
         if (a.data_f64 && a.mode != DIAG_FIT) return launch_p2<NN, true>(st, a, P);                \
@@ -1137,6 +1556,10 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
 size_t diag_lds_bytes(int nbin)
 {
     if (p2_supported(nbin)) return 0;
+    if (mr_supported(nbin)) {   // k_diag_mr's largest form: one group, f64 data, the closed mode's row
+        const MrLayout L = mr_layout(nbin, nbin > 1024, true, true);
+        return L.groups_off + L.per_group;
+    }
     const DiagLayout lay = generic_layout(nbin);
     return (size_t)lay.ntw * 16 + lay.per_wave;
 }

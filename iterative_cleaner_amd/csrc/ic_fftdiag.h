@@ -1,5 +1,5 @@
 // ic_fftdiag.h -- device-only code that the diagnostics (ic_diag.hip:
-// k_diag, k_diag_p2, k_diag_cl) and the rotation (ic_rotate.hip: k_rotate,
+// k_diag, k_diag_p2, k_diag_cl, k_diag_mr) and the rotation (ic_rotate.hip: k_rotate,
 // whose fused statistics rot_stats are k_diag_cl's, and k_rotate_mr) share:
 // the f64 FFT pieces, the P2 / CLay profile-group layouts with their LDS
 // address maps, the group reductions, the compile-time Stockham chain, and
@@ -11,7 +11,7 @@
 
 namespace icgpu {
 
-// ---- mixed-radix (8/4/2) Stockham FFT helpers (forward, exp(-2 pi i jk/N)) ----
+// ---- mixed-radix (8/4/2, 3/5 for k_diag_mr) Stockham FFT helpers (forward, exp(-2 pi i jk/N)) ----
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ double2 cmul(double2 a, double2 w)
@@ -68,6 +68,39 @@ __device__ __forceinline__ void dft_small<8>(double2 (&v)[8])
     v[6] = csub(e[2], o2);
     v[3] = cadd(e[3], o3);
     v[7] = csub(e[3], o3);
+}
+
+// DFT_3 / DFT_5 in the written order of phase_rotation.py (_dft3, _dft5), f64
+// constants (k_diag_mr; the rotation's packed f32 forms are rot_dft3 / rot_dft5)
+template <>
+__device__ __forceinline__ void dft_small<3>(double2 (&v)[3])
+{
+    constexpr double s3 = 0x1.bb67ae8584caap-1;   // sqrt(3)/2
+    const double2 t = cadd(v[1], v[2]), d = csub(v[1], v[2]);
+    const double2 m = make_double2(v[0].x - t.x * 0.5, v[0].y - t.y * 0.5);
+    const double2 e = make_double2(d.x * s3, d.y * s3);
+    v[0] = cadd(v[0], t);
+    v[1] = make_double2(m.x + e.y, m.y - e.x);   // m - i e
+    v[2] = make_double2(m.x - e.y, m.y + e.x);   // m + i e
+}
+
+template <>
+__device__ __forceinline__ void dft_small<5>(double2 (&v)[5])
+{
+    constexpr double c1 = 0x1.3c6ef372fe950p-2;    // cos(2 pi/5)
+    constexpr double c2 = -0x1.9e3779b97f4a8p-1;   // cos(4 pi/5)
+    constexpr double s1 = 0x1.e6f0e134454ffp-1;    // sin(2 pi/5)
+    constexpr double s2 = 0x1.2cf2304755a5ep-1;    // sin(4 pi/5)
+    const double2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]), d1 = csub(v[1], v[4]), d2 = csub(v[2], v[3]);
+    const double2 m1 = make_double2((v[0].x + t1.x * c1) + t2.x * c2, (v[0].y + t1.y * c1) + t2.y * c2);
+    const double2 m2 = make_double2((v[0].x + t1.x * c2) + t2.x * c1, (v[0].y + t1.y * c2) + t2.y * c1);
+    const double2 e1 = make_double2(d1.x * s1 + d2.x * s2, d1.y * s1 + d2.y * s2);
+    const double2 e2 = make_double2(d1.x * s2 - d2.x * s1, d1.y * s2 - d2.y * s1);
+    v[0] = cadd(v[0], cadd(t1, t2));
+    v[1] = make_double2(m1.x + e1.y, m1.y - e1.x);
+    v[2] = make_double2(m2.x + e2.y, m2.y - e2.x);
+    v[3] = make_double2(m2.x - e2.y, m2.y + e2.x);
+    v[4] = make_double2(m1.x - e1.y, m1.y + e1.x);
 }
 
 // layout of a k_diag_p2<N> profile group

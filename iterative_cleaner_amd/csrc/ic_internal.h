@@ -289,7 +289,8 @@ inline bool p2_supported(int nbin)
 // stay 16-byte addressable: RotateArgs' strides are multiples of 4), nbin/2 =
 // 2^a 3^b 5^c, not a power of two (those are k_rotate<N>'s).  Like IC_P2_SIZES
 // this is the one place the set lives; the checks and error texts derive from
-// it.  The diagnostics of these lengths are the generic k_diag's.
+// it.  The diagnostics of these lengths are k_diag_mr's (a half-length FFT of
+// the same stages).
 constexpr int kMrMin = 64, kMrMax = 4096;
 constexpr int kMrMaxStages = 12;            // Stockham stages of FFT_{nbin/2} (4096: 5)
 constexpr size_t kMrLdsBytes = 64 * 1024;   // k_rotate_mr's LDS per block (one wave at 4096)
@@ -302,21 +303,53 @@ inline bool mr_supported(int nbin)
         while (m % f == 0) m /= f;
     return m == 1;
 }
+// the Stockham stages of FFT_{nbin/2} in the definition's order
+// (phase_rotation.py stage_radices): radix 8 while three or more power-of-two
+// levels remain, then 4 or 2, then the 3s, then the 5s; 4 bits per stage
+// (k_rotate_mr and k_diag_mr take the same fields).  Returns the stage count,
+// 0 for a length outside the set.
+inline int mr_plan(int nbin, unsigned long long *radices)
+{
+    int m = nbin / 2, lg = 0, nst = 0;
+    unsigned long long r = 0;
+    const auto push = [&](int R) {
+        if (nst < kMrMaxStages) r |= (unsigned long long)R << (4 * nst);
+        ++nst;
+    };
+    while (m % 2 == 0) {
+        m /= 2;
+        ++lg;
+    }
+    for (; lg >= 3; lg -= 3) push(8);
+    if (lg) push(1 << lg);
+    const int odd[2] = {3, 5};
+    for (const int f : odd)
+        while (m % f == 0) {
+            m /= f;
+            push(f);
+        }
+    *radices = r;
+    return m == 1 && nst <= kMrMaxStages ? nst : 0;
+}
 // the lengths the FFT dedispersion serves, for the error texts:
 // fail(..., "... needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, nbin)
 #define IC_ROT_NBIN_FMT                                                                            \
     "a power-of-two nbin in %d..%d, or a multiple of 8 in %d..%d whose half has only the prime factors 2, 3 and 5"
 #define IC_ROT_NBIN_ARGS ::icgpu::kP2Min, ::icgpu::kP2Max, ::icgpu::kMrMin, ::icgpu::kMrMax
 
-// Diagnostics kernels (k_diag_p2<N> for the power-of-two nbin above, k_diag
-// otherwise).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
+// Diagnostics kernels (k_diag_p2<N> / k_diag_cl<N> for the power-of-two nbin
+// above, k_diag_mr for the mixed-radix set, the generic k_diag otherwise: 100,
+// 500, ...).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
 // the fit cube D (row stride ldD); DIAG_CLOSED = fit_mode 1, the closed-form
 // amplitude sum(T*p)/TT from raw + base (written to amp/info), then the same
 // residual; DIAG_STATS = comprehensive_stats of the rows of D alone (no shift).
 // tw: exp(-2 pi i q/nbin), q < nbin; tw_p2 (power-of-two nbin only): see p2_twiddles()
 // DIAG_FIT = the closed-form amplitude alone (amp/info) of the rows of D (no
 // shift, no level): fit_mode 1 with fractional dedispersion, whose residual is
-// then rotated back and measured in DIAG_STATS.
+// then rotated back and measured in DIAG_STATS; power-of-two nbin only.
+// list / nctr / skip: the power-of-two and mixed-radix kernels in DIAG_EXACT
+// and DIAG_STATS, k_diag_cl in its modes (diag_list_supported); the generic
+// k_diag measures every profile.
 enum DiagMode { DIAG_EXACT = 0, DIAG_CLOSED = 1, DIAG_STATS = 2, DIAG_FIT = 3 };
 struct DiagArgs {
     int mode;

@@ -1103,34 +1103,7 @@ hipError_t launch_phasor_table(hipStream_t st, const double *delay, int nchan, i
 
 bool rotate_supported(int nbin) { return p2_supported(nbin) || mr_supported(nbin); }
 
-// the Stockham stages of FFT_{nbin/2} in the definition's order
-// (phase_rotation.py stage_radices): radix 8 while three or more power-of-two
-// levels remain, then 4 or 2, then the 3s, then the 5s; 4 bits per stage
-static int mr_plan(int nbin, unsigned long long *radices)
-{
-    int m = nbin / 2, lg = 0, nst = 0;
-    unsigned long long r = 0;
-    const auto push = [&](int R) {
-        if (nst < kMrMaxStages) r |= (unsigned long long)R << (4 * nst);
-        ++nst;
-    };
-    while (m % 2 == 0) {
-        m /= 2;
-        ++lg;
-    }
-    for (; lg >= 3; lg -= 3) push(8);
-    if (lg) push(1 << lg);
-    const int odd[2] = {3, 5};
-    for (const int f : odd)
-        while (m % f == 0) {
-            m /= f;
-            push(f);
-        }
-    *radices = r;
-    return m == 1 && nst <= kMrMaxStages ? nst : 0;
-}
-
-// k_rotate_mr: waves per block from the LDS it needs, 8 nbin bytes for the
+// k_rotate_mr: the stages from mr_plan (ic_internal.h); waves per block from the LDS it needs, 8 nbin bytes for the
 // block's f32 twiddle table and 8 nbin per wave, within kMrLdsBytes
 static hipError_t launch_rotate_mr(hipStream_t st, const RotateArgs &a, size_t P)
 {

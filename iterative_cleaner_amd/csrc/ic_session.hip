@@ -1071,7 +1071,7 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
         return fail(IC_EINVAL, "input_dedispersed=%d needs dedisp_mode IC_DEDISP_FFT (0 or 1)", p.input_dedispersed);
     if (p.dedisp_mode == IC_DEDISP_FFT && !rotate_supported(p.nbin))
         return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, p.nbin);
-    // launch_diag has no DIAG_FIT for the generic kernel these lengths use
+    // launch_diag has no DIAG_FIT at these lengths (k_diag_mr: EXACT, CLOSED and STATS)
     if (p.dedisp_mode == IC_DEDISP_FFT && p.fit_mode == IC_FIT_CLOSED && mr_supported(p.nbin))
         return fail(IC_EINVAL,
                     "fit_mode IC_FIT_CLOSED with fractional dedispersion needs a power-of-two nbin in %d..%d; "

@@ -67,12 +67,13 @@ typedef struct {
                                   111-112, 206-209): X = f64(R) * f64(w), f64 mean
                                   sum and ptp, ptp scaled in f64.  The samples must
                                   still be f32 values (the archive's amplitudes).  */
-    int32_t dedisp_mode;       /* IC_DEDISP_SHIFT (default) or IC_DEDISP_FFT       */
+    int32_t dedisp_mode;       /* IC_DEDISP_SHIFT (default), IC_DEDISP_FFT or the
+                                  opt-in IC_DEDISP_FFT_ANY                         */
     int32_t input_dedispersed; /* 1: the uploaded cube is the archive as stored
                                   DEDISPERSED (psrchive get_dedispersed()): the
                                   reference's dedisperse (:91, :100) is then a
                                   no-op and only the residual's dededisperse (:104)
-                                  rotates.  IC_DEDISP_FFT only (with integer shifts
+                                  rotates.  IC_DEDISP_FFT(_ANY) only (with integer shifts
                                   the host rolls the cube back to the dispersed
                                   frame, which is exact); 0 otherwise.            */
 } ic_params;
@@ -119,9 +120,24 @@ typedef struct {
  *                    own, in both dedispersion modes).  Any other length, and
  *                    IC_FIT_CLOSED at a mixed-radix length, is refused with
  *                    IC_EINVAL by ic_session_create.  The shift arrays of the
- *                    uploads are then unused (pass zeros). */
+ *                    uploads are then unused (pass zeros).
+ *   IC_DEDISP_FFT_ANY  opt-in: IC_DEDISP_FFT in every respect (delays,
+ *                    ic_set_delays / ic_set_delays2 / ic_upload_delays_async,
+ *                    input_dedispersed), and at every length IC_DEDISP_FFT
+ *                    serves the very same kernels and bits.  Any other nbin in
+ *                    16..4096, odd and prime lengths included, is rotated by a
+ *                    chirp-z (Bluestein) transform of its own written f32
+ *                    order (phase_rotation.py rotate_czt, bit-identical to it;
+ *                    within 5.5 f32 epsilons of the profile's largest |sample|
+ *                    of numpy's f64 rotation): IC_FIT_EXACT only; the
+ *                    statistics of these lengths run in the generic
+ *                    direct-DFT diagnostics kernel.  nbin < 16, nbin > 4096
+ *                    outside IC_DEDISP_FFT's set, and IC_FIT_CLOSED at a
+ *                    chirp-z or mixed-radix length are refused with IC_EINVAL.
+ *                    IC_DEDISP_FFT itself refuses exactly what it did. */
 #define IC_DEDISP_SHIFT 0
 #define IC_DEDISP_FFT 1
+#define IC_DEDISP_FFT_ANY 2
 
 /* Library / device info. */
 int ic_abi_version(void);
@@ -281,7 +297,7 @@ int ic_set_delays2(void *session, const double *delay_bins);
  * the consuming ic_run returns, page-locked for the copy to overlap.  The
  * slot's buffers (the table, nchan * (nbin/2 + 1) * 2 floats, and nsub * nchan
  * doubles) are allocated at first need and kept until ic_session_destroy.
- *   IC_ESTATE  the session is not IC_DEDISP_FFT; no upload is pending; the
+ *   IC_ESTATE  the session is not IC_DEDISP_FFT(_ANY); no upload is pending; the
  *              newest pending upload already has delays; the session has failed
  *   IC_EINVAL  a null pointer; per_profile not 0 or 1; a delay that is not
  *              finite (checked on the host, at the call): nothing is queued,
@@ -298,6 +314,11 @@ int ic_rotate_profiles(int device, int nsub, int nchan, int nbin, const float *i
 /* The same with per-profile delays delay_bins [nsub*nchan] (ic_set_delays2). */
 int ic_rotate_profiles2(int device, int nsub, int nchan, int nbin, const float *in, const double *delay_bins,
                         int sign, float *out);
+/* The same under IC_DEDISP_FFT_ANY's rule (opt-in): the lengths the two calls
+ * above serve keep their kernels and bits, any other nbin in 16..4096 takes the
+ * chirp-z rotation.  per_profile 0: delay_bins [nchan], 1: [nsub*nchan]. */
+int ic_rotate_profiles_any(int device, int nsub, int nchan, int nbin, const float *in, const double *delay_bins,
+                           int per_profile, int sign, float *out);
 
 /* The last iteration's residual cube (:101-108), dispersed frame, unweighted,
  * f32 [nsub][nchan][nbin] — what --unload_res writes (:161-162). */

@@ -27,7 +27,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_set_timing_kernel", "ic_set_option", "ic_get_option", "ic_comprehensive_stats_rowstat",
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
-           "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised")
+           "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised",
+           "ic_rotate_profiles_any")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -42,6 +43,7 @@ FIT_EXACT = 0    # IC_FIT_EXACT: scipy leastsq emulated bit for bit (the referen
 FIT_CLOSED = 1   # IC_FIT_CLOSED: closed-form amplitude fused with the diagnostics (fast mode)
 DEDISP_SHIFT = 0  # IC_DEDISP_SHIFT: integer dedispersion shifts
 DEDISP_FFT = 1    # IC_DEDISP_FFT: fractional delays, FFT phase rotation (phase_rotation.py)
+DEDISP_FFT_ANY = 2    # IC_DEDISP_FFT_ANY (opt-in): the same, plus the chirp-z rotation of any other nbin in 16..4096
 
 
 class NativeError(RuntimeError):
@@ -169,6 +171,7 @@ def load_library(path: str = LIB_PATH):
     lib.ic_upload_delays_async.argtypes = [vp, vp, C.c_int]
     lib.ic_rotate_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     lib.ic_rotate_profiles2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    lib.ic_rotate_profiles_any.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
     lib.ic_comprehensive_stats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double,
                                            vp, vp, vp, vp, vp]
     lib.ic_comprehensive_stats_rowstat.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double,
@@ -208,11 +211,16 @@ class GpuSession:
 
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
-                 delay=None, options=None, input_dedispersed=False, dedisp_fft=False):
+                 delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None):
         """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
         with these delays (set_delays).  dedisp_fft=True: the same mode without
         delays yet: they come with set_delays, or with each archive
-        (upload_async / upload_quantised_async delay=)."""
+        (upload_async / upload_quantised_async delay=).  any_length (None = the
+        IC_ANY_NBIN switch, phase_rotation.any_length_enabled): that mode is
+        IC_DEDISP_FFT_ANY, which also serves any other nbin in 16..4096 by the
+        chirp-z rotation (the lengths IC_DEDISP_FFT serves keep their bits)."""
+        from .phase_rotation import any_length_enabled
+        fft_mode = DEDISP_FFT_ANY if (any_length_enabled() if any_length is None else any_length) else DEDISP_FFT
         self.lib = load_library()
         self.shape = (int(nsub), int(nchan), int(nbin))
         self.max_iter = int(max_iter)
@@ -220,7 +228,7 @@ class GpuSession:
         on, fac, a, b = normalise_pulse_region(list(pulse_region), int(nbin))
         self.params = Params(int(nsub), int(nchan), int(nbin), int(max_iter), float(chanthresh),
                              float(subintthresh), on, fac, a, b, float(baseline_duty), self.fit_mode,
-                             1 if data_f64 else 0, DEDISP_FFT if (delay is not None or dedisp_fft) else DEDISP_SHIFT,
+                             1 if data_f64 else 0, fft_mode if (delay is not None or dedisp_fft) else DEDISP_SHIFT,
                              1 if input_dedispersed else 0)
         self.data_f64 = bool(data_f64)
         h = C.c_void_p()
@@ -554,11 +562,15 @@ def encode_profiles(cube, big_endian=False, device=0):
     return q, scl, offs
 
 
-def rotate_profiles(cube, delay, sign=1, device=0):
+def rotate_profiles(cube, delay, sign=1, device=0, any_length=None):
     """Fractional dedispersion of a (nsub, nchan, nbin) cube on the GPU: the FFT
     phase rotation by +delay (sign 1, dedisperse) or -delay (sign -1); delay
     (nchan,) per channel (ic_rotate_profiles) or (nsub, nchan) per profile
-    (ic_rotate_profiles2)."""
+    (ic_rotate_profiles2).  any_length (None = the IC_ANY_NBIN switch):
+    ic_rotate_profiles_any, which also serves any other nbin in 16..4096."""
+    from .phase_rotation import any_length_enabled
+    if any_length is None:
+        any_length = any_length_enabled()
     lib = load_library()
     cube = np.ascontiguousarray(cube, dtype=np.float32)
     if cube.ndim != 3:
@@ -571,7 +583,12 @@ def rotate_profiles(cube, delay, sign=1, device=0):
     else:
         d = np.ascontiguousarray(delay, dtype=np.float64).reshape(nchan)
         fn, name = lib.ic_rotate_profiles, "ic_rotate_profiles"
-    rc = fn(int(device), nsub, nchan, nbin, _ptr(cube), _ptr(d), int(sign), _ptr(out))
+    if any_length:
+        name = "ic_rotate_profiles_any"
+        rc = lib.ic_rotate_profiles_any(int(device), nsub, nchan, nbin, _ptr(cube), _ptr(d), int(d.ndim == 2),
+                                        int(sign), _ptr(out))
+    else:
+        rc = fn(int(device), nsub, nchan, nbin, _ptr(cube), _ptr(d), int(sign), _ptr(out))
     if rc != 0:
         raise NativeError("%s: %s (rc=%d)" % (name, _err(lib), rc))
     return out

@@ -156,7 +156,7 @@ class Archive:
     def __init__(self, data, weights=None, dm_shift=None, dedispersed=False,
                  filename="synthetic.ar", source="J0000+0000",
                  centre_frequency=1400.0, mjd_start=60000.0, mjd_end=60000.01,
-                 baseline_duty=BASELINE_DUTY, state=None, dm_delay=None):
+                 baseline_duty=BASELINE_DUTY, state=None, dm_delay=None, any_length=None):
         data = np.asarray(data, dtype=np.float32)
         if data.ndim != 4:
             raise ValueError("data must be (nsub, npol, nchan, nbin)")
@@ -175,9 +175,13 @@ class Archive:
         self._shift = np.mod(np.asarray(dm_shift, dtype=np.int64), nbin).reshape(nchan)
         self._delay = None
         if dm_delay is not None:
-            from .phase_rotation import UNSUPPORTED, is_supported
-            if not is_supported(nbin):
-                raise ValueError("fractional dedispersion %s (nbin=%d)" % (UNSUPPORTED, nbin))
+            # any_length (None = the IC_ANY_NBIN switch, read here): dedisperse /
+            # dededisperse take the chirp-z statement at the other lengths in 16..4096
+            from .phase_rotation import UNSUPPORTED, any_hint, any_length_enabled, czt_selected, is_supported
+            self._any_length = any_length_enabled() if any_length is None else bool(any_length)
+            if not is_supported(nbin) and not czt_selected(nbin, self._any_length):
+                raise ValueError("fractional dedispersion %s (nbin=%d)%s"
+                                 % (UNSUPPORTED, nbin, any_hint(nbin, self._any_length)))
             d = np.array(dm_delay, dtype=np.float64)
             self._delay = d.reshape((nsub, nchan) if d.ndim == 2 else (nchan,))
         self._dedispersed = bool(dedispersed)
@@ -209,6 +213,7 @@ class Archive:
 
     _psrfits_q = None
     _q_exact = False
+    _any_length = False
 
     # ---------------------------------------------------------------- shape
     def get_nsubint(self): return self._data.shape[0]
@@ -242,7 +247,7 @@ class Archive:
     def _rotate(self, data: np.ndarray, sign: int) -> np.ndarray:
         from .phase_rotation import phasors, rotate
         d = self._delay if self._delay.ndim == 1 else self._delay[:, None, :]   # over (nsub, npol, nchan)
-        return rotate(data, phasors(self.get_nbin(), d), sign)
+        return rotate(data, phasors(self.get_nbin(), d), sign, any_length=self._any_length)
 
     def get_dedispersed(self) -> bool:
         return self._dedispersed

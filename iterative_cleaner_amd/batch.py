@@ -248,7 +248,8 @@ class _Ring:
 
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
-                dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None):
+                dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
+                any_length=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -271,8 +272,9 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     alternate; psrfits_loader yields such items).  The delays are staged in the
     ring and go up with their archive.  An item without delays raises
     ValueError, as does one with delays when dedisp is "shift".
-    input_dedispersed, fit_mode and options (a dict of schedule options) are
-    handed to every lane's GpuSession."""
+    input_dedispersed, fit_mode, options (a dict of schedule options) and
+    any_length (None = the IC_ANY_NBIN switch: IC_DEDISP_FFT_ANY, any nbin in
+    16..4096) are handed to every lane's GpuSession."""
     if dedisp not in ("shift", "fft"):
         raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
     fft = dedisp == "fft"
@@ -383,7 +385,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
-                                               dedisp_fft=fft))
+                                               dedisp_fft=fft, any_length=any_length))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
@@ -406,7 +408,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                 rg.close()
 
 
-def psrfits_loader(paths, dedisp="shift"):
+def psrfits_loader(paths, dedisp="shift", any_length=None):
     """Loader for clean_batch(..., quantised=True, dedisp=dedisp) over fold-mode
     PSRFITS files (psrfits.load_quantised): yields (q, scl, offs, w0, shift),
     or with dedisp="fft" (q, scl, offs, w0, shift, delay), the delays the file's
@@ -414,12 +416,13 @@ def psrfits_loader(paths, dedisp="shift"):
     profile when the rows' periods differ).  Raises ValueError naming the file
     whose dedispersion is not `dedisp`: one with integral delays in an "fft"
     list, one with fractional delays in a "shift" list.  The delays are never
-    rounded, and integral ones never take the rotation, which is not exact."""
+    rounded, and integral ones never take the rotation, which is not exact.
+    any_length: psrfits.load_quantised's (dedispersion.plan's opt-in)."""
     if dedisp not in ("shift", "fft"):
         raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
     from . import psrfits
     for path in paths:
-        q, scl, offs, w0, shift, meta = psrfits.load_quantised(path)
+        q, scl, offs, w0, shift, meta = psrfits.load_quantised(path, any_length=any_length)
         delay = meta["delay"]
         if (delay is not None) != (dedisp == "fft"):
             raise ValueError("%s: the archive is dedispersed by %s, the batch by %s"

@@ -331,6 +331,27 @@ inline int mr_plan(int nbin, unsigned long long *radices)
     *radices = r;
     return m == 1 && nst <= kMrMaxStages ? nst : 0;
 }
+// The opt-in chirp-z rotation (dedisp_mode IC_DEDISP_FFT_ANY, k_rotate_czt;
+// phase_rotation.py rotate_czt): every nbin in kCztMin..kCztMax that neither
+// set above holds, odd and prime lengths included.  A DFT of length n as a
+// circular convolution of length L = czt_length(n), the smallest power of two
+// >= 2 n - 1 (Bluestein), whose FFT_L are the Stockham stages of mr_plan(2 L).
+constexpr int kCztMin = 16, kCztMax = 4096;
+inline bool czt_supported(int nbin)
+{
+    return nbin >= kCztMin && nbin <= kCztMax && !p2_supported(nbin) && !mr_supported(nbin);
+}
+inline int czt_length(int nbin)
+{
+    int L = 1;
+    while (L < 2 * nbin - 1) L *= 2;
+    return L;
+}
+// floats of the per-length tables (RotateArgs.czt): f32 pairs [L] tw =
+// exp(-2 pi i q / L), [L] the filter B, [nbin] the chirp w
+inline size_t czt_table_floats(int nbin) { return 2 * (2 * (size_t)czt_length(nbin) + (size_t)nbin); }
+#define IC_CZT_NBIN_FMT "; IC_DEDISP_FFT_ANY also serves any other nbin in %d..%d"
+#define IC_CZT_NBIN_ARGS ::icgpu::kCztMin, ::icgpu::kCztMax
 // the lengths the FFT dedispersion serves, for the error texts:
 // fail(..., "... needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, nbin)
 #define IC_ROT_NBIN_FMT                                                                            \
@@ -481,7 +502,8 @@ __host__ __device__ inline double2 ic_phasor(int k, double d, int n)
 // diagnostics fork's two passes).  in may equal out (each row is read whole
 // before it is written).  nbin a power of two, 64 .. 8192 (IC_P2_SIZES:
 // k_rotate<N>), or a mixed-radix length (mr_supported: k_rotate_mr, which
-// honours everything here but the fused statistics).
+// honours everything here but the fused statistics), or, with the czt tables
+// given, any other length in 16 .. 4096 (czt_supported: k_rotate_czt, likewise).
 struct RotateArgs {
     const float *in;
     long ld_in;
@@ -522,6 +544,12 @@ struct RotateArgs {
     const double2 *tw_p2;       // k_diag_p2's twiddle table (p2_twiddles); unused at a mixed-radix nbin
     double *std_o, *mean_o, *ptp_o, *fft_o;
     int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
+    // the chirp-z rotation (czt_supported(nbin), IC_DEDISP_FFT_ANY): the
+    // per-length tables (czt_table_floats: tw of L, B, chirp), or nullptr: such
+    // an nbin is then refused.  Its rows may have any stride and alignment (the
+    // strides' multiple-of-4 condition is the other kernels'); tw, tw_p2 and
+    // the fused statistics are unused.
+    const float *czt;
 };
 hipError_t launch_rotate(hipStream_t st, const RotateArgs &a);
 // RotateArgs.ph built on the device from delay [nchan] f64 (device memory):

@@ -1,6 +1,7 @@
 // ic_rotate.hip -- fractional dedispersion: the FFT phase rotation at
 // power-of-two (k_rotate, with the fused statistics rot_stats) and mixed-radix
-// (k_rotate_mr) profile lengths, the identity rotation, the channel phasor
+// (k_rotate_mr) profile lengths, the opt-in chirp-z rotation of any other
+// length (k_rotate_czt), the identity rotation, the channel phasor
 // table they read (k_phasor_table), and their launchers.
 #include <algorithm>
 #include <float.h>
@@ -1070,6 +1071,144 @@ __global__ __launch_bounds__(256) void k_rotate_mr(RotateArgs a, unsigned long l
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_rotate_czt: the opt-in rotation of any other length n in 16 .. 4096
+// (czt_supported; phase_rotation.py rotate_czt), odd and prime n included, by
+// Bluestein's chirp-z transform: DFT_n as a circular convolution of length
+// L = czt_length(n) with the chirp w[j] = exp(-i pi j^2 / n),
+//   conj(DFT_n(a)) L = FFT_L(conj(FFT_L(a w, zero-padded) B)),  B = FFT_L(conj w),
+// run twice: on the real row, and on conj(Y) of the spectrum times the phasors.
+//   1. v[j] = x'[j] w[j] (x' = f32(x - base), or the residual), 0 for j >= n
+//   2. V = FFT_L(v); V = conj(V B); D = FFT_L(V)
+//   3. k < n: X = (conj(D[k]) w[k]) / L; Y = X P (harmonic k <= n/2: (P.r,
+//      sign P.i)[k]; k > n/2: its conjugate at n - k; the Nyquist harmonic of
+//      an even n: both parts by P.r); v[k] = conj(Y) w[k], 0 for k >= n
+//   4. step 2 again; out[j] = (Re(conj(D[j]) w[j]) / L) (1/n)
+// One wave per profile, n and L runtime values; the wave's L complex points
+// ping-pong between two LDS buffers (16 L bytes), one Stockham stage (mr_stage,
+// radices 8 / 4 / 2) per trip.  The per-length tables (RotateArgs.czt: tw of L,
+// B, w; f32 pairs in HBM, shared by every profile) are read through L1/L2,
+// except that up to L = 4096 the block stages tw in LDS (TWG = false); at
+// L = 8192 the two buffers take 128 KiB of the CU's 160 and tw stays global
+// (TWG).  Rows of these lengths are not 16-byte aligned in general: every row
+// access is a 4-byte one, a wave's 64 consecutive.  Every complex operation is
+// the packed f32 arithmetic of k_rotate.  PP: per-profile delays.
+template <bool PP, bool TWG>
+__global__ __launch_bounds__(256) void k_rotate_czt(RotateArgs a, int L, unsigned long long radices, int nst)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char czt_sm[];
+    const int n = a.nbin, hn = n >> 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const rc2 *gtw = (const rc2 *)a.czt, *B = gtw + L, *ch = B + L;
+    rc2 *tws = (rc2 *)czt_sm;                                   // [L] tw (not TWG)
+    rc2 *v0 = tws + (TWG ? 0 : L) + (size_t)wv * 2 * L;         // the wave's two buffers of L points
+    rc2 *v1 = v0 + L;
+    if constexpr (!TWG) {
+        for (int i = threadIdx.x; i < L; i += blockDim.x) tws[i] = gtw[i];
+        __syncthreads();
+    }
+    const unsigned nsub = (unsigned)a.nsub, nchan = (unsigned)a.nchan;
+    const size_t P = (size_t)nsub * nchan;
+    const rc2 sgv = {1.0f, a.sign > 0 ? 1.0f : -1.0f};
+    const rc2 cj = {1.0f, -1.0f};
+    const float invL = 1.0f / (float)L;   // exact: L is a power of two
+    const float invn = (float)(1.0 / (double)n);
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const size_t nitems = a.list ? (size_t)rl.n() : P;
+    // FFT_L of the points in `z`, times B, conjugated, FFT_L again: returns the buffer of D
+    const auto convolve = [&](rc2 *z) {
+        rc2 *o = z == v0 ? v1 : v0;
+        if constexpr (TWG) z = mr_fft(z, o, gtw, L, L, radices, nst, lane);
+        else z = mr_fft(z, o, tws, L, L, radices, nst, lane);
+        for (int i = lane; i < L; i += 64) z[i] = rot_cmul(z[i], B[i]) * cj;
+        wave_sync();
+        o = z == v0 ? v1 : v0;
+        if constexpr (TWG) return mr_fft(z, o, gtw, L, L, radices, nst, lane);
+        else return mr_fft(z, o, tws, L, L, radices, nst, lane);
+    };
+    // items and skips as k_rotate's, restated (a shared helper changed both kernels' code): edit both
+    for (size_t item = (size_t)blockIdx.x * wpb + wv; item < nitems; item += (size_t)gridDim.x * wpb) {
+        unsigned c, s;
+        size_t p;
+        if (a.list) {
+            p = (size_t)rl.at((long)item);
+            c = (unsigned)(p % nchan);
+            s = (unsigned)(p / nchan);
+        } else {
+            c = (unsigned)(item / nsub);
+            s = (unsigned)(item % nsub);
+            p = (size_t)s * nchan + c;
+        }
+        if ((a.flags && a.flags[s] == 0) || (a.late && ((a.late[p] != 0) != (a.late_sel != 0)))) continue;
+        // PP: the profile's phasor parts as k_rotate_mr's
+        double2 Alo{}, Bhi{};
+        const float *phc = nullptr;
+        if constexpr (PP) {
+            const double dly = a.delay2[p];
+            Alo = ic_phasor0(lane, dly, n);
+            Bhi = ic_phasor0(64 * lane <= hn ? 64 * lane : 0, dly, n);
+        } else {
+            phc = a.ph + 2 * (size_t)c * (hn + 1);
+        }
+        // f32(ic_phasor(k, delay, n)), k <= n/2; every lane of the wave calls it together
+        auto phasor = [&](int k) {
+            if constexpr (PP) {
+                const int lo = k & 63, hi = k >> 6;
+                const double2 A = make_double2(__shfl(Alo.x, lo), __shfl(Alo.y, lo));
+                const double2 Bh = make_double2(__shfl(Bhi.x, hi), __shfl(Bhi.y, hi));
+                return rc2_of(lo == 0 ? Bh : (hi == 0 ? A : ic_phasor_mul(A, Bh)));
+            } else {
+                return *(const rc2 *)(phc + 2 * k);
+            }
+        };
+        {
+            const bool res = a.amp != nullptr;
+            const bool ok = res && fit_ok(a.info[p]);
+            const double am = res ? a.amp[p] : 0.0;
+            const float b = (!res && a.base) ? a.base[p] : 0.0f;
+            for (int j = lane; j < L; j += 64) {
+                rc2 v = {0.0f, 0.0f};
+                if (j < n) {
+                    const float xin = a.in[d_ofs(p, j, (int)a.ld_in, a.in_tiled)];
+                    // the residual of the exact fit (k_residual's arithmetic), formed on the fly
+                    const float x = res ? (ok ? residual_sample(am, a.T64[j], xin, j, a) : 0.0f) : xin - b;
+                    v = (rc2){x, x} * ch[j];
+                }
+                v0[j] = v;
+            }
+        }
+        wave_sync();
+        rc2 *z = convolve(v0);
+        // the spectrum times the phasors, conjugated, times the chirp.  Uniform
+        // trip count: the shuffles of phasor() need every lane
+        for (int k0 = 0; k0 < L; k0 += 64) {
+            const int k = k0 + lane;
+            if (k0 < n) {
+                const int kc = k < n ? k : n - 1;
+                const bool up = kc > hn;
+                rc2 pk = phasor(up ? n - kc : kc) * sgv;
+                if (up) pk = pk * cj;
+                if (k < n) {
+                    const rc2 w = ch[k];
+                    const rc2 X = rot_cmul(z[k] * cj, w) * (rc2){invL, invL};
+                    const rc2 Y = (2 * k == n) ? X * pk.xx : rot_cmul(X, pk);
+                    z[k] = rot_cmul(Y * cj, w);
+                }
+            }
+            if (k >= n && k < L) z[k] = (rc2){0.0f, 0.0f};   // L may be 32
+        }
+        wave_sync();
+        const rc2 *r = convolve(z);
+        float *o = a.out + p * (size_t)a.ldo;
+        for (int j = lane; j < n; j += 64) {
+            const float y = (rot_cmul(r[j] * cj, ch[j]).x * invL) * invn;
+            o[j] = y;
+            if (a.out2) a.out2[d_ofs(p, j, (int)a.ldo2, a.out2_tiled)] = y;
+        }
+        wave_sync();   // the buffers are reused by the wave's next profile
+    }
+}
+
 // The channel phasor table of the FFT dedispersion (RotateArgs.ph) from the
 // channels' delays on the device: ph[c][k] = f32(ic_phasor(k, delay[c], nbin)),
 // k <= nbin/2.  One element per thread, k fastest (a wave stores 512
@@ -1129,11 +1268,37 @@ static hipError_t launch_rotate_mr(hipStream_t st, const RotateArgs &a, size_t P
     return hipErrorInvalidValue;
 }
 
+// k_rotate_czt: FFT_L's stages from mr_plan(2 L); waves per block from the LDS it needs, 16 L bytes per wave and 8 L
+// for the block's f32 twiddle table (L <= 4096), within kMrLdsBytes where one wave fits there: L = 4096 takes 96 KiB
+// for its one wave, L = 8192 128 KiB without the table
+static hipError_t launch_rotate_czt(hipStream_t st, const RotateArgs &a, size_t P)
+{
+    const int L = czt_length(a.nbin);
+    unsigned long long radices = 0;
+    const int nst = mr_plan(2 * L, &radices);
+    if (!nst || L < 32 || L > 8192) return hipErrorInvalidValue;
+    const bool twg = L > 4096;
+    const size_t tab = twg ? 0 : 8 * (size_t)L, unit = 16 * (size_t)L;
+    const int wpb = kMrLdsBytes > tab + unit ? (int)std::min<size_t>(4, (kMrLdsBytes - tab) / unit) : 1;
+    const size_t shm = tab + unit * (size_t)wpb;
+    if (shm > kLdsBudget) return hipErrorInvalidValue;
+    const dim3 grid(cap_grid(std::min<size_t>(cdiv(P, wpb), 2048), a.grid_cap)), block(64 * wpb);
+    if (twg) {
+        if (a.delay2) IC_GGL((k_rotate_czt<true, true>), grid, block, shm, st, a, L, radices, nst);
+        else IC_GGL((k_rotate_czt<false, true>), grid, block, shm, st, a, L, radices, nst);
+    } else {
+        if (a.delay2) IC_GGL((k_rotate_czt<true, false>), grid, block, shm, st, a, L, radices, nst);
+        else IC_GGL((k_rotate_czt<false, false>), grid, block, shm, st, a, L, radices, nst);
+    }
+    return hipGetLastError();
+}
+
 bool rotate_stats_supported(int nbin, bool data_f64) { return nbin == 1024 && !data_f64; }
 
 // The identity "rotation" of an archive stored dedispersed (its dedisperse is a
 // no-op, archive.py dedisperse): out[p] = f32(in[p] - base[p]) (and out2), for
-// the subints flags selects; a wave per profile, 16-byte rows.
+// the subints flags selects; a wave per profile, 16-byte rows (4-byte accesses
+// where nbin or a stride is no multiple of 4: the chirp-z lengths).
 __global__ __launch_bounds__(256) void k_rotate_identity(RotateArgs a)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1141,6 +1306,14 @@ __global__ __launch_bounds__(256) void k_rotate_identity(RotateArgs a)
     for (size_t p = (size_t)blockIdx.x * 4 + wave; p < P; p += (size_t)gridDim.x * 4) {
         if (a.flags && a.flags[p / (unsigned)a.nchan] == 0) continue;
         const float b = a.base ? a.base[p] : 0.0f;
+        if ((a.nbin | a.ld_in | a.ldo | a.ldo2) & 3) {   // a chirp-z length: rows of any alignment
+            for (int j = lane; j < a.nbin; j += 64) {
+                const float y = a.in[d_ofs(p, j, (int)a.ld_in, a.in_tiled)] - b;
+                a.out[p * (size_t)a.ldo + j] = y;
+                if (a.out2) a.out2[d_ofs(p, j, (int)a.ldo2, a.out2_tiled)] = y;
+            }
+            continue;
+        }
         for (int j = 4 * lane; j < a.nbin; j += 256) {
             const float4 x = *(const float4 *)(a.in + d_ofs(p, j, (int)a.ld_in, a.in_tiled));
             const float4 y = make_float4(x.x - b, x.y - b, x.z - b, x.w - b);
@@ -1169,10 +1342,14 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
                   !a.ptp_o || !a.fft_o))
         return hipErrorInvalidValue;
     const bool mr = mr_supported(a.nbin);
-    if (!rotate_supported(a.nbin) || !a.in || (!a.out && !stats) || !a.tw || (!mr && !a.tw_p2) || a.ld_in < a.nbin ||
+    // the chirp-z lengths: opted in by their tables; rows of any stride (4-byte accesses)
+    const bool czt = a.czt && czt_supported(a.nbin);
+    const int ldm = czt ? 0 : 3;
+    if ((!rotate_supported(a.nbin) && !czt) || !a.in || (!a.out && !stats) || (!czt && !a.tw) ||
+        (!mr && !czt && !a.tw_p2) || a.ld_in < a.nbin ||
         (!stats && a.ldo < a.nbin) ||
         (!a.ph && !a.delay2 && !a.identity) ||
-        (a.ld_in & 3) || (a.ldo & 3) || (a.out2 && (a.ldo2 < a.nbin || (a.ldo2 & 3))) ||
+        (a.ld_in & ldm) || (a.ldo & ldm) || (a.out2 && (a.ldo2 < a.nbin || (a.ldo2 & ldm))) ||
         (a.amp && (!a.T64 || !a.info)) || (a.in_tiled && (a.ld_in & 31)) || (a.out2_tiled && (a.ldo2 & 31)) ||
         (a.identity && (a.amp || a.late || a.list)) || (a.list && !a.nctr))
         return hipErrorInvalidValue;
@@ -1182,6 +1359,7 @@ hipError_t launch_rotate(hipStream_t st, const RotateArgs &a)
         return hipGetLastError();
     }
     if (mr) return launch_rotate_mr(st, a, P);
+    if (czt) return launch_rotate_czt(st, a, P);
     if (stats) {   // nbin 1024 (rotate_stats_supported)
         rotate_p2<1024, true>(st, a, P);
         return hipGetLastError();

@@ -279,6 +279,7 @@ struct Session {
     float *dr = nullptr, *Tc = nullptr, *R = nullptr, *zbase = nullptr;
     int32_t *zshift = nullptr;
     float *ph = nullptr;   // f32 pairs
+    float *czt = nullptr;  // IC_DEDISP_FFT_ANY at a chirp-z length: the per-length tables (czt_tables)
     double *dly = nullptr;           // [P] the session's delays on the device (first need): the channel
                                      // row k_phasor_table reads, or the per-profile delays
     double *delay2 = nullptr;        // = dly while per-profile delays are in force, else nullptr
@@ -494,6 +495,97 @@ std::vector<double2> p2_twiddles(int N)
     return t;
 }
 
+// FFT_L of v (L a power of two) in f64: the rotation's Stockham stages in
+// their written order (phase_rotation.py _stockham with n = L, _dft8 / _dft4 in
+// f64; radix 8 while three or more levels remain, then 4 or 2), tw =
+// host_twiddles(L).  Host code under -ffp-contract=off: every operation one
+// IEEE f64 operation, so numpy's czt_filter gives the same bits.
+void stockham64(std::vector<double2> &v, const std::vector<double2> &tw)
+{
+    const int L = (int)v.size();
+    std::vector<double2> o(L);
+    const auto add = [](double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); };
+    const auto sub = [](double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); };
+    const auto dft4 = [&](double2 *b) {
+        const double2 c0 = add(b[0], b[2]), c1 = sub(b[0], b[2]), c2 = add(b[1], b[3]), d = sub(b[1], b[3]);
+        const double2 c3 = make_double2(d.y, -d.x);   // -i d
+        b[0] = add(c0, c2);
+        b[1] = add(c1, c3);
+        b[2] = sub(c0, c2);
+        b[3] = sub(c1, c3);
+    };
+    int lg = 0;
+    while ((1 << lg) < L) ++lg;
+    for (int ns = 1; lg > 0;) {
+        const int R = lg >= 3 ? 8 : (1 << lg), G = L / R, step = L / (R * ns);
+        for (int j = 0; j < G; ++j) {
+            const int k = j % ns;
+            double2 u[8];
+            for (int q = 0; q < R; ++q) u[q] = v[j + q * G];
+            if (ns > 1)
+                for (int q = 1; q < R; ++q) {
+                    const double2 w = tw[(size_t)q * k * step], x = u[q];
+                    u[q] = make_double2(x.x * w.x - x.y * w.y, x.x * w.y + x.y * w.x);
+                }
+            if (R == 8) {
+                const double s8 = 0.7071067811865476;
+                double2 c[8];
+                for (int q = 0; q < 4; ++q) {
+                    c[q] = add(u[q], u[q + 4]);
+                    c[q + 4] = sub(u[q], u[q + 4]);
+                }
+                c[5] = make_double2((c[5].x + c[5].y) * s8, (c[5].y - c[5].x) * s8);
+                c[6] = make_double2(c[6].y, -c[6].x);
+                c[7] = make_double2((c[7].y - c[7].x) * s8, -((c[7].x + c[7].y) * s8));
+                dft4(c);
+                dft4(c + 4);
+                for (int q = 0; q < 4; ++q) {
+                    u[2 * q] = c[q];
+                    u[2 * q + 1] = c[q + 4];
+                }
+            } else if (R == 4) {
+                dft4(u);
+            } else {
+                const double2 x = u[0], y = u[1];
+                u[0] = add(x, y);
+                u[1] = sub(x, y);
+            }
+            for (int q = 0; q < R; ++q) o[(size_t)(j - k) * R + k + (size_t)q * ns] = u[q];
+        }
+        v.swap(o);
+        ns *= R;
+        lg -= R == 8 ? 3 : (R == 4 ? 2 : 1);
+    }
+}
+
+// The chirp-z rotation's per-length tables (RotateArgs.czt; phase_rotation.py
+// czt_chirp / czt_filter), f32 pairs: [L] tw = exp(-2 pi i q / L), [L] the
+// filter B = FFT_L(b) with b[j] = b[L - j] = conj(w[j]), j < n, built in f64 and
+// rounded once, [n] the chirp w[j] = exp(-i pi (j^2 mod 2n) / n)
+std::vector<float> czt_tables(int n)
+{
+    const int L = czt_length(n);
+    const std::vector<double2> tw = host_twiddles(L);
+    std::vector<double2> w(n), b(L, make_double2(0.0, 0.0));
+    for (int j = 0; j < n; ++j) {
+        w[j] = unit_root((long double)(((long long)j * j) % (2 * n)), (long double)(2 * n));
+        b[j] = b[(L - j) % L] = make_double2(w[j].x, -w[j].y);
+    }
+    stockham64(b, tw);
+    std::vector<float> t;
+    t.reserve(czt_table_floats(n));
+    const auto put = [&t](const std::vector<double2> &src) {
+        for (const double2 &e : src) {
+            t.push_back((float)e.x);
+            t.push_back((float)e.y);
+        }
+    };
+    put(tw);
+    put(b);
+    put(w);
+    return t;
+}
+
 int collect_timing(Session *s)
 {
     if (s->events.empty()) return 0;
@@ -680,6 +772,7 @@ RotateArgs rotate_args(Session *s, const float *in, const float *base, int sign,
     a.sign = sign;
     a.tw = s->tw;
     a.tw_p2 = s->tw_p2;
+    a.czt = s->czt;
     a.flags = flags;
     a.nsub = s->p.nsub;
     a.nchan = s->nchan;
@@ -1065,17 +1158,25 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     if (p.max_iter < 0) return fail(IC_EINVAL, "max_iter < 0");
     if (p.fit_mode != IC_FIT_EXACT && p.fit_mode != IC_FIT_CLOSED)
         return fail(IC_EINVAL, "fit_mode %d unsupported", p.fit_mode);
-    if (p.dedisp_mode != IC_DEDISP_SHIFT && p.dedisp_mode != IC_DEDISP_FFT)
+    if (p.dedisp_mode != IC_DEDISP_SHIFT && p.dedisp_mode != IC_DEDISP_FFT && p.dedisp_mode != IC_DEDISP_FFT_ANY)
         return fail(IC_EINVAL, "dedisp_mode %d unsupported", p.dedisp_mode);
-    if (p.input_dedispersed != 0 && (p.input_dedispersed != 1 || p.dedisp_mode != IC_DEDISP_FFT))
+    // IC_DEDISP_FFT_ANY (opt-in) is IC_DEDISP_FFT plus the chirp-z rotation of the other lengths in 16..4096
+    const bool fft_any = p.dedisp_mode == IC_DEDISP_FFT_ANY, fft_mode = fft_any || p.dedisp_mode == IC_DEDISP_FFT;
+    const bool czt = fft_any && czt_supported(p.nbin);
+    if (p.input_dedispersed != 0 && (p.input_dedispersed != 1 || !fft_mode))
         return fail(IC_EINVAL, "input_dedispersed=%d needs dedisp_mode IC_DEDISP_FFT (0 or 1)", p.input_dedispersed);
-    if (p.dedisp_mode == IC_DEDISP_FFT && !rotate_supported(p.nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, p.nbin);
+    if (fft_mode && !rotate_supported(p.nbin) && !czt)
+        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT IC_CZT_NBIN_FMT " (nbin=%d)",
+                    IC_ROT_NBIN_ARGS, IC_CZT_NBIN_ARGS, p.nbin);
     // launch_diag has no DIAG_FIT at these lengths (k_diag_mr: EXACT, CLOSED and STATS)
-    if (p.dedisp_mode == IC_DEDISP_FFT && p.fit_mode == IC_FIT_CLOSED && mr_supported(p.nbin))
+    if (fft_mode && p.fit_mode == IC_FIT_CLOSED && mr_supported(p.nbin))
         return fail(IC_EINVAL,
                     "fit_mode IC_FIT_CLOSED with fractional dedispersion needs a power-of-two nbin in %d..%d; "
                     "a mixed-radix nbin takes IC_FIT_EXACT (nbin=%d)", kP2Min, kP2Max, p.nbin);
+    if (czt && p.fit_mode == IC_FIT_CLOSED)
+        return fail(IC_EINVAL,
+                    "fit_mode IC_FIT_CLOSED with fractional dedispersion needs a power-of-two nbin in %d..%d; "
+                    "a chirp-z nbin (IC_DEDISP_FFT_ANY) takes IC_FIT_EXACT (nbin=%d)", kP2Min, kP2Max, p.nbin);
     if (diag_lds_bytes(p.nbin) > kLdsBlockMax)
         return fail(IC_EINVAL, "nbin=%d needs %zu bytes of LDS for the diagnostics (> 160 KiB)", p.nbin,
                     diag_lds_bytes(p.nbin));
@@ -1147,13 +1248,13 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     s->raw = s->slot_raw[0];
     // the closed-form fit reads the raw cube (no fit cube, no lmdif state), unless
     // the dedispersion is the FFT rotation: then the rotated fit cube is kept
-    if (exact || p.dedisp_mode == IC_DEDISP_FFT) {
+    if (exact || fft_mode) {
         AL(s->D, s->Ppad * (size_t)s->ldD);
         if (hipMemset(s->D, 0, sizeof(float) * s->Ppad * (size_t)s->ldD) != hipSuccess)
             return bail(fail(IC_EHIP, "hipMemset(D) failed"));
     }
     AL(s->TT, 1);
-    s->fftded = p.dedisp_mode == IC_DEDISP_FFT;
+    s->fftded = fft_mode;
     // The FFT mode forks too (round 6): its forked pass is the residual rotation
     // that measures the rows, one kernel since the statistics moved into it, and
     // it now hides behind the late fit rounds (C2 --dedisp fft 45.51-45.70 ->
@@ -1186,6 +1287,12 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
         AL(s->zbase, P);
         AL(s->zshift, (size_t)nchan);
         AL(s->ph, 2 * (size_t)nchan * (nbin / 2 + 1));
+        if (czt) {
+            const std::vector<float> ct = czt_tables(nbin);
+            AL(s->czt, ct.size());
+            if (hipMemcpy(s->czt, ct.data(), sizeof(float) * ct.size(), hipMemcpyHostToDevice) != hipSuccess)
+                return bail(fail(IC_EHIP, "upload of the chirp-z tables failed"));
+        }
         if (hipMemset(s->zbase, 0, sizeof(float) * P) != hipSuccess ||
             hipMemset(s->zshift, 0, sizeof(int32_t) * nchan) != hipSuccess)
             return bail(fail(IC_EHIP, "hipMemset(zero levels / shifts) failed"));
@@ -2137,11 +2244,13 @@ namespace {
 // ic_rotate_profiles(2): per_profile = 0: delay_bins [nchan] (the phasor
 // table), 1: [nsub*nchan] (phasors evaluated per profile in the kernel)
 int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, const double *delay_bins,
-                    int per_profile, int sign, float *out)
+                    int per_profile, int sign, float *out, bool any = false)
 {
     if (!in || !delay_bins || !out || nsub <= 0 || nchan <= 0) return fail(IC_EINVAL, "bad argument");
-    if (!rotate_supported(nbin))
-        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT " (nbin=%d)", IC_ROT_NBIN_ARGS, nbin);
+    const bool czt = any && czt_supported(nbin);   // ic_rotate_profiles_any at a chirp-z length
+    if (!rotate_supported(nbin) && !czt)
+        return fail(IC_EINVAL, "fractional dedispersion needs " IC_ROT_NBIN_FMT IC_CZT_NBIN_FMT " (nbin=%d)",
+                    IC_ROT_NBIN_ARGS, IC_CZT_NBIN_ARGS, nbin);
     if (sign != 1 && sign != -1) return fail(IC_EINVAL, "sign must be +1 or -1");
     const size_t nd = per_profile ? (size_t)nsub * nchan : (size_t)nchan;
     for (size_t c = 0; c < nd; ++c)
@@ -2150,9 +2259,10 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
     const size_t N = (size_t)nsub * nchan * nbin;
     const std::vector<float> ph = per_profile ? std::vector<float>(2) : make_phasors(nbin, nchan, delay_bins);
     const std::vector<double2> tw = host_twiddles(nbin), tw2 = p2_twiddles(nbin);   // tw2: the rotation's stage tables
+    const std::vector<float> ct = czt ? czt_tables(nbin) : std::vector<float>();
     const auto bad = [](hipError_t e) { return named_fail("ic_rotate_profiles", e); };
     Scratch sc;
-    float *d = nullptr, *dph = nullptr;
+    float *d = nullptr, *dph = nullptr, *dct = nullptr;
     double2 *dtw = nullptr, *dtw2 = nullptr;
     double *ddl = nullptr;
     CKF(sc.open_stream(), bad);
@@ -2171,7 +2281,12 @@ int rotate_profiles(int device, int nsub, int nchan, int nbin, const float *in, 
         CKF(sc.mem.alloc_exact(&dtw2, tw2.size()), bad);
         CKF(hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st), bad);
     }
+    if (czt) {
+        CKF(sc.mem.alloc_exact(&dct, ct.size()), bad);
+        CKF(hipMemcpyAsync(dct, ct.data(), sizeof(float) * ct.size(), hipMemcpyHostToDevice, st), bad);
+    }
     RotateArgs a{};
+    a.czt = dct;
     a.in = d;
     a.ld_in = nbin;
     a.ph = per_profile ? nullptr : dph;
@@ -2201,6 +2316,13 @@ int ic_rotate_profiles2(int device, int nsub, int nchan, int nbin, const float *
                         int sign, float *out)
 {
     return rotate_profiles(device, nsub, nchan, nbin, in, delay_bins, 1, sign, out);
+}
+
+int ic_rotate_profiles_any(int device, int nsub, int nchan, int nbin, const float *in, const double *delay_bins,
+                           int per_profile, int sign, float *out)
+{
+    if (per_profile != 0 && per_profile != 1) return fail(IC_EINVAL, "per_profile must be 0 or 1");
+    return rotate_profiles(device, nsub, nchan, nbin, in, delay_bins, per_profile, sign, out, true);
 }
 
 int ic_get_bad_fits(void *session, int32_t *per_iter, int n)

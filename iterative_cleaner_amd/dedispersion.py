@@ -25,13 +25,16 @@ Mode selection (:func:`plan`):
     or a multiple of 8 in 64..4096 whose half has only the prime factors 2, 3
     and 5 (phase_rotation.mr_supported: 1000, 1200, 1536, 2000, ...); any
     other nbin raises (the rotation kernels do not serve it, and rounding the
-    delays would silently change which profiles get zapped).
+    delays would silently change which profiles get zapped), unless the caller
+    opts in (``any_length=True`` or the environment switch IC_ANY_NBIN): then
+    any other nbin in 16..4096 is served by the chirp-z rotation
+    (IC_DEDISP_FFT_ANY, phase_rotation.rotate_czt).
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .phase_rotation import UNSUPPORTED, mr_supported
+from .phase_rotation import UNSUPPORTED, any_hint, czt_selected, mr_supported
 
 DISPERSION_CONSTANT = 1.0 / 2.41e-4    # s MHz^2 cm^3 / pc (psrchive, dspsr, tempo)
 
@@ -56,11 +59,13 @@ def delays_from_dm(dm, freqs, fref, periods, nbin) -> np.ndarray:
     return t[None, :] / p[:, None] * float(nbin)
 
 
-def plan(delay, nbin: int, what: str = "archive"):
+def plan(delay, nbin: int, what: str = "archive", any_length=None):
     """(shift, delay) for the loop: integer shifts (delay None) when every delay
     is integral, else (zeros, delay) with delay (nchan,) if all rows agree or
     (nsub, nchan).  Raises ValueError for fractional delays at an nbin the
-    rotation does not serve, and for non-finite delays."""
+    rotation does not serve, and for non-finite delays.  any_length (None = the
+    IC_ANY_NBIN switch, phase_rotation.any_length_enabled): opt in to the
+    chirp-z rotation (IC_DEDISP_FFT_ANY) of any other nbin in 16..4096."""
     d = np.asarray(delay, dtype=np.float64)
     if d.ndim == 1:
         d = d[None, :]
@@ -73,9 +78,9 @@ def plan(delay, nbin: int, what: str = "archive"):
             return rows[0], None
         # integral, but a channel's shift differs between subints: the shift
         # arrays are per channel, so these go through the per-profile rotation
-    if not fft_supported(nbin):
-        raise ValueError("%s: the FFT phase rotation of fractional dedispersion delays %s (nbin=%d); "
-                         "the delays are not rounded" % (what, UNSUPPORTED, nbin))
+    if not fft_supported(nbin) and not czt_selected(nbin, any_length):
+        raise ValueError("%s: the FFT phase rotation of fractional dedispersion delays %s (nbin=%d)%s; "
+                         "the delays are not rounded" % (what, UNSUPPORTED, nbin, any_hint(nbin, any_length)))
     zeros = np.zeros(nchan, np.int64)
     if np.all(d == d[:1]):
         return zeros, np.ascontiguousarray(d[0])

@@ -79,13 +79,57 @@ and half rows stay 16-byte addressable), N/2 = 2^a 3^b 5^c, N not a power of
 two.  Measured on random profiles (tests/test_phase_rotation_mr.py) the MR
 lengths stay within the same 4 f32 epsilons of the largest sample as the
 powers of two.
+
+Any length (opt-in).  Every other n in 16 .. 4096, odd and prime n included,
+is served only when the caller opts in (``any_length=True``, or the environment
+switch IC_ANY_NBIN read by :func:`any_length_enabled`; the library's
+IC_DEDISP_FFT_ANY and ic_rotate_profiles_any, kernel k_rotate_czt); with
+nothing switched on such a length is refused as before.  The lengths the
+default kernels serve (:func:`kernel_supported`) keep the definition above and
+its bits under the opt-in too; the others take this chirp-z (Bluestein)
+statement, :func:`rotate_czt`: a DFT of length n as a circular convolution of
+length L, the smallest power of two >= 2 n - 1, every step one IEEE f32
+operation in the written order, the complex product always (a.r w.r - a.i w.i,
+a.r w.i + a.i w.r):
+
+1. x' = f32(x - base); v[j] = (x'[j] w[j].r, x'[j] w[j].i) for j < n, +0 for
+   n <= j < L, with the chirp w[j] = exp(-i pi (j^2 mod 2n) / n) =
+   tw_2n[j^2 mod 2n] (the reduction in exact integers; tw_2n = twiddles(2n):
+   long double, then f64, then f32).
+2. V = FFT_L(v): the Stockham stages of step 2 above for a power of two (radix
+   8 while three or more levels remain, then 4 or 2), with
+   w_q = tw_L[q k L/(R Ns)], tw_L = f32 of twiddles(L).  C = V B (the
+   product above, a = V); D = FFT_L(conj(C)) (conj negates the imaginary part).
+3. For k < n: X[k] = (conj(D[k]) w[k]) (1/L), both parts by the exact f32 1/L:
+   the spectrum DFT_n(x').  Y[k] = X[k] Ph[k], where Ph[k] = (P[k].r,
+   sign P[k].i) for k <= n/2 and the conjugate of that at n - k for k > n/2
+   (P = f32 of :func:`phasors`, n//2 + 1 entries); for an even n the Nyquist
+   harmonic takes P.r only: Y[n/2] = (X.r P.r, X.i P.r).
+   v[k] = conj(Y[k]) w[k], +0 for n <= k < L.
+4. Step 2 on that v; out[j] = ((conj(D[j]) w[j]).r (1/L)) (1/n), 1/n the f32
+   of the f64 quotient.
+
+The filter table B = FFT_L(b), b[j] = b[L - j] = conj(w[j]) for j < n and 0
+elsewhere, is built once per length in f64 (:func:`czt_filter`): the f64
+chirp, the same Stockham stages with every operation in f64, f64 twiddles(L)
+and the f64 sqrt(2)/2, then one rounding to f32 (the library runs the same
+stages on the host without contraction and gives the same bits; within 1 f32
+ulp of numpy's f64 fft of b).  With B computed by the f32 stages instead the
+error below grows by about one epsilon.  Measured against numpy's f64 rotation
+on the inputs of tests/test_phase_rotation_mr.py, in f32 epsilons of the
+largest |sample| (tests/test_phase_rotation_any.py): 16: 4.08, 17: 2.73,
+33: 3.30, 48: 2.92, 100: 3.09, 125: 2.47, 129: 3.25, 448: 3.16, 500: 3.08,
+997: 3.54, 2047: 3.23, 2049: 3.05, 2500: 3.78, 4095: 2.93; the asserted bound
+is 5.5.  phasors() serves an odd n as it stands (harmonics 0 .. (n - 1)/2,
+within 1e-15 of x87 long double).
 """
 from __future__ import annotations
 
 import numpy as np
 
 __all__ = ["PI_L", "twiddles", "phasors", "rotate", "is_supported", "mr_supported", "stage_radices",
-           "MR_NBIN_MIN", "MR_NBIN_MAX", "UNSUPPORTED"]
+           "MR_NBIN_MIN", "MR_NBIN_MAX", "UNSUPPORTED", "any_length_enabled", "kernel_supported", "czt_selected",
+           "rotate_czt", "czt_length", "czt_chirp", "czt_filter", "CZT_NBIN_MIN", "CZT_NBIN_MAX"]
 
 PI_L = np.longdouble("3.141592653589793238462643383279502884")
 
@@ -157,7 +201,8 @@ _PH_C = tuple(float.fromhex(h) for h in (
 
 def phasors(nbin: int, delays) -> np.ndarray:
     """(2, *delays.shape, nbin/2 + 1) f64: exp(+2 pi i k s / nbin) for every
-    delay s (bins) and harmonic k <= nbin/2 (any even nbin <= 8192; 1/nbin and
+    delay s (bins) and harmonic k <= nbin/2 (any nbin <= 8192, odd ones with
+    nbin/2 rounded down: the chirp-z statement's; 1/nbin and
     4/nbin are rounded f64 factors unless nbin is a power of two), in this f64
     operation order:
 
@@ -215,6 +260,7 @@ def phasors(nbin: int, delays) -> np.ndarray:
 
 
 S8 = np.float32(0.7071067811865476)   # f32 of f64(sqrt(2)/2) = Re exp(-i pi/4) of the f32 twiddle table
+S8_64 = np.float64(0.7071067811865476)   # the f64 stages of the chirp-z filter table (czt_filter)
 
 
 def _dft4(ar, ai):
@@ -231,11 +277,12 @@ def _dft4(ar, ai):
 def _dft8(ar, ai):
     cr = [ar[q] + ar[q + 4] for q in range(4)] + [ar[q] - ar[q + 4] for q in range(4)]
     ci = [ai[q] + ai[q + 4] for q in range(4)] + [ai[q] - ai[q + 4] for q in range(4)]
+    s8 = S8 if ar[0].dtype == np.float32 else S8_64
     t1, t2 = cr[5] + ci[5], ci[5] - cr[5]    # c5 * exp(-i pi/4)
-    cr[5], ci[5] = t1 * S8, t2 * S8
+    cr[5], ci[5] = t1 * s8, t2 * s8
     cr[6], ci[6] = ci[6], -cr[6]             # c6 * -i
     t1, t2 = ci[7] - cr[7], cr[7] + ci[7]    # c7 * exp(-3 i pi/4)
-    cr[7], ci[7] = t1 * S8, -(t2 * S8)
+    cr[7], ci[7] = t1 * s8, -(t2 * s8)
     er, ei = _dft4(cr[:4], ci[:4])
     orr, oi = _dft4(cr[4:], ci[4:])
     return ([er[0], orr[0], er[1], orr[1], er[2], orr[2], er[3], orr[3]],
@@ -271,11 +318,13 @@ def _dft5(ar, ai):
             [ai[0] + (t1i + t2i), m1i - e1r, m2i - e2r, m2i + e2r, m1i + e1r])
 
 
-def _stockham(vr: np.ndarray, vi: np.ndarray, tw: np.ndarray):
+def _stockham(vr: np.ndarray, vi: np.ndarray, tw: np.ndarray, n: int | None = None):
     """FFT of the last axis (M complex points): Stockham stages in the order of
-    :func:`stage_radices` (module docstring)."""
+    :func:`stage_radices` (module docstring).  tw: exp(-2 pi i q / n), n = 2 M
+    (the real rotation's table) unless given (the chirp-z transform's n = M)."""
     m = vr.shape[-1]
-    n = 2 * m
+    if n is None:
+        n = 2 * m
     ns = 1
     for r in stage_radices(m):
         g = m // r
@@ -339,17 +388,23 @@ def _pair(zkr, zki, zqr, zqi, c, sn, pkr, pki, pqr, pqi):
 
 
 def rotate(x: np.ndarray, ph: np.ndarray, sign: int, tw: np.ndarray | None = None,
-           base: np.ndarray | None = None) -> np.ndarray:
+           base: np.ndarray | None = None, any_length: bool | None = None) -> np.ndarray:
     """Rotate profiles x (..., nchan, nbin) f32 by their delays.
 
     ph: phasors(nbin, delays) for the nchan channels (axis -2 of x), or for
     every profile (delays of x's leading shape, e.g. (nsub, nchan)); sign +1 =
     dedisperse (y[j] = x[j + s]), -1 = dededisperse; base (..., nchan) f32 is
-    subtracted first in f32 (remove_baseline's levels)."""
+    subtracted first in f32 (remove_baseline's levels).  any_length (None = the
+    IC_ANY_NBIN switch, :func:`any_length_enabled`): a length in 16..4096 that
+    the rotation kernels do not serve takes the chirp-z statement
+    (:func:`rotate_czt`); the lengths they serve keep this one's bits."""
     x = np.asarray(x, dtype=np.float32)
     n = x.shape[-1]
+    if czt_selected(n, any_length):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return rotate_czt(x, ph, sign, base)
     if not is_supported(n):
-        raise ValueError("fractional dedispersion %s (nbin=%d)" % (UNSUPPORTED, n))
+        raise ValueError("fractional dedispersion %s (nbin=%d)%s" % (UNSUPPORTED, n, any_hint(n, any_length)))
     if tw is None:
         tw = twiddles(n)
     tw = np.asarray(tw, dtype=np.float64).astype(np.float32)   # f32 of the f64 table
@@ -390,5 +445,134 @@ def _rotate(x, ph, sign, tw, base):
     out[..., 0::2] = rr * inv
     out[..., 1::2] = (-ri) * inv
     for a in (vr, vi, ur, ui, rr, ri):
+        assert a.dtype == np.float32   # every operation of the definition is f32
+    return out
+
+
+# ---------------------------------------------------------------------------
+# The opt-in chirp-z statement: any nbin in 16..4096 (module docstring, "Any
+# length")
+
+CZT_NBIN_MIN, CZT_NBIN_MAX = 16, 4096    # the library's kCztMin / kCztMax (csrc/ic_internal.h)
+ANY_NBIN_ENV = "IC_ANY_NBIN"
+
+
+def any_length_enabled() -> bool:
+    """The process-wide opt-in switch of the host layer: the environment
+    variable IC_ANY_NBIN (unset, empty or ``0`` = off).  Read at every call."""
+    import os
+    return os.environ.get(ANY_NBIN_ENV, "") not in ("", "0")
+
+
+def kernel_supported(nbin: int) -> bool:
+    """The lengths the default rotation kernels serve (the library's
+    rotate_supported): a power of two in 64..8192, or a mixed-radix length."""
+    return (64 <= nbin <= 8192 and (nbin & (nbin - 1)) == 0) or mr_supported(nbin)
+
+
+def czt_selected(nbin: int, any_length: bool | None = None) -> bool:
+    """The chirp-z statement serves nbin: the opt-in is on (any_length, None =
+    :func:`any_length_enabled`), 16 <= nbin <= 4096, and the default kernels do
+    not serve it (those lengths keep their statement and their bits)."""
+    if any_length is None:
+        any_length = any_length_enabled()
+    return bool(any_length) and CZT_NBIN_MIN <= nbin <= CZT_NBIN_MAX and not kernel_supported(nbin)
+
+
+def any_hint(nbin: int, any_length: bool | None = None) -> str:
+    """What a refusal adds to UNSUPPORTED: the switch, or its range when it is on."""
+    if any_length is None:
+        any_length = any_length_enabled()
+    if any_length:
+        return "; with any_length / %s, any other nbin in %d..%d" % (ANY_NBIN_ENV, CZT_NBIN_MIN, CZT_NBIN_MAX)
+    if CZT_NBIN_MIN <= nbin <= CZT_NBIN_MAX:
+        return "; any_length=True or %s=1 opts in to the chirp-z rotation of any nbin in %d..%d" % (
+            ANY_NBIN_ENV, CZT_NBIN_MIN, CZT_NBIN_MAX)
+    return ""
+
+
+def czt_length(n: int) -> int:
+    """L: the smallest power of two >= 2 n - 1."""
+    L = 1
+    while L < 2 * n - 1:
+        L *= 2
+    return L
+
+
+def czt_chirp(n: int) -> np.ndarray:
+    """(2, n) f64: w[j] = exp(-i pi (j^2 mod 2n) / n) = twiddles(2n)[j^2 mod 2n]
+    (the reduction is exact integer arithmetic)."""
+    j = np.arange(n, dtype=np.int64)
+    return twiddles(2 * n)[:, (j * j) % (2 * n)]
+
+
+def czt_filter(n: int) -> np.ndarray:
+    """(2, L) f32: B = FFT_L(b), b[j] = b[L - j] = conj(w[j]) (j < n), 0
+    elsewhere, by the module's Stockham stages run in f64 (f64 chirp, f64
+    twiddles(L), f64 sqrt(2)/2), then rounded to f32."""
+    L = czt_length(n)
+    w = czt_chirp(n)
+    br = np.zeros(L)
+    bi = np.zeros(L)
+    j = np.arange(n)
+    br[j], bi[j] = w[0], -w[1]
+    br[(L - j) % L], bi[(L - j) % L] = w[0], -w[1]
+    Br, Bi = _stockham(br, bi, twiddles(L), L)
+    assert Br.dtype == np.float64
+    return np.stack([Br, Bi]).astype(np.float32)
+
+
+def _cmul(ar, ai, wr, wi):
+    """The rotation's complex product (a.r w.r - a.i w.i, a.r w.i + a.i w.r)."""
+    return ar * wr - ai * wi, ar * wi + ai * wr
+
+
+def _czt_conv(ar, ai, B, twL, L):
+    """D = FFT_L(conj(FFT_L(a, zero-padded to L) B)) for a (..., n) f32, the
+    chirped input: D[k] = L conj(DFT_n)[k] / w[k] for k < n (module docstring,
+    "Any length", step 2)."""
+    n = ar.shape[-1]
+    vr = np.zeros(ar.shape[:-1] + (L,), np.float32)
+    vi = np.zeros(ar.shape[:-1] + (L,), np.float32)
+    vr[..., :n], vi[..., :n] = ar, ai
+    vr, vi = _stockham(vr, vi, twL, L)
+    cr, ci = _cmul(vr, vi, B[0], B[1])
+    return _stockham(cr, -ci, twL, L)
+
+
+def rotate_czt(x: np.ndarray, ph: np.ndarray, sign: int, base: np.ndarray | None = None) -> np.ndarray:
+    """The chirp-z statement of the rotation (module docstring, "Any length"):
+    x (..., nchan, n) f32, ph = phasors(n, delays), any n >= 2 (the library
+    serves 16..4096)."""
+    x = np.asarray(x, dtype=np.float32)
+    n = x.shape[-1]
+    L = czt_length(n)
+    h = n // 2
+    w = czt_chirp(n).astype(np.float32)
+    B = czt_filter(n)
+    twL = twiddles(L).astype(np.float32)
+    invL = np.float32(1.0 / L)
+    invn = np.float32(1.0 / n)
+    if base is not None:
+        x = (x - np.asarray(base, dtype=np.float32)[..., None]).astype(np.float32)
+    # X = DFT_n(x)
+    dr, di = _czt_conv(x * w[0], x * w[1], B, twL, L)
+    xr, xi = _cmul(dr[..., :n], -di[..., :n], w[0], w[1])
+    xr, xi = xr * invL, xi * invL
+    # Y = X P: harmonic k <= n/2 takes (P.r, sign P.i)[k], k > n/2 its conjugate at n - k
+    k = np.arange(n)
+    kk = np.where(k <= h, k, n - k)
+    pr = np.asarray(ph[0]).astype(np.float32)[..., kk]
+    pi = np.asarray(ph[1] if sign > 0 else -ph[1]).astype(np.float32)[..., kk]
+    pi = np.where(k <= h, pi, -pi)
+    yr, yi = _cmul(xr, xi, pr, pi)
+    if n % 2 == 0:   # the Nyquist harmonic takes P.r only
+        yr[..., h], yi[..., h] = xr[..., h] * pr[..., h], xi[..., h] * pr[..., h]
+    # y = Re conj(DFT_n(conj(Y))) / n
+    vr, vi = _cmul(yr, -yi, w[0], w[1])
+    dr, di = _czt_conv(vr, vi, B, twL, L)
+    orr, _ = _cmul(dr[..., :n], -di[..., :n], w[0], w[1])
+    out = (orr * invL) * invn
+    for a in (dr, di, xr, xi, yr, yi, out):
         assert a.dtype == np.float32   # every operation of the definition is f32
     return out

@@ -296,7 +296,7 @@ def probe_shape(path: str):
             fh.seek(n + (-n % BLOCK), 1)
 
 
-def _read_subint(path: str, channels, native: bool) -> dict:
+def _read_subint(path: str, channels, native: bool, any_length=None) -> dict:
     """The SUBINT table's columns and keywords as load() and load_quantised()
     use them; native: the int16 samples in host byte order (else as stored)."""
     with open(path, "rb") as fh:
@@ -346,7 +346,7 @@ def _read_subint(path: str, channels, native: bool) -> dict:
         from . import dedispersion
         allf = np.array(rows["DAT_FREQ"].reshape(nsub, nchan_total)[0], np.float64)
         delay = dedispersion.delays_from_dm(dm, allf, cfreq, period, nbin)[:, c0:c1]
-        shift, frac = dedispersion.plan(delay, nbin, path)
+        shift, frac = dedispersion.plan(delay, nbin, path, any_length)
     else:
         shift = np.zeros(nchan, np.int64)
     mjd0 = float(primary.get("STT_IMJD", 60000)) + (float(primary.get("STT_SMJD", 0))
@@ -361,18 +361,20 @@ def _read_subint(path: str, channels, native: bool) -> dict:
                 nchan_total=nchan_total)
 
 
-def load(path: str, channels=None):
+def load(path: str, channels=None, any_length=None):
     """Read a fold-mode PSRFITS archive.  channels = (c0, c1): only those
     channels; the SUBINT table is memory-mapped, so the other channels' samples
-    are never read (channel-sharded cleaning)."""
+    are never read (channel-sharded cleaning).  any_length (None = the
+    IC_ANY_NBIN switch): dedispersion.plan's and Archive's opt-in."""
     from .archive import Archive
-    t = _read_subint(path, channels, True)
+    t = _read_subint(path, channels, True, any_length)
     q, scl, offs, primary, hdr, mjd0, period = (t[k] for k in ("q", "scl", "offs", "primary", "hdr", "mjd0", "period"))
     ar = Archive(decode(q, scl, offs), t["weights"], t["shift"], dedispersed=bool(hdr.get("IC_DEDSP", False)),
                  filename=path, source=str(primary.get("SRC_NAME", "J0000+0000")),
                  centre_frequency=t["cfreq"], mjd_start=mjd0,
                  mjd_end=float(hdr.get("IC_MJDE", mjd0 + 0.01)),
-                 baseline_duty=float(hdr.get("IC_DUTY", 0.15)), state=t["state"], dm_delay=t["frac"])
+                 baseline_duty=float(hdr.get("IC_DUTY", 0.15)), state=t["state"], dm_delay=t["frac"],
+                 any_length=any_length)
     if channels is not None:
         ar._chan_range = (t["c0"], t["c1"])
         ar._nchan_total = t["nchan_total"]
@@ -385,7 +387,7 @@ def load(path: str, channels=None):
     return ar
 
 
-def load_quantised(path: str, channels=None):
+def load_quantised(path: str, channels=None, any_length=None):
     """The samples of a fold-mode PSRFITS archive as the file stores them, for
     GpuSession.upload_quantised[_async] and batch loaders: the f32 cube is never
     formed.  Returns (q, scl, offs, weights, shift, meta): q int16 (nsub, npol,
@@ -394,7 +396,7 @@ def load_quantised(path: str, channels=None):
     the values load() gives its archive; meta: the state ('Intensity', 'PPQQ',
     'Coherence' or 'Stokes'), dedispersed, baseline_duty, delay (the
     fractional delays or None), npol and source."""
-    t = _read_subint(path, channels, False)
+    t = _read_subint(path, channels, False, any_length)
     q = t["q"]
     nsub, npol, nchan, nbin = q.shape
     hdr = t["hdr"]

@@ -32,7 +32,7 @@ def _loop_kwargs(args):
                 pulse_region=args.get("pulse_region", (0, 0, 1)),
                 baseline_duty=args.get("baseline_duty", 0.15), fit_mode=args.get("fit_mode", 0),
                 data_f64=args.get("data_f64", False), options=args.get("options"),
-                input_dedispersed=args.get("input_dedispersed", False))
+                input_dedispersed=args.get("input_dedispersed", False), any_length=args.get("any_length"))
 
 
 def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, fit_tail=None, **args):

@@ -45,8 +45,12 @@ extern "C" {
 
 /* Loop parameters: args Namespace of iterative_cleaner.py:16-42.
  * nbin: a power of two in 64..8192 runs the templated diagnostics kernels
- * (k_diag_p2 / k_diag_cl; at 8192 a profile is shared by eight waves), any
- * other length the generic k_diag, as far as its per-profile LDS need allows
+ * (k_diag_p2 / k_diag_cl; at 8192 a profile is shared by eight waves), a
+ * mixed-radix length (see dedisp_mode) k_diag_mr, and any other length from
+ * 129 to 4096 (odd ones to 2048) k_diag_czt, whose fftmax is a chirp-z
+ * transform; all of these serve the diagnostics fork.  What is left (below
+ * 129, odd above 2048, beyond 4096) runs the generic direct-DFT k_diag,
+ * unforked, as far as its per-profile LDS need allows
  * (ic_session_create says how many bytes a refused length would take: every
  * power of two above 8192 is refused that way).  With IC_DEDISP_FFT the
  * length must also be one the rotation serves (see dedisp_mode below).
@@ -129,9 +133,12 @@ typedef struct {
  *                    chirp-z (Bluestein) transform of its own written f32
  *                    order (phase_rotation.py rotate_czt, bit-identical to it;
  *                    within 5.5 f32 epsilons of the profile's largest |sample|
- *                    of numpy's f64 rotation): IC_FIT_EXACT only; the
- *                    statistics of these lengths run in the generic
- *                    direct-DFT diagnostics kernel.  nbin < 16, nbin > 4096
+ *                    of numpy's f64 rotation): IC_FIT_EXACT only.  The
+ *                    statistics of these lengths run in k_diag_czt (an f64
+ *                    chirp-z transform for fftmax, with the diagnostics
+ *                    fork) from 129 bins, odd lengths to 2048, and in the
+ *                    generic direct-DFT kernel otherwise, as they do with
+ *                    integer shifts.  nbin < 16, nbin > 4096
  *                    outside IC_DEDISP_FFT's set, and IC_FIT_CLOSED at a
  *                    chirp-z or mixed-radix length are refused with IC_EINVAL.
  *                    IC_DEDISP_FFT itself refuses exactly what it did. */

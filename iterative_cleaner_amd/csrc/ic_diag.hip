@@ -11,10 +11,12 @@
 // Kernels:
 //   k_diag           residual (ic.py:279-288), f32 store (:272), dededisperse
 //                    (:104), apply_weights (:296), diagnostics (:206-217); any
-//                    nbin, a wave per profile
+//                    nbin, a wave per profile (what no kernel below serves)
 //   k_diag_p2        the same for the power-of-two nbin (IC_P2_SIZES)
 //   k_diag_cl        the chain layout at nbin 1024 / 2048 / 4096
 //   k_diag_mr        the same for the mixed-radix nbin (mr_supported)
+//   k_diag_czt       the same for the other nbin in 129..4096 (diag_czt_supported):
+//                    fftmax by a chirp-z transform
 //   k_residual       the residual cube on request (ic_get_residual)
 //   k_tnorm          sum(T*T), fit_mode 1's denominator
 #include <algorithm>
@@ -1361,6 +1363,368 @@ __global__ __launch_bounds__(MW ? 256 : 512, PPT > 2 ? 3 : 4) void k_diag_mr(Dia
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_diag_czt: k_diag's diagnostics for the other lengths (diag_czt_supported:
+// 129 .. 4096, neither a power of two nor mixed-radix; odd and prime lengths
+// to 2048 included; the kernel itself takes any n in 16 .. 4096 whose L <=
+// 4096), n a runtime value.  std / mean / ptp / amp are k_diag's
+// arithmetic, bit for bit, in k_diag_mr's form (the row image in LDS, the
+// PwPlan's chains and leaf sums spread over the group, the post-order adds in
+// the lanes of the first wave).  fftmax replaces the direct O(n^2) DFT by a
+// chirp-z (Bluestein) transform in f64 (diag_czt.py states it in numpy):
+//   even n: Z = DFT_m of z[q] = v[2q] + i v[2q+1], m = n/2 (odd m included),
+//           then the conjugate-pair step over k = 0 .. m/2 (spec_pair_nan: for
+//           an odd m no bin pairs with itself, and the pairs (k, m - k) of
+//           k <= (m-1)/2 still cover 0 .. m);
+//   odd n:  DFT_n of the real row, bins 0 .. (n-1)/2;
+//   DFT_m:  a = z w zero-padded to L = czt_length(m), A = FFT_L(a), times the
+//           per-length filter B / L, the inverse FFT_L as the conjugate of a
+//           forward one, times w: Z_k = w_k conj(c_k), w_j = exp(-i pi j^2/m).
+//           |w| = 1, so the odd lengths take |c_k| directly.
+// The per-length tables (DiagArgs.czt, f64 pairs): [L] exp(-2 pi i q/L), [L]
+// B / L, [m] w.  The FFT_L are mr_plan(2 L)'s radix 8 / 4 / 2 Stockham stages, in
+// place over one work array per group at mr_pad (k_diag_mr's stage); the first
+// stage of each FFT forms its input on the fly (a from the row image, which
+// the work array then overwrites; conj(A B) from the array itself).  A group is
+// one wave while L <= 512, with the twiddles of L in LDS (MW = false), and
+// L/512 = 2 .. 8 waves above, with the twiddles read through L1/L2 (MW = true):
+// the work array bounds the profiles a CU holds, so more waves around one
+// array is what fills the SIMDs, and 8 points per thread is what fits the
+// registers without a spill.  B and w are read from global memory by every
+// profile and stay cache-resident.  PPT: points of the work array a thread
+// holds (L <= 64 W PPT), which is also the samples of the row it holds (n <=
+// L).  Nothing depends on the launch.
+__host__ __device__ inline MrLayout czt_layout(int n, int L, bool mw, bool d64, bool closed)
+{
+    MrLayout lay;
+    const int nlub = n / 64 + 1;   // leaves hold >= 64 samples
+    lay.tw_bytes = mw ? 0 : (size_t)L * 16;
+    lay.plan_off = lay.tw_bytes;
+    lay.groups_off = lay.plan_off + (((size_t)nlub * 8 + 15) & ~(size_t)15);
+    const size_t cb = (size_t)(L + L / 8 + 1) * 16, xb = (size_t)n * (d64 ? 8 : 4);
+    const size_t work = ((cb > xb ? cb : xb) + 15) & ~(size_t)15;
+    lay.p_off = work;
+    lay.acc_off = lay.p_off + (closed ? (((size_t)n * 4 + 15) & ~(size_t)15) : 0);
+    lay.red_off = lay.acc_off + (size_t)nlub * 64;   // 8 chain sums of 8 B per leaf
+    lay.per_group = lay.red_off + 40 * 8;   // k_diag_czt's partials: up to 8 waves
+    return lay;
+}
+
+// mr_pairwise without its limit of 32 leaves (4094 bins have 33): slot s of the
+// plan lives in lane s & 63 of the group's first wave, register s >> 6, so up
+// to 64 leaves and 128 slots.  The same chains, leaf sums and post-order adds,
+// so the same bits.
+template <bool MW, typename Tp, typename Get>
+__device__ __forceinline__ Tp czt_pairwise(const MrPlan &pl, Get get, Tp *acc, Tp *res, int t, int tpp)
+{
+    const int nl = pl.nl;
+    for (int task = t; task < nl * 8; task += tpp) {
+        const int Lf = task >> 3, j = task & 7;
+        const int st = pl.ls[Lf], len = pl.ll[Lf];
+        const int main = len - len % 8;
+        Tp r = get(st + j);
+        for (int q = 8; q < main; q += 8) r = r + get(st + q + j);
+        acc[task] = r;
+    }
+    gsync<MW ? 2 : 1>();
+    Tp v0 = (Tp)0, v1 = (Tp)0;
+    if (t < nl) {
+        const int st = pl.ls[t], len = pl.ll[t];
+        const Tp *r = acc + t * 8;
+        const Tp a01 = r[0] + r[1], a23 = r[2] + r[3], a45 = r[4] + r[5], a67 = r[6] + r[7];
+        const Tp lo = a01 + a23, hi = a45 + a67;
+        v0 = lo + hi;
+        for (int q = len - len % 8; q < len; ++q) v0 = v0 + get(st + q);
+    }
+    Tp out = (Tp)0;
+    if (!MW || t < 64) {   // slot[nl + o] = slot[op_a[o]] + slot[op_b[o]]
+        const auto slot = [&](int s) { return s < 64 ? lane_read(v0, s) : lane_read(v1, s - 64); };
+        for (int o = 0; o < pl.nops; ++o) {
+            const int ab = __builtin_amdgcn_readlane(pl.opv, o);
+            const Tp s = slot(ab & 0xffff) + slot(ab >> 16);
+            const int d = nl + o;
+            if (t == d) v0 = s;
+            if (t == d - 64) v1 = s;
+        }
+        out = (Tp)0 + slot(pl.root);
+    }
+    if constexpr (MW) {
+        if (t == 0) res[0] = out;
+        __syncthreads();
+        out = res[0];
+    }
+    return out;
+}
+
+// One radix-R Stockham stage of the group's FFT_L (L and ns powers of two), in
+// place: butterfly j < G = L/R takes the points get(j + q G) into registers,
+// multiplies by tw[q k step] (k = j mod ns, step = L/(R ns); not in a first
+// stage, ns = 1) and, once the whole group has read, writes DFT_R's y_p to
+// point (j - k) R + k + p ns.
+template <int R, int PPT, bool MW, typename Get>
+__device__ __forceinline__ void czt_stage(double2 *C, Get get, const double2 *tw, int L, int step, int ns, int t,
+                                          int tpp)
+{
+    constexpr int BPT = (PPT + R - 1) / R;   // butterflies a thread holds
+    const int G = L / R;
+    double2 v[BPT][R];
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const int j = t + tpp * u;
+        if (j < G) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) v[u][q] = get(j + q * G);
+        }
+    }
+    gsync<MW ? 2 : 1>();
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const int j = t + tpp * u;
+        if (j < G) {
+            const int k = j & (ns - 1);
+            if (ns > 1) {
+                double2 w[R];
+#pragma unroll
+                for (int q = 1; q < R; ++q) w[q] = tw[q * k * step];
+#pragma unroll
+                for (int q = 1; q < R; ++q) v[u][q] = cmul_f(v[u][q], w[q]);
+            }
+            dft_small<R>(v[u]);
+            const int o = (j - k) * R + k;
+#pragma unroll
+            for (int p = 0; p < R; ++p) C[mr_pad(o + p * ns)] = v[u][p];
+        }
+    }
+    gsync<MW ? 2 : 1>();
+}
+
+template <int PPT, bool MW, bool D64>
+__global__ __launch_bounds__(512, 3) void k_diag_czt(DiagArgs a, unsigned long long radices,
+                                                                             int nst, int L)
+{
+    using XT = typename std::conditional<D64, double, float>::type;
+    extern __shared__ __attribute__((aligned(16))) unsigned char cz_sm[];
+    const int n = a.nbin;
+    const bool even = !(n & 1);
+    const int m = even ? n >> 1 : n;          // the Bluestein DFT's length
+    const int H = even ? m >> 1 : n >> 1;     // the last pair task (even n) / bin (odd n)
+    const int mode = a.mode;
+    const int lane = threadIdx.x & 63;
+    const int tpp = MW ? (int)blockDim.x : 64;
+    int t = MW ? (int)threadIdx.x : lane;
+    const int group = MW ? 0 : (int)(threadIdx.x >> 6);
+    const int gpb = MW ? 1 : (int)(blockDim.x >> 6);
+    const MrLayout lay = czt_layout(n, L, MW, D64, mode == DIAG_CLOSED);
+    const double2 *tw = MW ? a.czt : (const double2 *)cz_sm;   // exp(-2 pi i q/L)
+    const double2 *Bf = a.czt + L;                             // the filter, scaled by 1/L
+    const double2 *ch = a.czt + 2 * (size_t)L;                 // the chirp w[m]
+    MrPlan pl;
+    {
+        int32_t *ls = (int32_t *)(cz_sm + lay.plan_off);
+        const int nl = a.plan->nleaf;
+        int32_t *ll = ls + nl;
+        if (!MW)
+            for (int q = threadIdx.x; q < L; q += blockDim.x) ((double2 *)cz_sm)[q] = a.czt[q];
+        for (int q = threadIdx.x; q < nl; q += blockDim.x) {
+            ls[q] = a.plan->leaf_start[q];
+            ll[q] = a.plan->leaf_len[q];
+        }
+        pl.ls = ls;
+        pl.ll = ll;
+        pl.nl = nl;
+        pl.nops = a.plan->nops;
+        pl.root = a.plan->root;
+        pl.opv = lane < pl.nops ? (a.plan->op_a[lane] | (a.plan->op_b[lane] << 16)) : 0;
+        __syncthreads();
+    }
+    unsigned char *gb = cz_sm + lay.groups_off + (size_t)group * lay.per_group;
+    XT *X = (XT *)gb;
+    double2 *C = (double2 *)gb;   // takes X's place once the first stage has read it
+    float *Pr = (float *)(gb + lay.p_off);
+    double *acc = (double *)(gb + lay.acc_off);
+    double *red = (double *)(gb + lay.red_off);
+    const unsigned P = (unsigned)a.nsub * (unsigned)a.nchan;
+    const unsigned stride = gridDim.x * gpb;
+    const double *T64 = a.T64;
+    // profiles: all P, or the slots of a list, minus those with skip[k] != 0
+    const RoundList rl(a.list, a.nctr, (long)P);
+    const unsigned nslot = (unsigned)rl.n();
+    const uint8_t *skip = a.skip;
+    for (unsigned slot = blockIdx.x * gpb + group; slot < nslot; slot += stride) {
+        const unsigned k = (unsigned)rl.at(slot);
+        if (skip && skip[k]) continue;   // group-uniform
+        // opaque to the optimiser: the stages' LDS addresses derive from t (k_diag_p2)
+        asm volatile("" : "+v"(t));
+        const float w = a.w0[k];
+        const bool valid = (w != 0.0f);
+        const int sh = mode == DIAG_STATS ? 0 : a.shift[k % (unsigned)a.nchan];
+        const bool tr = a.dtiled && mode == DIAG_EXACT;   // the tiled fit cube (dt_ofs)
+        // every global load of the row in flight at once: CLOSED the raw row
+        // (dispersed order j), otherwise the fit cube / given row (order i)
+        float pv[PPT];
+#pragma unroll
+        for (int u = 0; u < PPT; ++u) {
+            const int i = t + tpp * u;
+            pv[u] = 0.0f;
+            if (i < n) {
+                if (mode == DIAG_CLOSED) pv[u] = a.raw[(size_t)k * n + i];
+                else pv[u] = a.D[d_ofs(k, i, a.ldD, tr)];
+            }
+        }
+        double x = 0.0;
+        int stt = 0;
+        gsync<MW ? 2 : 1>();   // the previous profile's LDS reads are done
+        if (mode == DIAG_CLOSED) {
+            // the fit-cube row f32(ded - base0), dedispersed order, then the
+            // closed-form amplitude from numpy pairwise sums over the stored
+            // (dispersed) order j: bin i = (j - sh) mod n
+            const float b = a.base[k];
+#pragma unroll
+            for (int u = 0; u < PPT; ++u) {
+                const int j = t + tpp * u;
+                if (j < n) {
+                    int i = j - sh;
+                    if (i < 0) i += n;
+                    Pr[i] = pv[u] - b;
+                }
+            }
+            gsync<MW ? 2 : 1>();
+            const double dot = czt_pairwise<MW, double>(pl, [&](int q) {
+                int i = q - sh;
+                if (i < 0) i += n;
+                return T64[i] * (double)Pr[i];
+            }, acc, red, t, tpp);
+            const double TT = *a.TT;
+            x = TT != 0.0 ? dot / TT : 0.0;
+            stt = isfinite(x) ? 1 : 5;
+            if (t == 0) {
+                a.amp[k] = x;
+                a.info[k] = stt;
+            }
+#pragma unroll
+            for (int u = 0; u < PPT; ++u) {
+                const int i = t + tpp * u;
+                if (i < n) pv[u] = Pr[i];
+            }
+        } else if (mode == DIAG_EXACT) {
+            x = a.amp[k];
+            stt = a.info[k];
+        }
+        const bool ok = fit_ok(stt);
+        // residual -> X (dispersed frame): X[j] = f32(f32(r[i]) * w), j = (i + sh) mod n
+        // (f64(f32(r[i])) * f64(w) for f64 data); the thread keeps its values for the ptp
+        XT xv[PPT];
+#pragma unroll
+        for (int u = 0; u < PPT; ++u) {
+            const int i = t + tpp * u;
+            xv[u] = (XT)0;
+            if (i < n) {
+                float R = 0.0f;
+                if (mode == DIAG_STATS) R = pv[u];
+                else if (ok) R = residual_sample(x, T64[i], pv[u], i, a);
+                int j = i + sh;
+                if (j >= n) j -= n;
+                if constexpr (D64) xv[u] = (double)R * (double)w;
+                else xv[u] = R * w;
+                X[j] = xv[u];
+            }
+        }
+        gsync<MW ? 2 : 1>();
+        double mean = 0.0, sd = 0.0, fftv = 0.0, ptp = ptp_fill(D64);
+        // a non-finite sample: fftmax is NaN (numpy's rfft spreads it over every bin)
+        int nanx = 0;
+#pragma unroll
+        for (int u = 0; u < PPT; ++u)
+            if (t + tpp * u < n) nanx |= !isfinite(xv[u]);
+        if (valid) {
+            // mean: pairwise sum in the data dtype; var: f64 pairwise sum of (f64(X) - mean)^2
+            const XT s = czt_pairwise<MW, XT>(pl, [&](int q) { return X[q]; }, (XT *)acc, (XT *)red, t, tpp);
+            mean = (double)s / (double)n;
+            const double mu = mean;
+            const double ss = czt_pairwise<MW, double>(pl, [&](int q) {
+                const double d = (double)X[q] - mu;
+                return d * d;
+            }, acc, red + 1, t, tpp);
+            sd = sqrt(ss / (double)n);
+            // ptp (NaN-propagating), max - min in the data dtype
+            XT mx = -INFINITY, mn = INFINITY;
+            int nan = 0;
+#pragma unroll
+            for (int u = 0; u < PPT; ++u) {
+                if (t + tpp * u < n) {
+                    nan |= isnan(xv[u]);
+                    mx = OpMaxF()(mx, xv[u]);
+                    mn = OpMinF()(mn, xv[u]);
+                }
+            }
+            mx = mr_tree<MW>(mx, OpMaxF(), (XT *)(red + 2), t, tpp);
+            mn = mr_tree<MW>(mn, OpMinF(), (XT *)(red + 10), t, tpp);
+            nan = mr_tree<MW>(nan, OpOr(), (int *)(red + 18), t, tpp);
+            ptp = nan ? (double)NAN : (double)(XT)(mx - mn);
+            // a = (f64(X) - mean as complex pairs, or as a real row) w, zero-padded to L
+            const auto in = [&](int p) -> double2 {
+                if (p >= m) return make_double2(0.0, 0.0);
+                const double2 wv = ch[p];
+                if (even) return cmul_f(make_double2((double)X[2 * p] - mu, (double)X[2 * p + 1] - mu), wv);
+                const double re = (double)X[p] - mu;
+                return make_double2(re * wv.x, re * wv.y);
+            };
+            // conj(A B / L): the inverse FFT_L is the conjugate of a forward one of this
+            const auto mid = [&](int p) -> double2 {
+                const double2 y = cmul_f(C[mr_pad(p)], Bf[p]);
+                return make_double2(y.x, -y.y);
+            };
+            const auto pt = [&](int p) -> double2 { return C[mr_pad(p)]; };
+            for (int f = 0; f < 2; ++f) {
+                int ns = 1, step = L;
+                for (int st = 0; st < nst; ++st) {
+                    const int R = (int)((radices >> (4 * st)) & 15);
+                    step /= R;
+                    if (st == 0) {   // L >= 16: the first radix is 8
+                        if (f == 0) czt_stage<8, PPT, MW>(C, in, tw, L, step, ns, t, tpp);
+                        else czt_stage<8, PPT, MW>(C, mid, tw, L, step, ns, t, tpp);
+                    } else {
+                        switch (R) {
+                        case 8: czt_stage<8, PPT, MW>(C, pt, tw, L, step, ns, t, tpp); break;
+                        case 4: czt_stage<4, PPT, MW>(C, pt, tw, L, step, ns, t, tpp); break;
+                        default: czt_stage<2, PPT, MW>(C, pt, tw, L, step, ns, t, tpp); break;
+                        }
+                    }
+                    ns *= R;
+                }
+            }
+            // C holds c_k = conj(y_k), and Z_k = w_k y_k.  Even n: the real spectrum in
+            // conjugate bin pairs (k_diag_p2), 2 X_k and 2 X_(m-k) from Z_k, Z_(m-k) and
+            // exp(-2 pi i k/n), k = 0 .. m/2; odd n: |X_k| = |c_k|, k = 0 .. (n-1)/2
+            double best2 = 0.0, nsum = 0.0;
+            if (even) {
+                const auto Z = [&](int q) -> double2 {
+                    const double2 c = C[mr_pad(q)];
+                    return cmul_f(make_double2(c.x, -c.y), ch[q]);
+                };
+                for (int kk = t; kk <= H; kk += tpp)
+                    spec_pair_nan(Z(kk), Z(kk == 0 ? 0 : m - kk), a.tw[kk], best2, nsum);
+            } else {
+                for (int kk = t; kk <= H; kk += tpp) {
+                    const double2 c = C[mr_pad(kk)];
+                    const double a2 = __builtin_fma(c.x, c.x, c.y * c.y);
+                    nsum = nsum + a2;
+                    best2 = fmax(best2, a2);
+                }
+            }
+            int nanf = isnan(nsum) | nanx;
+            best2 = mr_tree<MW>(best2, OpMaxF(), red + 22, t, tpp);
+            nanf = mr_tree<MW>(nanf, OpOr(), (int *)(red + 30), t, tpp);
+            fftv = nanf ? NAN : (even ? 0.5 * sqrt(best2) : sqrt(best2));
+        } else {
+            // invalid: rfft of f64(X) = +-0 -> 0, unless R was non-finite (X NaN)
+            nanx = mr_tree<MW>(nanx, OpOr(), (int *)(red + 18), t, tpp);
+            fftv = nanx ? NAN : 0.0;
+        }
+        if (t == 0) diag_store(a, k, valid, mean, sd, ptp, fftv);
+    }
+}
+
 // residual cube on request (ic_get_residual): R (dispersed frame, unweighted).
 // D == nullptr (fit_mode 1 keeps no fit cube): the fit-cube row is formed from
 // raw and the w0 baseline as in k_chan_partials mode 3, f32(ded - base).
@@ -1491,6 +1855,39 @@ static hipError_t launch_mr(hipStream_t st, const DiagArgs &a, size_t P)
 #undef IC_DIAG_MR
 }
 
+// k_diag_czt serves the chirp-z lengths in every mode but DIAG_FIT
+static bool uses_czt(const DiagArgs &a)
+{
+    return diag_czt_supported(a.nbin) && (a.mode == DIAG_EXACT || a.mode == DIAG_CLOSED || a.mode == DIAG_STATS);
+}
+
+static hipError_t launch_czt(hipStream_t st, const DiagArgs &a, size_t P)
+{
+    const int n = a.nbin, L = diag_czt_length(n);
+    unsigned long long radices = 0;
+    const int nst = mr_plan(2 * L, &radices);   // FFT_L: radix 8 while three levels remain, then 4 or 2
+    // the tables are the caller's (the session's, or a one-shot scratch); the
+    // pairwise adds run in two registers of the lanes of one wave (czt_pairwise)
+    if (!a.czt || !nst || 2 * pairwise_leaves(n) > 128) return hipErrorInvalidValue;
+    const int W = (L + 511) / 512;   // waves around one work array: 8 points per thread
+    const bool mw = W > 1, d64 = a.data_f64 != 0, small = L <= 256;
+    const MrLayout lay = czt_layout(n, L, mw, d64, a.mode == DIAG_CLOSED);
+    const int gpb = mw ? 1 : mr_groups_per_block(lay, 12);   // __launch_bounds__: 3 waves per SIMD
+    const size_t shm = lay.groups_off + gpb * lay.per_group;
+    if (shm > kLdsBlockMax) return hipErrorInvalidValue;
+    const dim3 grid(cap_grid(std::min<size_t>((P + gpb - 1) / gpb, 4096), a.grid_cap)), block(64 * (mw ? W : gpb));
+#define IC_DIAG_CZT(PPT, MW)                                                                       \
+    do {                                                                                           \
+        if (d64) IC_GGL((k_diag_czt<PPT, MW, true>), grid, block, shm, st, a, radices, nst, L);    \
+        else IC_GGL((k_diag_czt<PPT, MW, false>), grid, block, shm, st, a, radices, nst, L);       \
+        return hipGetLastError();                                                                  \
+    } while (0)
+    if (mw) IC_DIAG_CZT(8, true);
+    if (small) IC_DIAG_CZT(4, false);
+    IC_DIAG_CZT(8, false);
+#undef IC_DIAG_CZT
+}
+
 static bool uses_cl(const DiagArgs &a)
 {
     if (!a.chain || a.data_f64 || !(a.nbin == 1024 || a.nbin == 2048 || a.nbin == 4096)) return false;
@@ -1500,13 +1897,13 @@ static bool uses_cl(const DiagArgs &a)
     return (a.mode == DIAG_EXACT || a.mode == DIAG_CLOSED) && a.T2 && a.raw && a.base && !a.pr_on;
 }
 
-// profile lists / skips: k_diag_cl, and k_diag_p2 / k_diag_mr in the exact
-// mode and on given rows (the FFT mode's rotated residuals)
+// profile lists / skips: k_diag_cl, and k_diag_p2 / k_diag_mr / k_diag_czt in
+// the exact mode and on given rows (the FFT mode's rotated residuals)
 bool diag_list_supported(const DiagArgs &a)
 {
     const int n = a.nbin;
     return uses_cl(a) ||
-           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && (p2_supported(n) || mr_supported(n)));
+           ((a.mode == DIAG_EXACT || a.mode == DIAG_STATS) && (p2_supported(n) || mr_supported(n) || diag_czt_supported(n)));
 }
 
 // the generic k_diag's LDS layout as the host sizes it: nleaf/nops upper bound
@@ -1542,6 +1939,7 @@ hipError_t launch_diag(hipStream_t st, const DiagArgs &a)
     IC_P2_SIZES(IC_P2)
 #undef IC_P2
     if (a.mode == DIAG_FIT) return hipErrorInvalidValue;   // power-of-two nbin only
+    if (uses_czt(a)) return launch_czt(st, a, P);
     const DiagLayout lay = generic_layout(nbin);
     const size_t fixed = (size_t)lay.ntw * 16;
     int wpb = 4;
@@ -1559,6 +1957,11 @@ size_t diag_lds_bytes(int nbin)
     if (mr_supported(nbin)) {   // k_diag_mr's largest form: one group, f64 data, the closed mode's row
         const MrLayout L = mr_layout(nbin, nbin > 1024, true, true);
         return L.groups_off + L.per_group;
+    }
+    if (diag_czt_supported(nbin)) {   // k_diag_czt's largest form, likewise
+        const int L = diag_czt_length(nbin);
+        const MrLayout lay = czt_layout(nbin, L, L > 512, true, true);
+        return lay.groups_off + lay.per_group;
     }
     const DiagLayout lay = generic_layout(nbin);
     return (size_t)lay.ntw * 16 + lay.per_wave;

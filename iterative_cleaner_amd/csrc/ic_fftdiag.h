@@ -1,5 +1,5 @@
 // ic_fftdiag.h -- device-only code that the diagnostics (ic_diag.hip:
-// k_diag, k_diag_p2, k_diag_cl, k_diag_mr) and the rotation (ic_rotate.hip: k_rotate,
+// k_diag, k_diag_p2, k_diag_cl, k_diag_mr, k_diag_czt) and the rotation (ic_rotate.hip: k_rotate,
 // whose fused statistics rot_stats are k_diag_cl's, and k_rotate_mr) share:
 // the f64 FFT pieces, the P2 / CLay profile-group layouts with their LDS
 // address maps, the group reductions, the compile-time Stockham chain, and

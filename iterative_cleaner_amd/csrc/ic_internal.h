@@ -350,6 +350,29 @@ inline int czt_length(int nbin)
 // floats of the per-length tables (RotateArgs.czt): f32 pairs [L] tw =
 // exp(-2 pi i q / L), [L] the filter B, [nbin] the chirp w
 inline size_t czt_table_floats(int nbin) { return 2 * (2 * (size_t)czt_length(nbin) + (size_t)nbin); }
+// The chirp-z statistics FFT (k_diag_czt, in both dedispersion modes;
+// diag_czt.py): the lengths of czt_supported, narrowed by kDiagCztMin, below
+// which the generic k_diag's direct DFT is faster per launch (measured: 0.67
+// against 0.75 ms at 127 bins, 1.04 against 0.79 at 129; DESIGN.md,
+// "Diagnostics at the other lengths"), and by the odd lengths above kDiagCztOddMax, whose
+// convolution length 8192 needs a 144-KiB work array per profile.  Lengths
+// outside it keep the generic k_diag.  This is the one place the set lives:
+// launch_diag, diag_list_supported, diag_lds_bytes and the session's table
+// allocation read it.  The transform is a DFT of nbin/2 complex points for an
+// even nbin and of nbin real points for an odd one.
+constexpr int kDiagCztMin = 129, kDiagCztOddMax = 2048;
+inline bool diag_czt_supported(int nbin)
+{
+    return czt_supported(nbin) && nbin >= kDiagCztMin && !((nbin & 1) && nbin > kDiagCztOddMax);
+}
+inline int diag_czt_points(int nbin) { return (nbin & 1) ? nbin : nbin / 2; }
+inline int diag_czt_length(int nbin) { return czt_length(diag_czt_points(nbin)); }
+// f64 pairs of the per-length tables (DiagArgs.czt): [L] tw = exp(-2 pi i q / L),
+// [L] the filter B / L, [m] the chirp w, L = diag_czt_length, m = diag_czt_points
+inline size_t diag_czt_table_entries(int nbin)
+{
+    return 2 * (size_t)diag_czt_length(nbin) + (size_t)diag_czt_points(nbin);
+}
 #define IC_CZT_NBIN_FMT "; IC_DEDISP_FFT_ANY also serves any other nbin in %d..%d"
 #define IC_CZT_NBIN_ARGS ::icgpu::kCztMin, ::icgpu::kCztMax
 // the lengths the FFT dedispersion serves, for the error texts:
@@ -359,8 +382,9 @@ inline size_t czt_table_floats(int nbin) { return 2 * (2 * (size_t)czt_length(nb
 #define IC_ROT_NBIN_ARGS ::icgpu::kP2Min, ::icgpu::kP2Max, ::icgpu::kMrMin, ::icgpu::kMrMax
 
 // Diagnostics kernels (k_diag_p2<N> / k_diag_cl<N> for the power-of-two nbin
-// above, k_diag_mr for the mixed-radix set, the generic k_diag otherwise: 100,
-// 500, ...).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
+// above, k_diag_mr for the mixed-radix set, k_diag_czt for the other lengths in
+// 129..4096 (diag_czt_supported: 250, 500, 997, 2500, ...), the generic k_diag
+// for what is left: 100, 125, the odd lengths above 2048).  mode: DIAG_EXACT = residual from the exact fit's amp/info and
 // the fit cube D (row stride ldD); DIAG_CLOSED = fit_mode 1, the closed-form
 // amplitude sum(T*p)/TT from raw + base (written to amp/info), then the same
 // residual; DIAG_STATS = comprehensive_stats of the rows of D alone (no shift).
@@ -368,9 +392,9 @@ inline size_t czt_table_floats(int nbin) { return 2 * (2 * (size_t)czt_length(nb
 // DIAG_FIT = the closed-form amplitude alone (amp/info) of the rows of D (no
 // shift, no level): fit_mode 1 with fractional dedispersion, whose residual is
 // then rotated back and measured in DIAG_STATS; power-of-two nbin only.
-// list / nctr / skip: the power-of-two and mixed-radix kernels in DIAG_EXACT
-// and DIAG_STATS, k_diag_cl in its modes (diag_list_supported); the generic
-// k_diag measures every profile.
+// list / nctr / skip: the power-of-two, mixed-radix and chirp-z kernels in
+// DIAG_EXACT and DIAG_STATS, k_diag_cl in its modes (diag_list_supported); the
+// generic k_diag measures every profile.
 enum DiagMode { DIAG_EXACT = 0, DIAG_CLOSED = 1, DIAG_STATS = 2, DIAG_FIT = 3 };
 struct DiagArgs {
     int mode;
@@ -399,6 +423,9 @@ struct DiagArgs {
     const uint8_t *skip = nullptr;   // != nullptr: profiles with skip[k] != 0 are left out
     int chain = 1;   // 0: the row-layout k_diag_p2 at nbin 1024/2048/4096 too (IC_OPT_DIAG_CHAIN)
     int grid_cap = 0;   // > 0: at most this many blocks (IC_OPT_GRID_CAP; read by the launcher only)
+    // k_diag_czt's per-length tables (diag_czt_table_entries); required where
+    // diag_czt_supported(nbin), unused elsewhere
+    const double2 *czt = nullptr;
 };
 hipError_t launch_diag(hipStream_t st, const DiagArgs &a);
 // the diagnostics kernel launch_diag picks for `a` takes a profile list

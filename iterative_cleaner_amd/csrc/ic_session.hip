@@ -280,6 +280,7 @@ struct Session {
     int32_t *zshift = nullptr;
     float *ph = nullptr;   // f32 pairs
     float *czt = nullptr;  // IC_DEDISP_FFT_ANY at a chirp-z length: the per-length tables (czt_tables)
+    double2 *dczt = nullptr;   // diag_czt_supported(nbin): k_diag_czt's per-length tables (diag_czt_tables)
     double *dly = nullptr;           // [P] the session's delays on the device (first need): the channel
                                      // row k_phasor_table reads, or the per-profile delays
     double *delay2 = nullptr;        // = dly while per-profile delays are in force, else nullptr
@@ -583,6 +584,28 @@ std::vector<float> czt_tables(int n)
     put(tw);
     put(b);
     put(w);
+    return t;
+}
+
+// k_diag_czt's per-length tables (DiagArgs.czt; diag_czt.py chirp / filter),
+// f64 pairs: [L] tw = exp(-2 pi i q / L), [L] the filter B / L with B = FFT_L(b),
+// b[j] = b[L - j] = conj(w[j]), j < m (the scale is a power of two: exact), [m]
+// the chirp w[j] = exp(-i pi (j^2 mod 2m) / m); m = diag_czt_points(n), L =
+// diag_czt_length(n)
+std::vector<double2> diag_czt_tables(int n)
+{
+    const int m = diag_czt_points(n), L = diag_czt_length(n);
+    std::vector<double2> t = host_twiddles(L), w(m), b(L, make_double2(0.0, 0.0));
+    for (int j = 0; j < m; ++j) {
+        w[j] = unit_root((long double)(((long long)j * j) % (2 * m)), (long double)(2 * m));
+        b[j] = b[(L - j) % L] = make_double2(w[j].x, -w[j].y);
+    }
+    stockham64(b, t);
+    const double sc = 1.0 / (double)L;
+    for (double2 &e : b) e = make_double2(e.x * sc, e.y * sc);
+    t.reserve(diag_czt_table_entries(n));
+    t.insert(t.end(), b.begin(), b.end());
+    t.insert(t.end(), w.begin(), w.end());
     return t;
 }
 
@@ -1332,6 +1355,12 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
     AL(s->tw, (size_t)nbin);
     AL(s->tw_p2, (size_t)nbin);
     AL(s->plan, 1);
+    if (diag_czt_supported(nbin)) {
+        const std::vector<double2> dt = diag_czt_tables(nbin);
+        AL(s->dczt, dt.size());
+        if (hipMemcpy(s->dczt, dt.data(), sizeof(double2) * dt.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return bail(fail(IC_EHIP, "upload of the chirp-z statistics tables failed"));
+    }
     if (exact) AL(s->lists, 3 * P);   // two ping-pong round lists + the fork round's survivors
     AL(s->rcount, (size_t)kRoundWords + 4);   // + two spare words and the tail's sweep counter
     if (exact) AL(s->late, P);
@@ -1860,6 +1889,7 @@ DiagArgs diag_args(Session *s, int pr_start, int pr_end)
     a.data_f64 = p.data_f64 != 0;
     a.chain = s->diag_chain ? 1 : 0;
     a.grid_cap = s->grid_cap;
+    a.czt = s->dczt;
     return a;
 }
 
@@ -2514,6 +2544,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     PwPlan plan;
     if (make_plan(nbin, &plan) != 0) return fail(IC_EINVAL, "pairwise plan too large for nbin=%d", nbin);
     const std::vector<double2> tw = host_twiddles(nbin), tw2 = p2_twiddles(nbin);
+    const std::vector<double2> dt = diag_czt_supported(nbin) ? diag_czt_tables(nbin) : std::vector<double2>();
     Scratch sc;
     CK(sc.open_stream());
     hipStream_t st = sc.stream;
@@ -2521,7 +2552,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     uint8_t *valid;
     double *sd, *mn, *ff, *pt, *test, *lstat;
     int32_t *cnt;
-    double2 *dtw, *dtw2;
+    double2 *dtw, *dtw2, *ddt;
     PwPlan *dplan;
     struct {
         void **p;
@@ -2530,7 +2561,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
               {(void **)&hist, 8 * P},  {(void **)&sd, 8 * P},   {(void **)&mn, 8 * P}, {(void **)&ff, 8 * P},
               {(void **)&pt, 8 * P},    {(void **)&test, 8 * P}, {(void **)&lstat, 8 * 16 * ((size_t)nsub + nchan)},
               {(void **)&cnt, 4 * 8},   {(void **)&dtw, 16 * (size_t)nbin}, {(void **)&dtw2, 16 * (size_t)nbin + 16},
-              {(void **)&dplan, sizeof plan}};
+              {(void **)&dplan, sizeof plan}, {(void **)&ddt, 16 * dt.size()}};
     for (auto &x : al)
         if (sc.mem.alloc_bytes(x.p, x.bytes + 16) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(%zu) failed", x.bytes);
     CK(hipMemcpyAsync(D, data, 4 * N, hipMemcpyHostToDevice, st));
@@ -2538,6 +2569,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     CK(hipMemcpyAsync(dtw, tw.data(), 16 * (size_t)nbin, hipMemcpyHostToDevice, st));
     if (!tw2.empty()) CK(hipMemcpyAsync(dtw2, tw2.data(), 16 * tw2.size(), hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(dplan, &plan, sizeof plan, hipMemcpyHostToDevice, st));
+    if (!dt.empty()) CK(hipMemcpyAsync(ddt, dt.data(), 16 * dt.size(), hipMemcpyHostToDevice, st));
     CK(hipMemsetAsync(cnt, 0, 4 * 8, st));
     CK(launch_valid(st, w0, valid, W, hist, P));
     DiagArgs a{};
@@ -2548,6 +2580,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     a.tw = dtw;
     a.tw_p2 = dtw2;
     a.plan = dplan;
+    a.czt = dt.empty() ? nullptr : ddt;
     a.nsub = nsub;
     a.nchan = nchan;
     a.nbin = nbin;

@@ -246,15 +246,33 @@ int ic_decode_profiles(int device, int nsub, int npol, int nsum, int nchan, int 
  * ic_encode_profiles: the encode alone, in [nsub][nchan][nbin] f32 on the host.
  * Synchronous.
  * ic_get_residual_quantised: the last iteration's residual, the cube
- * ic_get_residual returns (a shard: its channel slice), materialised on the
- * device as there and encoded there; the f32 cube never reaches the host.
+ * ic_get_residual returns (a shard: its channel slice), encoded on the device;
+ * the f32 cube never reaches the host.  With integer shifts (nbin <= 8192) one
+ * kernel forms each row and encodes it and no f32 cube exists at all; with
+ * IC_DEDISP_FFT(_ANY) the rotated rows pass through a session-owned f32 cube.
  * IC_ESTATE before a completed iteration and on a failed session.  The first
  * call allocates the int16 / scale / offset staging on the device (2 nbin + 8
- * bytes per profile), kept until ic_session_destroy; IC_ENOMEM if that, or the
- * call's f32 temporary, fails. */
+ * bytes per profile; FFT modes: the f32 cube too), kept until
+ * ic_session_destroy; IC_ENOMEM if that fails.  It is
+ * ic_get_residual_quantised_async followed by ic_residual_wait. */
 int ic_encode_profiles(int device, int nsub, int nchan, int nbin, const float *in, int flags, int16_t *q,
                        float *scl, float *offs);
 int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, float *offs);
+/* Queue the last run's residual, encoded exactly as ic_get_residual_quantised
+ * encodes it, and its download into q/scl/offs (page-locked for the copy to
+ * overlap); returns when queued.  IC_ESTATE with no completed iteration.
+ * The encode runs on the session's stream, the copies on a download stream of
+ * the session's own (created at first use), so a following ic_run and the
+ * uploads of later archives proceed while the samples travel; an asynchronous
+ * upload into the input slot the encode still reads waits for the encode.
+ * q/scl/offs must stay allocated, and are undefined, until ic_residual_wait
+ * (or ic_session_destroy) returns.  A further call before the wait is allowed:
+ * its encode waits until the earlier download has left the staging, and one
+ * ic_residual_wait then covers both. */
+int ic_get_residual_quantised_async(void *session, int flags, int16_t *q, float *scl, float *offs);
+/* Wait until the queued residual download (if any) has landed; IC_OK when none
+ * is pending.  A wait that exceeds IC_OPT_SYNC_TIMEOUT_MS fails the session. */
+int ic_residual_wait(void *session);
 
 /* Run the cleaning loop to convergence or max_iter (iterative_cleaner.py:83-146).
  * Outputs (host, any may be NULL):

@@ -28,7 +28,7 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
            "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised",
-           "ic_rotate_profiles_any")
+           "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -150,6 +150,8 @@ def load_library(path: str = LIB_PATH):
     lib.ic_decode_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.ic_encode_profiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     lib.ic_get_residual_quantised.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.ic_get_residual_quantised_async.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.ic_residual_wait.argtypes = [vp]
     lib.ic_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     lib.ic_host_free.argtypes = [vp]
     lib.ic_host_free.restype = None
@@ -423,6 +425,25 @@ class GpuSession:
                                                        _ptr(offs)), "ic_get_residual_quantised")
         return q, scl, offs
 
+    def residual_quantised_async(self, q, scl, offs):
+        """Queue residual_quantised() into the caller's arrays
+        (ic_get_residual_quantised_async) and return: the encode runs behind the
+        last run(), the download beside whatever follows (the next run(), later
+        uploads).  q: C-contiguous int16 (nsub, nchan, nbin), native or '>i2'
+        (the dtype selects the byte order); scl, offs: C-contiguous f32 (nsub,
+        nchan).  Page-locked arrays (PinnedArray) let the copy overlap.  They
+        must stay alive, and hold nothing defined, until residual_wait() or
+        close() returns."""
+        check_residual_arrays(self.shape, q, scl, offs, "residual_quantised_async")
+        self._check(self.lib.ic_get_residual_quantised_async(self.h, 0 if q.dtype.isnative else Q_BIG_ENDIAN, _ptr(q),
+                                                             _ptr(scl), _ptr(offs)),
+                    "ic_get_residual_quantised_async")
+
+    def residual_wait(self):
+        """Wait until every queued residual download has landed
+        (ic_residual_wait); returns at once when none is pending."""
+        self._check(self.lib.ic_residual_wait(self.h), "ic_residual_wait")
+
     def template(self):
         out = np.empty(self.shape[2], np.float32)
         self._check(self.lib.ic_get_template(self.h, _ptr(out)), "ic_get_template")
@@ -615,6 +636,21 @@ def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=
     if rc != 0:
         raise NativeError("ic_comprehensive_stats: %s (rc=%d)" % (_err(lib), rc))
     return (test, (sd, mn, pt, ff)) if diagnostics else test
+
+
+def check_residual_arrays(shape, q, scl, offs, what):
+    """The destination of an asynchronous residual download, handed over as it
+    is (not copied): q C-contiguous int16 (native or '>i2') of the session's
+    shape, scl / offs C-contiguous f32 (nsub, nchan)."""
+    nsub, nchan, nbin = shape
+    f32 = np.dtype(np.float32)
+    if (not isinstance(q, np.ndarray) or q.dtype.kind != "i" or q.dtype.itemsize != 2
+            or q.shape != (nsub, nchan, nbin) or not q.flags.c_contiguous):
+        raise ValueError("%s needs C-contiguous int16 (native or '>i2') samples of shape %s"
+                         % (what, (nsub, nchan, nbin)))
+    for a in (scl, offs):
+        if not isinstance(a, np.ndarray) or a.dtype != f32 or a.shape != (nsub, nchan) or not a.flags.c_contiguous:
+            raise ValueError("%s needs C-contiguous float32 %s scl / offs arrays" % (what, (nsub, nchan)))
 
 
 class PinnedArray:

@@ -55,7 +55,57 @@ def _queue_upload(session, arrays, nsum):
         session.upload_async(*arrays[:3], **kw)
 
 
-def pipeline(session, items, fetch=True, nsum=1):
+def _residual_slots(session, residuals):
+    """The (q, scl, offs) triples one session downloads its residuals into,
+    checked (GpuSession.residual_quantised_async's rules): at least 2, because
+    one is in flight while the consumer still holds the one yielded before."""
+    slots = [tuple(t) for t in residuals]
+    if len(slots) < 2:
+        raise ValueError("residuals needs at least 2 (q, scl, offs) triples per session, not %d" % len(slots))
+    for t in slots:
+        if len(t) != 3:
+            raise ValueError("a residual slot is a (q, scl, offs) triple, not %d arrays" % len(t))
+        _native.check_residual_arrays(session.shape, *t, "residuals")
+    return slots
+
+
+class _ResidualQueue:
+    """One session's residual downloads, one in flight at a time.  queue(out)
+    after run() of archive k starts its encode and download into the next slot
+    (round-robin) and returns True - or False for a run without an iteration,
+    which has no residual (run_loop's rule).  land() waits for the download in
+    flight and returns its dict, now holding out["residual_q"] = (q, scl,
+    offs), or None.  Calling land() after the run of archive k+1 leaves the
+    download of k the whole of that run (and the upload of k+2) to overlap."""
+
+    def __init__(self, session, slots):
+        self.session, self.slots = session, slots
+        self.n = 0              # residuals queued so far
+        self.inflight = None    # (dict, slot index)
+
+    def next_slot(self):
+        return self.n % len(self.slots)
+
+    def queue(self, out):
+        if out.get("n_iter", 0) <= 0:
+            return False
+        j = self.next_slot()
+        self.session.residual_quantised_async(*self.slots[j])
+        self.n += 1
+        self.inflight = (out, j)
+        return True
+
+    def land(self):
+        if self.inflight is None:
+            return None, None
+        out, j = self.inflight
+        self.session.residual_wait()
+        self.inflight = None
+        out["residual_q"] = self.slots[j]
+        return out, j
+
+
+def pipeline(session, items, fetch=True, nsum=1, residuals=None):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -67,7 +117,31 @@ def pipeline(session, items, fetch=True, nsum=1):
     behind the archive's copy, and become the session's delays for that archive
     and after it.  The arrays must stay valid until their result is
     yielded (page-locked for the copies to overlap).  Yields the ic_run dicts in
-    order."""
+    order.
+
+    residuals: a sequence of at least 2 (q, scl, offs) triples, used round-robin
+    (GpuSession.residual_quantised_async: int16 native or '>i2' (nsub, nchan,
+    nbin), f32 (nsub, nchan); page-locked for the download to overlap).  After
+    run() of archive k its residual is encoded on the GPU and its download
+    queued; the dict of archive k is yielded with out["residual_q"] = (q, scl,
+    offs) once that has landed, which is after the clean of archive k+1 has
+    been issued: the download runs beside that clean and the upload of k+2.
+    The triple is valid until the generator is advanced twice more (with 2
+    slots: once more).  An archive whose run made no iteration has no
+    "residual_q"."""
+    rq = _ResidualQueue(session, _residual_slots(session, residuals)) if residuals is not None else None
+
+    def after_run(out):
+        if rq is None:
+            yield out
+            return
+        landed, _ = rq.land()
+        queued = rq.queue(out)   # before the yield: it travels while the consumer works on `landed`
+        if landed is not None:
+            yield landed
+        if not queued:
+            yield out
+
     it = iter(items)
     first = next(it, None)
     if first is None:
@@ -75,20 +149,29 @@ def pipeline(session, items, fetch=True, nsum=1):
     _queue_upload(session, first, nsum)
     for nxt in it:
         _queue_upload(session, nxt, nsum)
-        yield session.run(fetch)
-    yield session.run(fetch)
+        yield from after_run(session.run(fetch))
+    yield from after_run(session.run(fetch))
+    if rq is not None:
+        landed, _ = rq.land()
+        if landed is not None:
+            yield landed
 
 
 _EXITED = -2   # a worker's last message (run_lanes)
 
 
-def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1):
+def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1, residuals=None):
     """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
     each with or without trailing delays, as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
     session overlaps its next upload with its current run).  The arrays must
     stay valid until their result is yielded.  Yields the ic_run dicts in input
     order.  One session: exactly `pipeline`.
+
+    residuals: per session a sequence of at least 2 (q, scl, offs) triples, as
+    `pipeline`'s: every dict comes with out["residual_q"], a triple of its
+    lane, valid until the generator is advanced past it - a lane takes a slot
+    again only after the consumer has moved on from the result that held it.
 
     On a worker error, or when the consumer stops early (generator closed), the
     lanes stop: the `stop` event (created here if not given) is set, queued work
@@ -99,9 +182,19 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
     leaked, its session marked (`_ic_leaked`, handle dropped so nothing
     destroys it under the running call) and, with the arrays it was handed,
     kept in _LEAKED."""
+    if residuals is not None and len(residuals) != len(sessions):
+        raise ValueError("residuals needs one sequence of (q, scl, offs) triples per session (%d), not %d"
+                         % (len(sessions), len(residuals)))
     if len(sessions) == 1:
-        yield from pipeline(sessions[0], items, fetch, nsum)
+        yield from pipeline(sessions[0], items, fetch, nsum, None if residuals is None else residuals[0])
         return
+    rqs = None
+    if residuals is not None:
+        rqs = [_ResidualQueue(sess, _residual_slots(sess, r)) for sess, r in zip(sessions, residuals)]
+        # slot j of lane q is free: taken by the worker before it queues a
+        # download into it, given back by the consumer once it has moved on
+        slot_free = [[threading.Semaphore(1) for _ in rq.slots] for rq in rqs]
+    rslot = {}   # archive index -> (lane, slot) of its residual, until the consumer has moved on
     stop = stop if stop is not None else threading.Event()
     work = queue.Queue(maxsize=2 * len(sessions))
     done = queue.Queue()
@@ -110,14 +203,44 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
 
     def worker(lane, sess):
         pending = None   # index uploaded to this session, not yet run
+        rq = rqs[lane] if rqs is not None else None
+        flying = None    # index of the archive whose residual download is in flight
+
+        def land():
+            nonlocal flying
+            out, j = rq.land()
+            if out is not None:
+                rslot[flying] = (lane, j)
+                done.put((flying, out))
+                flying = None
+
+        def finish(idx, out):
+            """hand over a run's result: at once, or with residuals the one before it"""
+            nonlocal flying
+            if rq is None:
+                done.put((idx, out))
+                return
+            land()   # first: the consumer may need it to free the slot waited for below
+            sem = slot_free[lane][rq.next_slot()]
+            while out.get("n_iter", 0) > 0 and not sem.acquire(timeout=0.1):
+                if stop.is_set():
+                    return
+            if rq.queue(out):
+                flying = idx
+            else:
+                done.put((idx, out))
+
         try:
             while not stop.is_set():
                 try:
                     item = work.get_nowait()
                 except queue.Empty:
                     if pending is not None:   # nothing queued: run what we hold
-                        done.put((pending, sess.run(fetch)))
+                        finish(pending, sess.run(fetch))
                         pending = None
+                        continue
+                    if flying is not None:    # nothing to overlap it with: hand it over
+                        land()
                         continue
                     item = work.get()
                 if item is None or stop.is_set():
@@ -127,10 +250,12 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
                 del held[lane][:-3]             # an upload is consumed by the second run after it
                 _queue_upload(sess, arrays, nsum)
                 if pending is not None:
-                    done.put((pending, sess.run(fetch)))
+                    finish(pending, sess.run(fetch))
                 pending = idx
             if pending is not None and not stop.is_set():
-                done.put((pending, sess.run(fetch)))
+                finish(pending, sess.run(fetch))
+            if flying is not None and not stop.is_set():
+                land()
         except BaseException as e:  # noqa: BLE001 - re-raised by the consumer
             stop.set()
             done.put((-1, e))
@@ -174,6 +299,9 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
         while True:
             if nxt in ready:
                 yield ready.pop(nxt)
+                if nxt in rslot:          # the consumer has moved on: its residual's slot is free
+                    lane, j = rslot.pop(nxt)
+                    slot_free[lane][j].release()
                 nxt += 1
                 continue
             if live == 0:
@@ -212,7 +340,8 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1)
                 # rather than hang the caller's cleanup
                 sys.stderr.write("iterative_cleaner: batch lane %d still inside ic_run after %.0f s; "
                                  "leaking its session\n" % (q, limit))
-                _LEAKED.append((sess, getattr(sess, "h", None), list(held[q])))
+                _LEAKED.append((sess, getattr(sess, "h", None),
+                                list(held[q]) + (list(residuals[q]) if residuals is not None else [])))
                 if hasattr(sess, "h"):
                     sess.h = None
                 sess._ic_leaked = True
@@ -246,10 +375,28 @@ class _Ring:
                 p.close()
 
 
+class _ResultRing:
+    """`n` page-locked (q, scl, offs) slots for one lane's residual downloads:
+    int16 samples (nsub, nchan, nbin) of `dtype` ('>i2' or native), f32 scales
+    and offsets (nsub, nchan)."""
+
+    def __init__(self, n, nsub, nchan, nbin, dtype):
+        spec = [((nsub, nchan, nbin), dtype), ((nsub, nchan), np.float32), ((nsub, nchan), np.float32)]
+        self.slots = [tuple(_native.PinnedArray(shape, dt) for shape, dt in spec) for _ in range(n)]
+
+    def triples(self):
+        return [tuple(p.array for p in slot) for slot in self.slots]
+
+    def close(self):
+        for slot in self.slots:
+            for p in slot:
+                p.close()
+
+
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
-                any_length=None):
+                any_length=None, residuals=False, residual_big_endian=True):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -274,7 +421,20 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     ValueError, as does one with delays when dedisp is "shift".
     input_dedispersed, fit_mode, options (a dict of schedule options) and
     any_length (None = the IC_ANY_NBIN switch: IC_DEDISP_FFT_ANY, any nbin in
-    16..4096) are handed to every lane's GpuSession."""
+    16..4096) are handed to every lane's GpuSession.
+
+    residuals=True: every dict of an archive that was cleaned (n_iter > 0) comes
+    with out["residual_q"] = (q, scl, offs), its pulse-free residual as a
+    fold-mode PSRFITS file stores it (GpuSession.residual_quantised: int16
+    (nsub, nchan, nbin), '>i2' unless residual_big_endian is False, and f32
+    (nsub, nchan) scales and offsets), encoded on the GPU and downloaded while
+    the lane cleans its next archive.  The three arrays are views into a
+    page-locked result ring of the batch (2 slots with one lane, else 3 per
+    lane), not copies: they expire when the generator is advanced to the next
+    result, or closed - write or copy them before that;
+    psrfits.save_quantised(path, *out["residual_q"], ...) writes them as they
+    are.  Stopping early and a leaked lane follow the input ring's rules: the
+    result ring of a batch with a leaked lane is never freed."""
     if dedisp not in ("shift", "fft"):
         raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
     fft = dedisp == "fft"
@@ -379,14 +539,20 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
 
     order = []
     sessions = []
+    result_rings = []
     lanes_gen = None
     try:
+        if residuals:
+            for _ in range(lanes):
+                result_rings.append(_ResultRing(2 if lanes == 1 else 3, nsub, nchan, nbin,
+                                                ">i2" if residual_big_endian else np.int16))
         for _ in range(lanes):
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
                                                dedisp_fft=fft, any_length=any_length))
-        lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum)
+        lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
+                              residuals=[rr.triples() for rr in result_rings] if residuals else None)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
             yield out
@@ -403,8 +569,10 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             sess.close()
         if any(getattr(sess, "_ic_leaked", False) for sess in sessions):
             _LEAKED.extend(rings)       # a leaked lane's copies may still read the page-locked ring
+            _LEAKED.extend(result_rings)   # ... and its downloads still write the result ring
         else:
-            for rg in rings:
+            # (sess.close() above has drained every lane's download stream)
+            for rg in rings + result_rings:
                 rg.close()
 
 

@@ -5,7 +5,8 @@
 // address maps, the group reductions, the compile-time Stockham chain, and
 // the one definition of each rule of the reference that both restate (the
 // diagnostics' stores, the conjugate-pair spectrum step, the exact fit's
-// residual sample).  Everything is forced inline or constexpr.
+// residual sample; ic_codec.hip's k_residual_q takes the last from here too).
+// Everything is forced inline or constexpr.
 #pragma once
 #include "ic_wave.h"
 

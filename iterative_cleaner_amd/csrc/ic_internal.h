@@ -110,6 +110,7 @@ enum KernelId {
     K_EXCHANGE,       // the collectives themselves (host transport or peer copies)
     K_TNORM,          // fit_mode 1: sum(T*T)
     K_ROTATE,         // fractional dedispersion (FFT phase rotation)
+    K_RESIDUAL_Q,     // the residual formed and encoded to int16 in one pass
     K_COUNT
 };
 
@@ -592,5 +593,27 @@ hipError_t launch_residual(hipStream_t st, const float *D, const float *raw, con
                            const double *amp, const int32_t *info, const int32_t *shift, int nsub, int nchan,
                            int nbin, int ldD, int dtiled, int pr_on, double pr_factor, int pr_start, int pr_end,
                            float *R, int grid_cap = 0);
+// launch_residual and launch_encode_q in one pass (k_residual_q): the rows of
+// launch_residual, never written as f32, -> q [P][nbin] int16 (big_endian: as
+// FITS stores them) with scl / offs [P], bit for bit what launch_encode_q makes
+// of launch_residual's cube.  A row is held in LDS: nbin <= kResidualQMaxBin
+// (longer rows take the two launches).
+constexpr int kResidualQMaxBin = 8192;
+struct ResidualQArgs {
+    const float *D;             // fit cube, or nullptr: rows from raw and base (fit_mode 1)
+    const float *raw, *base;
+    const double *T64, *amp;
+    const int32_t *info, *shift;
+    int nsub, nchan, nbin;
+    int ldD, dtiled;
+    int pr_on;
+    double pr_factor;
+    int pr_start, pr_end;
+    bool big_endian;
+    int16_t *q;
+    float *scl, *offs;
+    int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP)
+};
+hipError_t launch_residual_q(hipStream_t st, const ResidualQArgs &a);
 
 }  // namespace icgpu

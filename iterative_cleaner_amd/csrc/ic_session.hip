@@ -142,7 +142,7 @@ const char *kKernelNames[K_COUNT] = {"k_chan_partials", "k_window",    "k_base",
                                      "k_fscrunch",      "k_tscrunch",  "k_fit_pass", "k_fit_state",
                                      "k_diag",          "k_linestats", "k_combine",  "k_residual",
                                      "k_fit_tail",      "k_sb_tree",   "k_shard_pack", "exchange",
-                                     "k_tnorm",         "k_rotate"};
+                                     "k_tnorm",         "k_rotate",    "k_residual_q"};
 
 constexpr long kTailProfiles = 8192;  // default: hand the remaining profiles to k_fit_tail below this
 constexpr long kTailProfilesLarge = 4096;   // the same for sessions of >= 2^20 profiles
@@ -204,6 +204,17 @@ struct Session {
     // int16 samples [N] and scl then offs [P] each; first use, kept
     int16_t *res_q = nullptr;
     float *res_so = nullptr;
+    // its asynchronous form (ic_get_residual_quantised_async): the copies run on
+    // dl_stream (first use; neither the session's stream nor copy_stream, so
+    // downloads, uploads and cleaning queue behind nothing but their own kind).
+    // enc_ev: the encode is done (the session's stream); dl_ev: the newest
+    // download has landed; dl_pending: dl_ev has not been waited for by the host;
+    // enc_slot: the input slot the newest encode read (raw, shift), -1 once an
+    // upload into it has been ordered behind enc_ev
+    hipStream_t dl_stream = nullptr;
+    hipEvent_t enc_ev = nullptr, dl_ev = nullptr;
+    bool dl_pending = false;
+    int enc_slot = -1;
     hipStream_t copy_stream = nullptr;
     int cur = 0, fifo[2] = {0, 0}, fifo_n = 0;
     bool ever_uploaded = false;
@@ -626,9 +637,15 @@ int collect_timing(Session *s)
 
 void free_all(Session *s)
 {
+    // hazard (d): a residual download may still be writing the caller's arrays
+    // from res_q / res_so; it ends before the staging is freed
+    if (s->dl_stream) {
+        (void)hipStreamSynchronize(s->dl_stream);
+        (void)hipStreamDestroy(s->dl_stream);
+    }
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     if (s->dstream) (void)hipStreamDestroy(s->dstream);
-    for (hipEvent_t ev : {s->slot_ev[0], s->slot_ev[1], s->fork_ev, s->join_ev, s->fork2_ev})
+    for (hipEvent_t ev : {s->slot_ev[0], s->slot_ev[1], s->fork_ev, s->join_ev, s->fork2_ev, s->enc_ev, s->dl_ev})
         if (ev) (void)hipEventDestroy(ev);
     s->mem.free_all();
     if (s->comm) {   // the transport's buffers
@@ -1555,7 +1572,11 @@ void ic_session_destroy(void *session)
     if (s->failed) {
         // kernels of this session may still be running (a wait timed out):
         // freeing their buffers could hand memory in use to another
-        // allocation, and a synchronising free could hang; leak them
+        // allocation, and a synchronising free could hang; leak them.
+        // Hazard (d) on this path: a residual download still queued writes the
+        // caller's arrays, which the caller frees next, so it is waited for,
+        // within the session's timeout (it sits behind those kernels)
+        if (s->dl_pending && hipSetDevice(s->device) == hipSuccess) (void)poll_event(s, s->dl_ev);
         s->mem.abandon();
         delete s;
         return;
@@ -1593,6 +1614,14 @@ static int async_slot(Session *s, int *target)
         return fail(IC_ENOMEM, "second input slot (%zu bytes) failed", sizeof(float) * (s->N + s->P));
     if (!s->copy_stream) CK(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
     if (!s->slot_ev[t]) CK(hipEventCreateWithFlags(&s->slot_ev[t], hipEventDisableTiming));
+    // hazard (a): the run that used slot t has returned, but the residual encode
+    // queued after it (ic_get_residual_quantised_async) may not have run yet, and
+    // it reads the slot's shifts and, for the closed form, its raw cube: the
+    // copies into the slot wait for the encode's event
+    if (s->enc_slot == t) {
+        CK(hipStreamWaitEvent(s->copy_stream, s->enc_ev, 0));
+        s->enc_slot = -1;
+    }
     *target = t;
     return IC_OK;
 }
@@ -2131,7 +2160,7 @@ int ic_get_residual(void *session, float *out)
     return IC_OK;
 }
 
-int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, float *offs)
+int ic_get_residual_quantised_async(void *session, int flags, int16_t *q, float *scl, float *offs)
 {
     Session *s = (Session *)session;
     if (!s || !q || !scl || !offs) return fail(IC_EINVAL, "null argument");
@@ -2139,24 +2168,87 @@ int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, 
     if (s->failed) return failed_session();
     if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
     CK(hipSetDevice(s->device));
+    const ic_params &p = s->p;
+    const bool big_endian = (flags & IC_Q_BIG_ENDIAN) != 0;
+    // one kernel forms and encodes the rows of the integer-shift residual; the
+    // FFT modes (and rows too long for its LDS) rotate / form them into the f32
+    // cube R first, which is free between runs (every iteration rewrites it
+    // whole before reading it) and is allocated here if the run did not need it
+    const bool fused = !s->fftded && p.nbin <= kResidualQMaxBin;
     // the encoded residual's staging: first use, kept until ic_session_destroy
-    if (s->mem.ensure(&s->res_q, s->N) != hipSuccess || s->mem.ensure(&s->res_so, 2 * s->P) != hipSuccess)
+    if (s->mem.ensure(&s->res_q, s->N) != hipSuccess || s->mem.ensure(&s->res_so, 2 * s->P) != hipSuccess ||
+        (!fused && s->mem.ensure(&s->R, s->N) != hipSuccess))
         return fail(IC_ENOMEM, "quantised residual staging (%zu bytes) failed",
-                    sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P);
-    // the f32 cube stays a per-call temporary, as in ic_get_residual
+                    sizeof(int16_t) * s->N + 2 * sizeof(float) * s->P + (fused ? 0 : sizeof(float) * s->N));
+    if (!s->dl_stream) CK(hipStreamCreateWithFlags(&s->dl_stream, hipStreamNonBlocking));
+    if (!s->enc_ev) CK(hipEventCreateWithFlags(&s->enc_ev, hipEventDisableTiming));
+    if (!s->dl_ev) CK(hipEventCreateWithFlags(&s->dl_ev, hipEventDisableTiming));
+    // hazard (b): an earlier download may still be reading res_q / res_so; this
+    // encode overwrites them only after it (an event wait on the session's
+    // stream: one staging, and the host does not block)
+    if (s->dl_pending) CK(hipStreamWaitEvent(s->stream, s->dl_ev, 0));
     const auto bad = [](hipError_t e) { return named_fail("quantised residual", e); };
-    Scratch tmp;
-    float *R = nullptr;
-    if (tmp.mem.alloc_exact(&R, s->N) != hipSuccess)
-        return fail(IC_ENOMEM, "residual cube (%zu bytes) failed", sizeof(float) * s->N);
-    CKF(launch_residual_cube(s, R), bad);
-    CKF(launch_encode_q(s->stream, R, (int)s->P, s->p.nbin, (flags & IC_Q_BIG_ENDIAN) != 0, s->res_q, s->res_so,
-                        s->res_so + s->P, s->grid_cap), bad);
-    CKF(hipMemcpyAsync(q, s->res_q, sizeof(int16_t) * s->N, hipMemcpyDeviceToHost, s->stream), bad);
-    CKF(hipMemcpyAsync(scl, s->res_so, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream), bad);
-    CKF(hipMemcpyAsync(offs, s->res_so + s->P, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->stream), bad);
-    CKF(hipStreamSynchronize(s->stream), bad);
+    if (fused) {
+        ResidualQArgs a{};
+        a.D = s->D;
+        a.raw = s->raw;
+        a.base = s->base0;
+        a.T64 = s->T64;
+        a.amp = s->amp;
+        a.info = s->info;
+        a.shift = s->shift;
+        a.nsub = p.nsub;
+        a.nchan = s->nchan;
+        a.nbin = p.nbin;
+        a.ldD = s->ldD;
+        a.dtiled = s->dtiled;
+        a.pr_on = p.pr_on;
+        a.pr_factor = p.pr_factor;
+        a.pr_start = p.pr_start < 0 ? 0 : (p.pr_start > p.nbin ? p.nbin : p.pr_start);
+        a.pr_end = p.pr_end < 0 ? 0 : (p.pr_end > p.nbin ? p.nbin : p.pr_end);
+        a.big_endian = big_endian;
+        a.q = s->res_q;
+        a.scl = s->res_so;
+        a.offs = s->res_so + s->P;
+        a.grid_cap = s->grid_cap;
+        LAUNCH(s, K_RESIDUAL_Q, launch_residual_q(s->stream, a));
+    } else {
+        CKF(launch_residual_cube(s, s->R), bad);
+        CKF(launch_encode_q(s->stream, s->R, (int)s->P, p.nbin, big_endian, s->res_q, s->res_so, s->res_so + s->P,
+                            s->grid_cap), bad);
+    }
+    CKF(hipEventRecord(s->enc_ev, s->stream), bad);
+    s->enc_slot = s->cur;   // hazard (a), closed in async_slot
+    // hazard (c): a following ic_run queues behind the encode on the session's
+    // stream and touches neither res_q / res_so nor the caller's arrays, so it
+    // needs no wait for the copies below
+    CKF(hipStreamWaitEvent(s->dl_stream, s->enc_ev, 0), bad);
+    CKF(hipMemcpyAsync(q, s->res_q, sizeof(int16_t) * s->N, hipMemcpyDeviceToHost, s->dl_stream), bad);
+    CKF(hipMemcpyAsync(scl, s->res_so, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->dl_stream), bad);
+    CKF(hipMemcpyAsync(offs, s->res_so + s->P, sizeof(float) * s->P, hipMemcpyDeviceToHost, s->dl_stream), bad);
+    CKF(hipEventRecord(s->dl_ev, s->dl_stream), bad);
+    s->dl_pending = true;
     return IC_OK;
+}
+
+int ic_residual_wait(void *session)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!s->dl_pending) return IC_OK;
+    CK(hipSetDevice(s->device));
+    const hipError_t e = poll_event(s, s->dl_ev);
+    if (e != hipSuccess) return named_fail("ic_residual_wait", e);
+    s->dl_pending = false;
+    return IC_OK;
+}
+
+// one path: the asynchronous call, then its wait
+int ic_get_residual_quantised(void *session, int flags, int16_t *q, float *scl, float *offs)
+{
+    if (int rc = ic_get_residual_quantised_async(session, flags, q, scl, offs)) return rc;
+    return ic_residual_wait(session);
 }
 
 int ic_encode_profiles(int device, int nsub, int nchan, int nbin, const float *in, int flags, int16_t *q,

@@ -498,6 +498,42 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
                                    int rowstat_waves, int rowstat_minlen);
 
 /* ------------------------------------------------------------------------
+ * Detrended scaling (opt-in; the definition is iterative_cleaner_amd/detrend.py).
+ * Before a diagnostic is scaled by its channel's (a line over the subints) or
+ * its subint's (a line over the channels) median and MAD, a polynomial trend of
+ * the line is removed: abscissa x_j = (2j - (n-1)) / (n-1), order chan_order /
+ * subint_order in 0..3 (0: that direction is not detrended), normal equations
+ * over the line's members summed as 64 chains and a halving tree, solved by
+ * elimination without pivoting, up to `rounds` (1..8) fits, each but the last
+ * followed by a clip of the members to |e - median(e)| <= clip * MAD(e) (clip a
+ * finite value > 0) of the residuals e; a line with a non-finite valid value,
+ * with no more members than the order, or with a refused pivot keeps a zero
+ * trend.  The scalers then run on d' = dtype(f64(d) - p(x)) as they run on d.
+ * The reference has no such step; it is modelled on coast_guard's
+ * iterative_detrend, and parity with coast_guard is UNPINNED (not available):
+ * detrend.py is the pin, and the kernels follow it bit for bit.
+ *
+ * ic_set_detrend: after create; holds for the ic_runs that follow; (0, 0, ..)
+ * switches it off, and a session on which it is off or was never called
+ * launches and computes exactly what it always did.  IC_EINVAL for a value out
+ * of range and on a channel-shard session.  It is no ic_set_option option:
+ * those never change the arithmetic.
+ * ic_get_trends: the last iteration's coefficients a_0..a_3 per line,
+ * chan_coef [4][nchan][4] and subint_coef [4][nsub][4] (diagnostics in the
+ * order std, mean, ptp, fftmax); either may be NULL.  IC_ESTATE before a
+ * completed iteration or while detrending is off.
+ * ic_comprehensive_stats_detrend: ic_comprehensive_stats with the detrended
+ * scaling; data_f64 as ic_params.data_f64 (ptp_out is f64: f32 values unless
+ * data_f64); chan_coef / subint_coef as ic_get_trends, may be NULL. */
+int ic_set_detrend(void *session, int chan_order, int subint_order, int rounds, double clip);
+int ic_get_trends(void *session, double *chan_coef, double *subint_coef);
+int ic_comprehensive_stats_detrend(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
+                                   double chanthresh, double subintthresh, double *test_out, double *std_out,
+                                   double *mean_out, double *ptp_out, double *fftmax_out, int data_f64,
+                                   int chan_order, int subint_order, int rounds, double clip, double *chan_coef,
+                                   double *subint_coef);
+
+/* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
  * SURVEY.md §8(e)).  The reference cleans an archive in one process
  * (iterative_cleaner.py:83-146); these entry points split the same loop by

@@ -28,7 +28,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_rccl_unique_id", "ic_session_create_rccl", "ic_rccl_set_library", "ic_rccl_set_init_timeout",
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
            "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised",
-           "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait")
+           "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait",
+           "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -178,6 +179,11 @@ def load_library(path: str = LIB_PATH):
                                            vp, vp, vp, vp, vp]
     lib.ic_comprehensive_stats_rowstat.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double,
                                                    C.c_double, vp, vp, vp, vp, vp, C.c_int, C.c_int]
+    lib.ic_set_detrend.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    lib.ic_get_trends.argtypes = [vp, vp, vp]
+    lib.ic_comprehensive_stats_detrend.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double,
+                                                   vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_double, vp, vp]
     if lib.ic_abi_version() != ABI_VERSION:
         raise NativeError("libicgpu ABI %d != expected %d" % (lib.ic_abi_version(), ABI_VERSION))
     _lib = lib
@@ -213,14 +219,17 @@ class GpuSession:
 
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
-                 delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None):
+                 delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None,
+                 detrend=None):
         """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
         with these delays (set_delays).  dedisp_fft=True: the same mode without
         delays yet: they come with set_delays, or with each archive
         (upload_async / upload_quantised_async delay=).  any_length (None = the
         IC_ANY_NBIN switch, phase_rotation.any_length_enabled): that mode is
         IC_DEDISP_FFT_ANY, which also serves any other nbin in 16..4096 by the
-        chirp-z rotation (the lengths IC_DEDISP_FFT serves keep their bits)."""
+        chirp-z rotation (the lengths IC_DEDISP_FFT serves keep their bits).
+        detrend = (chan_order, subint_order[, rounds, clip]): detrended scaling
+        (set_detrend; detrend.py); None: ic_set_detrend is never called."""
         from .phase_rotation import any_length_enabled
         fft_mode = DEDISP_FFT_ANY if (any_length_enabled() if any_length is None else any_length) else DEDISP_FFT
         self.lib = load_library()
@@ -242,6 +251,25 @@ class GpuSession:
             self.set_option(name, value)
         if delay is not None:
             self._initial_delays(delay)
+        if detrend is not None:
+            self.set_detrend(*detrend)
+
+    def set_detrend(self, chan_order, subint_order, rounds=4, clip=5.0):
+        """Detrended scaling for the runs that follow (ic_set_detrend; the
+        definition is detrend.py): polynomial orders 0..3 of the channel lines
+        and of the subint lines, (0, 0) = off; not on a channel shard."""
+        self._check(self.lib.ic_set_detrend(self.h, int(chan_order), int(subint_order), int(rounds), float(clip)),
+                    "ic_set_detrend")
+
+    def trends(self):
+        """The last iteration's trend coefficients (ic_get_trends): (chan
+        (4, nchan, 4), subint (4, nsub, 4)) f64, a_0..a_3 per line, diagnostics
+        in the order std, mean, ptp, fftmax."""
+        nsub, nchan, _ = self.shape
+        cc = np.empty((4, nchan, 4), np.float64)
+        sc = np.empty((4, nsub, 4), np.float64)
+        self._check(self.lib.ic_get_trends(self.h, _ptr(cc), _ptr(sc)), "ic_get_trends")
+        return cc, sc
 
     def _initial_delays(self, delay):
         self.set_delays(delay)
@@ -616,11 +644,16 @@ def rotate_profiles(cube, delay, sign=1, device=0, any_length=None):
 
 
 def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=0, diagnostics=False,
-                        rowstat_waves=8, rowstat_minlen=1024):
+                        rowstat_waves=8, rowstat_minlen=1024, detrend=None, data_f64=False):
     """comprehensive_stats (iterative_cleaner.py:181-226) on the GPU for the
     (nsub, nchan, nbin) data and (nsub, nchan) weights the reference masks and
     weights at :111-117; returns test [, (std, mean, ptp, fftmax)].
-    rowstat_*: the row-median form (IC_OPT_ROWSTAT_WAVES / _MINLEN)."""
+    rowstat_*: the row-median form (IC_OPT_ROWSTAT_WAVES / _MINLEN).
+    detrend = (chan_order, subint_order[, rounds, clip]): the detrended scaling
+    (ic_comprehensive_stats_detrend; detrend.py), with data_f64 the f64
+    statistics of a psrchive build; returns test, (chan_coef (4, nchan, 4),
+    subint_coef (4, nsub, 4)) [, (std, mean, ptp, fftmax)], ptp f64 with
+    data_f64."""
     lib = load_library()
     data = np.ascontiguousarray(data, dtype=np.float32)
     if data.ndim != 3:
@@ -628,6 +661,24 @@ def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=
     nsub, nchan, nbin = data.shape
     w = np.ascontiguousarray(weights, dtype=np.float32).reshape(nsub, nchan)
     test = np.empty((nsub, nchan), np.float64)
+    if detrend is None and data_f64:
+        raise ValueError("comprehensive_stats: data_f64 needs detrend")
+    if detrend is not None:
+        t = tuple(detrend)
+        co, so = t[:2]
+        rounds, clip = (t[2] if len(t) > 2 else 4), (t[3] if len(t) > 3 else 5.0)
+        sd, mn, pt, ff = (np.empty((nsub, nchan), np.float64) for _ in range(4))
+        cc = np.empty((4, nchan, 4), np.float64)
+        sc = np.empty((4, nsub, 4), np.float64)
+        rc = lib.ic_comprehensive_stats_detrend(int(device), nsub, nchan, nbin, _ptr(data), _ptr(w),
+                                                float(chanthresh), float(subintthresh), _ptr(test), _ptr(sd),
+                                                _ptr(mn), _ptr(pt), _ptr(ff), 1 if data_f64 else 0, int(co), int(so),
+                                                int(rounds), float(clip), _ptr(cc), _ptr(sc))
+        if rc != 0:
+            raise NativeError("ic_comprehensive_stats_detrend: %s (rc=%d)" % (_err(lib), rc))
+        if not data_f64:
+            pt = pt.astype(np.float32)   # exact: f32 values
+        return (test, (cc, sc), (sd, mn, pt, ff)) if diagnostics else (test, (cc, sc))
     sd, mn, ff = (np.empty((nsub, nchan), np.float64) for _ in range(3)) if diagnostics else (None,) * 3
     pt = np.empty((nsub, nchan), np.float32) if diagnostics else None
     rc = lib.ic_comprehensive_stats_rowstat(int(device), nsub, nchan, nbin, _ptr(data), _ptr(w),

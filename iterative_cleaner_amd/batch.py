@@ -105,7 +105,7 @@ class _ResidualQueue:
         return out, j
 
 
-def pipeline(session, items, fetch=True, nsum=1, residuals=None):
+def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -128,7 +128,13 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None):
     been issued: the download runs beside that clean and the upload of k+2.
     The triple is valid until the generator is advanced twice more (with 2
     slots: once more).  An archive whose run made no iteration has no
-    "residual_q"."""
+    "residual_q".
+
+    detrend = (chan_order, subint_order[, rounds, clip]): set on the session
+    before the first run (GpuSession.set_detrend); None leaves the session as
+    it is."""
+    if detrend is not None:
+        session.set_detrend(*detrend)
     rq = _ResidualQueue(session, _residual_slots(session, residuals)) if residuals is not None else None
 
     def after_run(out):
@@ -396,7 +402,7 @@ class _ResultRing:
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
-                any_length=None, residuals=False, residual_big_endian=True):
+                any_length=None, residuals=False, residual_big_endian=True, detrend=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -434,7 +440,13 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     result, or closed - write or copy them before that;
     psrfits.save_quantised(path, *out["residual_q"], ...) writes them as they
     are.  Stopping early and a leaked lane follow the input ring's rules: the
-    result ring of a batch with a leaked lane is never freed."""
+    result ring of a batch with a leaked lane is never freed.
+
+    detrend = (chan_order, subint_order[, rounds, clip]): the opt-in detrended
+    scaling (detrend.py) on every lane's session; None reads the IC_DETREND
+    switch (unset, empty or 0: off)."""
+    from .detrend import normalise
+    detrend = normalise(detrend)
     if dedisp not in ("shift", "fft"):
         raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
     fft = dedisp == "fft"
@@ -550,7 +562,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
-                                               dedisp_fft=fft, any_length=any_length))
+                                               dedisp_fft=fft, any_length=any_length, detrend=detrend))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
                               residuals=[rr.triples() for rr in result_rings] if residuals else None)
         for k, out in enumerate(lanes_gen):

@@ -207,7 +207,8 @@ def _device() -> int:
 
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
-             data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False):
+             data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
+             detrend=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -222,8 +223,15 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     residual comes encoded on the GPU as a PSRFITS file stores it, as
     ``residual_q`` = (q '>i2', scl, offs) instead of the f32 ``residual``
     (GpuSession.residual_quantised; under channel sharding the merged f32
-    ``residual`` is returned as ever)."""
+    ``residual`` is returned as ever).  ``detrend`` = (chan_order,
+    subint_order[, rounds, clip]): the opt-in detrended scaling (detrend.py);
+    None reads the switch IC_DETREND="chan,subint[,rounds,clip]" (unset, empty
+    or 0: off).  Not under channel sharding (ValueError)."""
+    from .detrend import normalise
     from .dist import channel_sharding
+    detrend = normalise(detrend)
+    if detrend is not None and channel_sharding():
+        raise ValueError("detrended scaling (detrend / IC_DETREND) is not available under channel sharding")
     if quantised is not None:
         if cube is not None or channel_sharding():
             raise ValueError("quantised input takes no f32 cube and no channel sharding")
@@ -255,7 +263,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     with _native.GpuSession(nsub, nchan, nbin, args.max_iter, args.chanthresh, args.subintthresh,
                             args.pulse_region, baseline_duty,
                             device=_device() if device is None else device, data_f64=data_f64, delay=delay,
-                            input_dedispersed=input_dedispersed) as s:
+                            input_dedispersed=input_dedispersed, detrend=detrend) as s:
         if quantised is not None:
             s.upload_quantised(quantised[0], quantised[1], quantised[2], w0, shift, quantised[3])
         elif pols:
@@ -317,8 +325,9 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch):
-    """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  Under
+def clean(ar, args, arch, detrend=None):
+    """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend:
+    run_loop's (None = the IC_DETREND switch; there is no CLI flag).  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -366,7 +375,7 @@ def clean(ar, args, arch):
     out = run_loop(cube, orig_weights, shift, args, want_residual=args.unload_res, baseline_duty=duty,
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
-                   residual_quantised=psrfits_res)
+                   residual_quantised=psrfits_res, detrend=detrend)
     del cube
 
     x = 0

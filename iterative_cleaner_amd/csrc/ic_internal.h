@@ -146,6 +146,15 @@ struct LineStatsArgs {
     int grp_waves = 8, grp_minlen = 1024;
 };
 
+// Detrended scaling (ic_set_detrend; detrend.py): the orders of the two
+// directions, the clipping rounds, and the lines' coefficients
+struct TrendArgs {
+    int chan_order, subint_order, rounds;
+    double clip;
+    double *col_coef;   // [4][nchan][4]
+    double *row_coef;   // [4][nsub][4]
+};
+
 // Grid cap (session option IC_OPT_GRID_CAP): the launchers whose grid is
 // min(blocks the work needs, a constant) launch min(that, grid_cap) blocks when
 // grid_cap > 0, so that a small archive drives every grid-stride loop through
@@ -449,6 +458,16 @@ hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *va
                           const double *row_med, const double *row_mad, double chanthresh,
                           double subintthresh, double *test, float *W, float *hist, int iter,
                           int32_t *counters, int grid_cap = 0);
+// the detrended forms (k_linetrend, k_combine_dt): launch_linetrend writes the
+// coefficients of t and the medians / MADs of the detrended lines into a's
+// col_* / row_*; launch_combine_dt scales the detrended entries with them
+hipError_t launch_linetrend(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int which = 3);
+hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                             int grid_cap = 0);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
 // bins, n even (<= 8192; 1/n and 4/n are rounded factors unless n is a power
 // of two): the phase rotation's multiplier

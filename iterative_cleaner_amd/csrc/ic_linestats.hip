@@ -1,5 +1,6 @@
 // ic_linestats.hip -- per channel / subint median and MAD (ic.py:229-256) and
-// the combine step (ic.py:221-225, :303-305, :127-141), with their launchers.
+// the combine step (ic.py:221-225, :303-305, :127-141), with their launchers,
+// and the opt-in detrended forms of both (k_linetrend, k_combine_dt; detrend.py).
 // The non-inlined wave_* / grp_* selection functions live here with all
 // their callers.
 #include <algorithm>
@@ -436,6 +437,257 @@ template <int W> __global__ __launch_bounds__(64 * W) void k_linestats_grp(LineS
     }
 }
 
+// ============================================================ detrended scaling
+// Opt-in (ic_set_detrend; iterative_cleaner_amd/detrend.py is the definition,
+// followed here operation by operation): a polynomial trend of order k <= 3 is
+// fitted to every line with clipping rounds, and the line's median and MAD are
+// those of d' = dtype(f64(d) - p(x)).  k_combine_dt forms the same d' per entry
+// with the same function (detrend_value).
+
+struct TrendCoef {
+    double a0, a1, a2, a3;
+};
+
+__device__ __forceinline__ double trend_x(int j, int n)
+{
+    return n == 1 ? 0.0 : (double)(2 * j - (n - 1)) / (double)(n - 1);
+}
+// p(x) by Horner from a_k
+__device__ __forceinline__ double trend_poly(double x, const TrendCoef &c, int k)
+{
+    double t = k >= 3 ? c.a3 : k == 2 ? c.a2 : k == 1 ? c.a1 : c.a0;
+    if (k >= 3) t = t * x + c.a2;
+    if (k >= 2) t = t * x + c.a1;
+    if (k >= 1) t = t * x + c.a0;
+    return t;
+}
+// d' of a valid entry j of a line of n values: dtype(f64(d) - p(x_j)), the
+// dtype's value held in a double (d holds an f32 value when f32)
+__device__ __forceinline__ double detrend_value(double d, bool f32, int j, int n, const TrendCoef &c, int k)
+{
+    const double r = d - trend_poly(trend_x(j, n), c, k);
+    return f32 ? (double)(float)r : r;
+}
+
+__device__ __forceinline__ double line_value(const LineStatsArgs &a, int diag, size_t kk)
+{
+    return diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
+}
+
+// one fit of order K over the entries of `use` (bit j of use[j / 64]): the 64
+// chains are the wave's lanes, whatever the block's wave count (every wave of
+// the block computes the same sums).  false: the trend is zero.
+template <int K>
+__device__ bool trend_fit(const LineStatsArgs &a, int diag, int rows, int idx, int len,
+                          const unsigned long long *use, int lane, TrendCoef &out)
+{
+    double S[2 * K + 1], B[K + 1];
+#pragma unroll
+    for (int p = 0; p <= 2 * K; ++p) S[p] = 0.0;
+#pragma unroll
+    for (int p = 0; p <= K; ++p) B[p] = 0.0;
+    for (int q0 = 0; q0 < len; q0 += 64) {
+        const int j = q0 + lane;
+        const unsigned long long w = use[q0 >> 6];
+        if (j < len && ((w >> lane) & 1ull)) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + j : (size_t)j * a.nchan + idx;
+            const double x = trend_x(j, len), y = line_value(a, diag, kk);
+            double xp = 1.0;
+#pragma unroll
+            for (int p = 0; p <= 2 * K; ++p) {
+                S[p] = S[p] + xp;
+                if (p <= K) B[p] = B[p] + xp * y;
+                xp = xp * x;
+            }
+        }
+    }
+    // halving tree over the chains: t[l] = t[l] + t[l + h], h = 32 .. 1
+#pragma unroll
+    for (int p = 0; p <= 2 * K; ++p) {
+        double v = S[p];
+        for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h);
+        S[p] = __shfl(v, 0);
+    }
+#pragma unroll
+    for (int p = 0; p <= K; ++p) {
+        double v = B[p];
+        for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h);
+        B[p] = __shfl(v, 0);
+    }
+    double G[K + 1][K + 1];
+#pragma unroll
+    for (int p = 0; p <= K; ++p)
+#pragma unroll
+        for (int q = 0; q <= K; ++q) G[p][q] = S[p + q];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i <= K; ++i) {
+        const double piv = G[i][i];
+        if (!(piv > 0.0 && isfinite(piv))) ok = false;
+#pragma unroll
+        for (int r = i + 1; r <= K; ++r) {
+            const double f = G[r][i] / piv;
+#pragma unroll
+            for (int c = i + 1; c <= K; ++c) G[r][c] = G[r][c] - f * G[i][c];
+            B[r] = B[r] - f * B[i];
+        }
+    }
+    if (!ok) return false;   // (the operations after a refused pivot are discarded)
+    double x[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = K; i >= 0; --i) {
+        double s = B[i];
+#pragma unroll
+        for (int c = i + 1; c <= K; ++c) s = s - G[i][c] * x[c];
+        x[i] = s / G[i][i];
+    }
+    out = TrendCoef{x[0], x[1], x[2], x[3]};
+    return true;
+}
+
+// one block of W waves per line (W = 1: one wave per line); LDS: 256 bins,
+// 2*W reduction slots, W segments of seg keys, the membership words of the line.
+// Every round reads the line again from memory (short and L2-resident); LDS
+// holds the selection keys and the membership bits only.
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_linetrend(LineStatsArgs a, TrendArgs t, int rows, int len)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned *hist = (unsigned *)lsm;
+    GrpRed<W> g{(unsigned long long *)(lsm + 1024), wave, lane};
+    const int nline = rows ? a.nsub : a.nchan;
+    const int line = blockIdx.x;
+    const int diag = line / nline, idx = line % nline;
+    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
+    const int k = rows ? t.subint_order : t.chan_order;
+    const int seg = (((len + W - 1) / W) + 63) & ~63;
+    const int q0w = min(len, wave * seg), q1w = min(len, q0w + seg);
+    unsigned long long *keys = (unsigned long long *)(lsm + 1024 + 16 * W) + (size_t)wave * seg;
+    unsigned long long *use = (unsigned long long *)(lsm + 1024 + 16 * W) + (size_t)W * seg;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // membership = valid; any valid value not finite: no trend
+    int nv = 0, bad = 0;
+    for (int q0 = q0w; q0 < q1w; q0 += 64) {
+        const int q = q0 + lane;
+        bool v = false;
+        if (q < q1w) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            bad |= v && !isfinite(line_value(a, diag, kk));
+        }
+        const unsigned long long m = __ballot(v);
+        if (lane == 0) use[q0 >> 6] = m;
+        nv += __popcll(m);
+    }
+    bad = g.sum_uniform(__any(bad) ? 1 : 0);   // the barrier also publishes the membership words
+    nv = g.sum_uniform(nv);
+    const TrendCoef zero{0.0, 0.0, 0.0, 0.0};
+    TrendCoef c = zero;
+    if (k > 0 && nv > 0 && !bad) {
+        int nuse = nv;
+        for (int r = 1; r <= t.rounds; ++r) {
+            if (nuse <= k) {
+                c = zero;
+                break;
+            }
+            const bool ok = k == 1   ? trend_fit<1>(a, diag, rows, idx, len, use, lane, c)
+                            : k == 2 ? trend_fit<2>(a, diag, rows, idx, len, use, lane, c)
+                                     : trend_fit<3>(a, diag, rows, idx, len, use, lane, c);
+            if (!ok) {
+                c = zero;
+                break;
+            }
+            if (r == t.rounds) break;
+            // e = y - p(x) over the membership, this wave's slice
+            int cnt = 0, nf = 0;
+            for (int q0 = q0w; q0 < q1w; q0 += 64) {
+                const int q = q0 + lane;
+                const bool in = q < q1w && ((use[q0 >> 6] >> lane) & 1ull);
+                double e = 0.0;
+                if (in) {
+                    const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+                    e = line_value(a, diag, kk) - trend_poly(trend_x(q, len), c, k);
+                }
+                const unsigned long long m = __ballot(in);
+                if (in) keys[cnt + __popcll(m & below)] = key64(e);
+                nf |= in && !isfinite(e);
+                cnt += __popcll(m);
+            }
+            nf = g.sum_uniform(__any(nf) ? 1 : 0);
+            if (nf) break;
+            const double med = grp_median<W>(g, keys, cnt, nuse, false, hist);
+            for (int j = lane; j < cnt; j += 64) keys[j] = key64(fabs(unkey64(keys[j]) - med));
+            const double mad = grp_median<W>(g, keys, cnt, nuse, false, hist);
+            if (mad == 0.0) break;
+            const double lim = t.clip * mad;
+            int changed = 0, nn = 0;
+            for (int q0 = q0w; q0 < q1w; q0 += 64) {
+                const int q = q0 + lane;
+                bool in = false;
+                if (q < q1w) {
+                    const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+                    if (plain ? true : (a.valid[kk] != 0)) {
+                        const double e = line_value(a, diag, kk) - trend_poly(trend_x(q, len), c, k);
+                        in = fabs(e - med) <= lim;
+                    }
+                }
+                const unsigned long long m = __ballot(in);
+                changed |= m != use[q0 >> 6];
+                if (lane == 0) use[q0 >> 6] = m;   // this wave's words: read by the others after the barrier below
+                nn += __popcll(m);
+            }
+            changed = g.sum_uniform(changed);
+            nuse = g.sum_uniform(nn);
+            if (!changed) break;
+        }
+    }
+    // median and MAD of d', as k_linestats_grp takes them of d
+    int cnt = 0, nan = 0;
+    for (int q0 = q0w; q0 < q1w; q0 += 64) {
+        const int q = q0 + lane;
+        double d = 0.0;
+        bool v = false;
+        if (q < q1w) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            if (v) d = detrend_value(line_value(a, diag, kk), f32, q, len, c, k);
+        }
+        const unsigned long long m = __ballot(v);
+        if (v) keys[cnt + __popcll(m & below)] = key64(d);
+        nan |= v && isnan(d);
+        cnt += __popcll(m);
+    }
+    nan = g.sum_uniform(__any(nan) ? 1 : 0);
+    double med = NAN, mad = NAN;
+    if (nv > 0 && !nan) {
+        med = grp_median<W>(g, keys, cnt, nv, f32, hist);
+        int rnan = 0;
+        for (int j = lane; j < cnt; j += 64) {
+            const double d = unkey64(keys[j]);
+            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
+            rnan |= isnan(r);
+            keys[j] = key64(r);
+        }
+        rnan = g.sum_uniform(__any(rnan) ? 1 : 0);
+        if (!rnan) mad = grp_median<W>(g, keys, cnt, nv, f32, hist);
+    }
+    if (threadIdx.x == 0) {
+        double *coef = (rows ? t.row_coef : t.col_coef) + ((size_t)diag * nline + idx) * 4;
+        coef[0] = c.a0;
+        coef[1] = c.a1;
+        coef[2] = c.a2;
+        coef[3] = c.a3;
+        if (!rows) {
+            a.col_med[diag * a.nchan + idx] = med;
+            a.col_mad[diag * a.nchan + idx] = mad;
+        } else {
+            a.row_med[diag * a.nsub + idx] = med;
+            a.row_mad[diag * a.nsub + idx] = mad;
+        }
+    }
+}
+
 // ============================================================ combine
 
 __device__ __forceinline__ double scale_masked_d(double dv, bool valid, double med, double mad, double thr)
@@ -486,14 +738,28 @@ constexpr double kNearTie = 1e-9;
 // lies within kNearTie of the zap threshold 1.0 (where the last bits of fftmax,
 // not bit-identical to pocketfft, could decide), [4+h] != hist[h]
 
-__global__ __launch_bounds__(256) void k_combine(
+// TR = TrendView: the detrended form (k_combine_dt): every diagnostic enters its channel's
+// scaler as the channel direction's d' and its subint's scaler as the subint
+// direction's d' (detrend_value with the line's coefficients; invalid entries
+// keep d); the rest is k_combine's.  bdim / gdim: the kernel's blockDim.x /
+// gridDim.x, read in the kernel
+struct NoTrend {
+    static constexpr bool on = false;
+};
+struct TrendView {
+    static constexpr bool on = true;
+    const TrendCoef *col_coef, *row_coef;   // [4][nchan], [4][nsub]
+    int chan_order, subint_order;
+};
+template <class TR>
+__device__ __forceinline__ void combine_body(
     int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
     const float *__restrict__ w0,
     const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
     const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
     const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
     double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
-    int32_t *__restrict__ counters)
+    int32_t *__restrict__ counters, const unsigned bdim, const unsigned gdim, const TR tr)
 {
     // grid-stride; the convergence counters are reduced per block (one atomic
     // per counter per block: same-address atomics serialise at the memory side)
@@ -503,23 +769,51 @@ __global__ __launch_bounds__(256) void k_combine(
     int changed = 0, zero = 0, bad = 0, near = 0;
     unsigned long long diff = 0ull;   // bit h: W != hist[h] somewhere (h < 64)
     const int hmax = iter < 64 ? iter : 64;
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < P; k += (size_t)gridDim.x * blockDim.x) {
+    for (size_t k = (size_t)blockIdx.x * bdim + threadIdx.x; k < P; k += (size_t)gdim * bdim) {
         const int s = (int)(k / nchan), c = (int)(k % nchan);
         const bool v = valid[k] != 0;
         double S[4];
-        S[0] = nanmax2(scale_masked_d(std_d[k], v, col_med[c], col_mad[c], cth),
-                       scale_masked_d(std_d[k], v, row_med[s], row_mad[s], sth));
-        S[1] = nanmax2(scale_masked_d(mean_d[k], v, col_med[nchan + c], col_mad[nchan + c], cth),
-                       scale_masked_d(mean_d[k], v, row_med[nsub + s], row_mad[nsub + s], sth));
-        // ptp: numpy.ma in f32 for f32 data (Appendix A.5), f64 for f64 data
-        S[2] = ptp_f32 ? nanmax2(scale_masked_f((float)ptp_d[k], v, (float)col_med[2 * nchan + c],
-                                                (float)col_mad[2 * nchan + c], cth),
-                                 scale_masked_f((float)ptp_d[k], v, (float)row_med[2 * nsub + s],
-                                                (float)row_mad[2 * nsub + s], sth))
-                       : nanmax2(scale_masked_d(ptp_d[k], v, col_med[2 * nchan + c], col_mad[2 * nchan + c], cth),
-                                 scale_masked_d(ptp_d[k], v, row_med[2 * nsub + s], row_mad[2 * nsub + s], sth));
-        S[3] = nanmax2(scale_plain(fft_d[k], col_med[3 * nchan + c], col_mad[3 * nchan + c], cth),
-                       scale_plain(fft_d[k], row_med[3 * nsub + s], row_mad[3 * nsub + s], sth));
+        if constexpr (TR::on) {
+            // dc / ds: the entry's d' in its channel line (entry s of nsub) and
+            // in its subint line (entry c of nchan)
+            const double dv[4] = {std_d[k], mean_d[k], ptp_d[k], fft_d[k]};
+            double dc[4], ds[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool f32 = q == 2 && ptp_f32;
+                const bool in = q == 3 || v;
+                dc[q] = in ? detrend_value(dv[q], f32, s, nsub, tr.col_coef[(size_t)q * nchan + c], tr.chan_order)
+                           : dv[q];
+                ds[q] = in ? detrend_value(dv[q], f32, c, nchan, tr.row_coef[(size_t)q * nsub + s], tr.subint_order)
+                           : dv[q];
+            }
+            S[0] = nanmax2(scale_masked_d(dc[0], v, col_med[c], col_mad[c], cth),
+                           scale_masked_d(ds[0], v, row_med[s], row_mad[s], sth));
+            S[1] = nanmax2(scale_masked_d(dc[1], v, col_med[nchan + c], col_mad[nchan + c], cth),
+                           scale_masked_d(ds[1], v, row_med[nsub + s], row_mad[nsub + s], sth));
+            S[2] = ptp_f32 ? nanmax2(scale_masked_f((float)dc[2], v, (float)col_med[2 * nchan + c],
+                                                    (float)col_mad[2 * nchan + c], cth),
+                                     scale_masked_f((float)ds[2], v, (float)row_med[2 * nsub + s],
+                                                    (float)row_mad[2 * nsub + s], sth))
+                           : nanmax2(scale_masked_d(dc[2], v, col_med[2 * nchan + c], col_mad[2 * nchan + c], cth),
+                                     scale_masked_d(ds[2], v, row_med[2 * nsub + s], row_mad[2 * nsub + s], sth));
+            S[3] = nanmax2(scale_plain(dc[3], col_med[3 * nchan + c], col_mad[3 * nchan + c], cth),
+                           scale_plain(ds[3], row_med[3 * nsub + s], row_mad[3 * nsub + s], sth));
+        } else {
+            S[0] = nanmax2(scale_masked_d(std_d[k], v, col_med[c], col_mad[c], cth),
+                           scale_masked_d(std_d[k], v, row_med[s], row_mad[s], sth));
+            S[1] = nanmax2(scale_masked_d(mean_d[k], v, col_med[nchan + c], col_mad[nchan + c], cth),
+                           scale_masked_d(mean_d[k], v, row_med[nsub + s], row_mad[nsub + s], sth));
+            // ptp: numpy.ma in f32 for f32 data (Appendix A.5), f64 for f64 data
+            S[2] = ptp_f32 ? nanmax2(scale_masked_f((float)ptp_d[k], v, (float)col_med[2 * nchan + c],
+                                                    (float)col_mad[2 * nchan + c], cth),
+                                     scale_masked_f((float)ptp_d[k], v, (float)row_med[2 * nsub + s],
+                                                    (float)row_mad[2 * nsub + s], sth))
+                           : nanmax2(scale_masked_d(ptp_d[k], v, col_med[2 * nchan + c], col_mad[2 * nchan + c], cth),
+                                     scale_masked_d(ptp_d[k], v, row_med[2 * nsub + s], row_mad[2 * nsub + s], sth));
+            S[3] = nanmax2(scale_plain(fft_d[k], col_med[3 * nchan + c], col_mad[3 * nchan + c], cth),
+                           scale_plain(fft_d[k], row_med[3 * nsub + s], row_mad[3 * nsub + s], sth));
+        }
         double t;
         if (isnan(S[0]) || isnan(S[1]) || isnan(S[2]) || isnan(S[3])) {
             t = NAN;
@@ -558,7 +852,7 @@ __global__ __launch_bounds__(256) void k_combine(
         near += __shfl_xor(near, off);
         diff |= __shfl_xor(diff, off);
     }
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int wave = threadIdx.x >> 6, nw = bdim >> 6;
     if ((threadIdx.x & 63) == 0) {
         red[0][wave] = changed;
         red[1][wave] = zero;
@@ -585,6 +879,33 @@ __global__ __launch_bounds__(256) void k_combine(
         for (int h = 0; h < hmax; ++h)
             if ((df >> h) & 1ull) atomicOr(&counters[4 + h], 1);
     }
+}
+
+__global__ __launch_bounds__(256) void k_combine(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters)
+{
+    combine_body(nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad,
+                 cth, sth, test, W, hist, iter, counters, blockDim.x, gridDim.x, NoTrend{});
+}
+
+__global__ __launch_bounds__(256) void k_combine_dt(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters, TrendArgs t)
+{
+    combine_body(nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad,
+                 cth, sth, test, W, hist, iter, counters, blockDim.x, gridDim.x,
+                 TrendView{(const TrendCoef *)t.col_coef, (const TrendCoef *)t.row_coef, t.chan_order, t.subint_order});
 }
 
 // ============================================================ launchers
@@ -627,6 +948,58 @@ hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// the detrended line stage: coefficients, and the medians / MADs of d' into
+// a's col_* / row_* (which: as launch_linestats).  Rows of >= grp_minlen values
+// take grp_waves waves per line, as launch_linestats' do; the bits do not
+// depend on it.
+template <int W>
+static hipError_t launch_linetrend_w(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int rows, int len,
+                                     int lines, bool *done)
+{
+    const int seg = (((len + W - 1) / W) + 63) & ~63;
+    const size_t shm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8 + (size_t)((len + 63) / 64) * 8;
+    *done = shm <= kLdsBlockMax;
+    if (!*done) return hipSuccess;
+    IC_GGL(k_linetrend<W>, dim3(lines), dim3(64 * W), shm, st, a, t, rows, len);
+    return hipGetLastError();
+}
+
+hipError_t launch_linetrend(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int which)
+{
+    for (int rows = 0; rows < 2; ++rows) {
+        if (!((which >> rows) & 1)) continue;
+        const int len = rows ? a.nchan : a.nsub;
+        const int lines = 4 * (rows ? a.nsub : a.nchan);
+        if (lines == 0 || len == 0) continue;
+        bool done = false;
+        hipError_t e = hipSuccess;
+        if (lines < 8192 && len >= a.grp_minlen) {
+            if (a.grp_waves == 4) e = launch_linetrend_w<4>(st, a, t, rows, len, lines, &done);
+            if (a.grp_waves == 8) e = launch_linetrend_w<8>(st, a, t, rows, len, lines, &done);
+        }
+        if (!done) {
+            e = launch_linetrend_w<1>(st, a, t, rows, len, lines, &done);
+            if (!done) return hipErrorInvalidValue;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                             int grid_cap)
+{
+    const size_t P = (size_t)nsub * nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
+    IC_GGL(k_combine_dt, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
+           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t);
+    return hipGetLastError();
 }
 
 hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,

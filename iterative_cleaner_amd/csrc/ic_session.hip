@@ -238,6 +238,14 @@ struct Session {
     int fit_rounds = 0;
     int plan_ub = 0;            // max(leaves, ops) of the pairwise plan (k_tnorm scratch)
     LineStatsArgs ls_knobs;     // row-median form (IC_OPT_ROWSTAT_*)
+    // detrended scaling (ic_set_detrend; both orders 0 = off: k_linestats and
+    // k_combine as ever, no buffer).  trend: [4][nchan][4] channel then
+    // [4][nsub][4] subint coefficients, from `mem` at the first detrended run;
+    // trends_ran: the last run's last iteration wrote them
+    int dt_chan = 0, dt_sub = 0, dt_rounds = 4;
+    double dt_clip = 5.0;
+    double *trend = nullptr;
+    bool trends_ran = false;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -1982,6 +1990,12 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     la.col_mad = s->lstat + 4 * nchan;
     la.row_med = s->lstat + 8 * nchan;
     la.row_mad = s->lstat + 8 * nchan + 4 * nsub;
+    const bool detrend = s->dt_chan > 0 || s->dt_sub > 0;
+    s->trends_ran = false;
+    if (detrend && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
+        return fail(IC_ENOMEM, "hipMalloc(trend coefficients: %zu doubles) failed", (size_t)16 * (nchan + nsub));
+    const TrendArgs ta{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
+                       s->trend ? s->trend + (size_t)16 * nchan : nullptr};
     int32_t *cnt = s->h_small;   // [max_iter + 5] counters, then the run stats (pinned)
     s->bad_fits.clear();
     int x = 0, loops = -1, n_iter = 0, converged = 0;
@@ -2062,15 +2076,25 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
             LAUNCH(s, K_DIAG, launch_diag(s->stream, da));
         }
         // channel medians are local to a shard; row medians need whole rows
-        LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, la, s->comm ? 1 : 3));
-        if (s->comm)
-            if (int rc = shard_rowstats(s, la)) return rc;
+        if (detrend) {   // never a shard (ic_set_detrend refuses those)
+            LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 3));
+        } else {
+            LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, la, s->comm ? 1 : 3));
+            if (s->comm)
+                if (int rc = shard_rowstats(s, la)) return rc;
+        }
         CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + 5), s->stream));
-        LAUNCH(s, K_COMBINE,
-               launch_combine(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp, la.ptp_f32,
-                              s->fft,
-                              la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh, p.subintthresh,
-                              s->test, s->W, s->hist, n_iter, s->counters, s->grid_cap));
+        if (detrend) {
+            LAUNCH(s, K_COMBINE,
+                   launch_combine_dt(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
+                                     la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
+                                     p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, ta, s->grid_cap));
+        } else {
+            LAUNCH(s, K_COMBINE,
+                   launch_combine(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
+                                  la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
+                                  p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, s->grid_cap));
+        }
         if (s->comm)
             CM(s, s->comm->allreduce_sum_i32(s->counters, (size_t)(n_iter + 4), s->stream), "convergence counters");
         CK(hipMemcpyAsync(cnt, s->counters, sizeof(int32_t) * (n_iter + 4), hipMemcpyDeviceToHost,
@@ -2108,6 +2132,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     s->stats.iterations = n_iter;
     if (converged_out) *converged_out = converged;
     s->ran = n_iter > 0;
+    s->trends_ran = detrend && n_iter > 0;
     return IC_OK;
 }
 
@@ -2553,6 +2578,47 @@ int ic_get_option(void *session, int option, int64_t *out)
     }
 }
 
+// the ranges of ic_set_detrend / ic_comprehensive_stats_detrend; 0 or the message
+static const char *detrend_range(int chan_order, int subint_order, int rounds, double clip)
+{
+    if (chan_order < 0 || chan_order > 3 || subint_order < 0 || subint_order > 3) return "orders outside 0..3";
+    if (rounds < 1 || rounds > 8) return "rounds outside 1..8";
+    if (!(std::isfinite(clip) && clip > 0.0)) return "clip must be finite and > 0";
+    return nullptr;
+}
+
+int ic_set_detrend(void *session, int chan_order, int subint_order, int rounds, double clip)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (const char *e = detrend_range(chan_order, subint_order, rounds, clip))
+        return fail(IC_EINVAL, "ic_set_detrend(%d, %d, %d, %g): %s", chan_order, subint_order, rounds, clip, e);
+    if (s->comm || s->world > 1)
+        return fail(IC_EINVAL, "ic_set_detrend on a channel shard: detrended rows across shards are not supported");
+    s->dt_chan = chan_order;
+    s->dt_sub = subint_order;
+    s->dt_rounds = rounds;
+    s->dt_clip = clip;
+    s->trends_ran = false;
+    return IC_OK;
+}
+
+int ic_get_trends(void *session, double *chan_coef, double *subint_coef)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!(s->dt_chan > 0 || s->dt_sub > 0)) return fail(IC_ESTATE, "detrending is off (ic_set_detrend)");
+    if (!s->ran || !s->trends_ran) return fail(IC_ESTATE, "no completed detrended iteration");
+    const size_t nc = (size_t)16 * s->nchan, ns = (size_t)16 * s->p.nsub;
+    if (chan_coef) CK(hipMemcpyAsync(chan_coef, s->trend, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
+    if (subint_coef)
+        CK(hipMemcpyAsync(subint_coef, s->trend + nc, sizeof(double) * ns, hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    return IC_OK;
+}
+
 int ic_get_run_stats(void *session, ic_run_stats *out)
 {
     Session *s = (Session *)session;
@@ -2619,10 +2685,41 @@ int ic_comprehensive_stats(int device, int nsub, int nchan, int nbin, const floa
                                           test_out, std_o, mean_o, ptp_o, fftmax_o, 8, 1024);
 }
 
+// the one-shot statistics; dt (optional): detrended (k_linetrend, k_combine_dt),
+// its coefficient pointers host outputs (may be null).  ptp goes to ptp_o (f32)
+// or ptp64_o.
+static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
+                         double chanthresh, double subintthresh, double *test_out, double *std_o, double *mean_o,
+                         float *ptp_o, double *ptp64_o, double *fftmax_o, int rowstat_waves, int rowstat_minlen,
+                         int data_f64, const TrendArgs *trend);
+
 int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, const float *data,
                                    const float *weights, double chanthresh, double subintthresh, double *test_out,
                                    double *std_o, double *mean_o, float *ptp_o, double *fftmax_o, int rowstat_waves,
                                    int rowstat_minlen)
+{
+    return stats_oneshot(device, nsub, nchan, nbin, data, weights, chanthresh, subintthresh, test_out, std_o, mean_o,
+                         ptp_o, nullptr, fftmax_o, rowstat_waves, rowstat_minlen, 0, nullptr);
+}
+
+int ic_comprehensive_stats_detrend(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
+                                   double chanthresh, double subintthresh, double *test_out, double *std_o,
+                                   double *mean_o, double *ptp_o, double *fftmax_o, int data_f64, int chan_order,
+                                   int subint_order, int rounds, double clip, double *chan_coef, double *subint_coef)
+{
+    if (data_f64 != 0 && data_f64 != 1) return fail(IC_EINVAL, "data_f64=%d (0 or 1)", data_f64);
+    if (const char *e = detrend_range(chan_order, subint_order, rounds, clip))
+        return fail(IC_EINVAL, "ic_comprehensive_stats_detrend(%d, %d, %d, %g): %s", chan_order, subint_order, rounds,
+                    clip, e);
+    const TrendArgs dt{chan_order, subint_order, rounds, clip, chan_coef, subint_coef};
+    return stats_oneshot(device, nsub, nchan, nbin, data, weights, chanthresh, subintthresh, test_out, std_o, mean_o,
+                         nullptr, ptp_o, fftmax_o, 8, 1024, data_f64, &dt);
+}
+
+static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
+                         double chanthresh, double subintthresh, double *test_out, double *std_o, double *mean_o,
+                         float *ptp_o, double *ptp64_o, double *fftmax_o, int rowstat_waves, int rowstat_minlen,
+                         int data_f64, const TrendArgs *trend)
 {
     if (!data || !weights || !test_out) return fail(IC_EINVAL, "null argument");
     if (rowstat_waves != 0 && rowstat_waves != 4 && rowstat_waves != 8)
@@ -2642,7 +2739,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     hipStream_t st = sc.stream;
     float *D, *w0, *W, *hist;
     uint8_t *valid;
-    double *sd, *mn, *ff, *pt, *test, *lstat;
+    double *sd, *mn, *ff, *pt, *test, *lstat, *coef;
     int32_t *cnt;
     double2 *dtw, *dtw2, *ddt;
     PwPlan *dplan;
@@ -2653,7 +2750,8 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
               {(void **)&hist, 8 * P},  {(void **)&sd, 8 * P},   {(void **)&mn, 8 * P}, {(void **)&ff, 8 * P},
               {(void **)&pt, 8 * P},    {(void **)&test, 8 * P}, {(void **)&lstat, 8 * 16 * ((size_t)nsub + nchan)},
               {(void **)&cnt, 4 * 8},   {(void **)&dtw, 16 * (size_t)nbin}, {(void **)&dtw2, 16 * (size_t)nbin + 16},
-              {(void **)&dplan, sizeof plan}, {(void **)&ddt, 16 * dt.size()}};
+              {(void **)&dplan, sizeof plan}, {(void **)&ddt, 16 * dt.size()},
+              {(void **)&coef, trend ? 8 * 16 * ((size_t)nsub + nchan) : 0}};
     for (auto &x : al)
         if (sc.mem.alloc_bytes(x.p, x.bytes + 16) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(%zu) failed", x.bytes);
     CK(hipMemcpyAsync(D, data, 4 * N, hipMemcpyHostToDevice, st));
@@ -2680,6 +2778,7 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     a.mean_o = mn;
     a.fft_o = ff;
     a.ptp_o = pt;
+    a.data_f64 = data_f64;
     CK(launch_diag(st, a));
     LineStatsArgs la;
     la.nsub = nsub;
@@ -2689,21 +2788,35 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
     la.mean_d = mn;
     la.fft_d = ff;
     la.ptp_d = pt;
-    la.ptp_f32 = 1;
+    la.ptp_f32 = !data_f64;
     la.grp_waves = rowstat_waves;
     la.grp_minlen = rowstat_minlen;
     la.col_med = lstat;
     la.col_mad = lstat + 4 * nchan;
     la.row_med = lstat + 8 * nchan;
     la.row_mad = lstat + 8 * nchan + 4 * nsub;
-    CK(launch_linestats(st, la, 3));
-    CK(launch_combine(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, 1, ff, la.col_med, la.col_mad, la.row_med, la.row_mad,
-                      chanthresh, subintthresh, test, W, hist, 1, cnt));
+    if (trend) {
+        TrendArgs ta = *trend;
+        ta.col_coef = coef;
+        ta.row_coef = coef + (size_t)16 * nchan;
+        CK(launch_linetrend(st, la, ta, 3));
+        CK(launch_combine_dt(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med, la.col_mad,
+                             la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt, ta));
+        if (trend->col_coef)
+            CK(hipMemcpyAsync(trend->col_coef, ta.col_coef, 8 * 16 * (size_t)nchan, hipMemcpyDeviceToHost, st));
+        if (trend->row_coef)
+            CK(hipMemcpyAsync(trend->row_coef, ta.row_coef, 8 * 16 * (size_t)nsub, hipMemcpyDeviceToHost, st));
+    } else {
+        CK(launch_linestats(st, la, 3));
+        CK(launch_combine(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, 1, ff, la.col_med, la.col_mad, la.row_med,
+                          la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt));
+    }
     CK(hipMemcpyAsync(test_out, test, 8 * P, hipMemcpyDeviceToHost, st));
     if (std_o) CK(hipMemcpyAsync(std_o, sd, 8 * P, hipMemcpyDeviceToHost, st));
     if (mean_o) CK(hipMemcpyAsync(mean_o, mn, 8 * P, hipMemcpyDeviceToHost, st));
     std::vector<double> ptp64(ptp_o ? P : 0);
     if (ptp_o) CK(hipMemcpyAsync(ptp64.data(), pt, 8 * P, hipMemcpyDeviceToHost, st));
+    if (ptp64_o) CK(hipMemcpyAsync(ptp64_o, pt, 8 * P, hipMemcpyDeviceToHost, st));
     if (fftmax_o) CK(hipMemcpyAsync(fftmax_o, ff, 8 * P, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     for (size_t k = 0; k < ptp64.size(); ++k) ptp_o[k] = (float)ptp64[k];

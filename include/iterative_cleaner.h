@@ -534,6 +534,55 @@ int ic_comprehensive_stats_detrend(int device, int nsub, int nchan, int nbin, co
                                    double *subint_coef);
 
 /* ------------------------------------------------------------------------
+ * Piecewise detrending (opt-in, on top of the detrended scaling; the definition
+ * is the piecewise part of iterative_cleaner_amd/detrend.py).  The lines of a
+ * direction are cut into pieces at strictly ascending starts b_0 = 0 < b_1 < ..
+ * < b_{m-1} < n (1 <= m <= 512; piece q is [b_q, b_{q+1}), the last one ends
+ * at n), the same for every line and diagnostic of that direction.  Every
+ * piece has its own abscissa x = (2i - (L-1)) / (L-1) over its local index i
+ * and length L (L == 1: 0) and is fitted on its own, from its own members, with
+ * the sums, the elimination and the order of the whole-line fit.  A piece with
+ * no more members than the order, or with a refused pivot, is retired: its
+ * coefficients are +0.0 from that round on, and the other pieces go on.  The
+ * members, the residuals' median and MAD, the clip and the stop rules stay
+ * those of the whole line; a line with a non-finite valid value keeps a zero
+ * trend in every piece.  d' of an entry uses its own piece's polynomial.  The
+ * entries of a retired piece therefore meet the scaler undetrended (a subband
+ * with too few live channels is likely to be zapped); no lower order is tried.
+ * With one piece per direction every output equals the whole-line form's bit
+ * for bit.  Modelled on coast_guard's breakpoints / numpieces (its detrend's
+ * `bp` and `numpieces`, the surgical cleaner's chan_/subint_breakpoints and
+ * _numpieces), stated from memory: parity with coast_guard is UNPINNED.
+ *
+ * ic_set_detrend_pieces: after create, in any order with ic_set_detrend; holds
+ * for the ic_runs that follow.  chan_*: the channel lines (over the subints,
+ * n = nsub); subint_*: the subint lines (over the channels, n = the session's
+ * nchan).  npieces == 0 with a NULL pointer: one piece in that direction.  A
+ * call with a direction non-zero selects the piecewise kernels for detrended
+ * runs (with one piece each as well); (0, NULL, 0, NULL) goes back to the
+ * whole-line kernels.  While detrending is off, pieces change nothing.
+ * IC_EINVAL: starts[0] != 0, starts not strictly ascending, a start >= n,
+ * npieces outside 0..512, a NULL pointer with npieces > 0, a channel-shard
+ * session.  IC_ENOMEM (from the run) when the pieces' buffers cannot be had.
+ * ic_get_trends_pieces: chan_coef [4][nchan][mc][4], subint_coef
+ * [4][nsub][ms][4] (mc, ms: the directions' piece counts); either may be NULL.
+ * IC_ESTATE as ic_get_trends, and when no pieces are set.  ic_get_trends
+ * itself returns IC_ESTATE while a direction has more than one piece.
+ * ic_comprehensive_stats_detrend_pieces: ic_comprehensive_stats_detrend with
+ * pieces (always the piecewise kernels); the coefficient outputs as
+ * ic_get_trends_pieces. */
+int ic_set_detrend_pieces(void *session, int chan_npieces, const int32_t *chan_starts, int subint_npieces,
+                          const int32_t *subint_starts);
+int ic_get_trends_pieces(void *session, double *chan_coef, double *subint_coef);
+int ic_comprehensive_stats_detrend_pieces(int device, int nsub, int nchan, int nbin, const float *data,
+                                          const float *weights, double chanthresh, double subintthresh,
+                                          double *test_out, double *std_out, double *mean_out, double *ptp_out,
+                                          double *fftmax_out, int data_f64, int chan_order, int subint_order,
+                                          int rounds, double clip, double *chan_coef, double *subint_coef,
+                                          int chan_npieces, const int32_t *chan_starts, int subint_npieces,
+                                          const int32_t *subint_starts);
+
+/* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
  * SURVEY.md §8(e)).  The reference cleans an archive in one process
  * (iterative_cleaner.py:83-146); these entry points split the same loop by

@@ -29,7 +29,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_set_delays2", "ic_rotate_profiles2", "ic_upload_quantised", "ic_upload_quantised_async",
            "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised",
            "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait",
-           "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend")
+           "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend",
+           "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -184,6 +185,10 @@ def load_library(path: str = LIB_PATH):
     lib.ic_comprehensive_stats_detrend.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double,
                                                    vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.c_double, vp, vp]
+    lib.ic_set_detrend_pieces.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    lib.ic_get_trends_pieces.argtypes = [vp, vp, vp]
+    lib.ic_comprehensive_stats_detrend_pieces.argtypes = (list(lib.ic_comprehensive_stats_detrend.argtypes)
+                                                          + [C.c_int, vp, C.c_int, vp])
     if lib.ic_abi_version() != ABI_VERSION:
         raise NativeError("libicgpu ABI %d != expected %d" % (lib.ic_abi_version(), ABI_VERSION))
     _lib = lib
@@ -197,6 +202,18 @@ def _err(lib) -> str:
 
 def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _piece_starts(spec, n):
+    """One direction's pieces (None, a count, "wN" or starts) on lines of n
+    entries -> (npieces, int32 starts or None) as the C-ABI takes them.  A list
+    of starts goes to the library as it is: the library checks it."""
+    from .detrend import piece_spec, resolve_pieces
+    sp = piece_spec(spec, "detrend_pieces")
+    if sp is None:
+        return 0, None
+    b = np.ascontiguousarray(sp if isinstance(sp, tuple) else resolve_pieces(sp, n), dtype=np.int32)
+    return int(b.shape[0]), b
 
 
 def device_count() -> int:
@@ -220,7 +237,7 @@ class GpuSession:
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
                  delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None,
-                 detrend=None):
+                 detrend=None, detrend_pieces=None):
         """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
         with these delays (set_delays).  dedisp_fft=True: the same mode without
         delays yet: they come with set_delays, or with each archive
@@ -229,7 +246,9 @@ class GpuSession:
         IC_DEDISP_FFT_ANY, which also serves any other nbin in 16..4096 by the
         chirp-z rotation (the lengths IC_DEDISP_FFT serves keep their bits).
         detrend = (chan_order, subint_order[, rounds, clip]): detrended scaling
-        (set_detrend; detrend.py); None: ic_set_detrend is never called."""
+        (set_detrend; detrend.py); None: ic_set_detrend is never called.
+        detrend_pieces = (chan, subint): piecewise detrending
+        (set_detrend_pieces); None: ic_set_detrend_pieces is never called."""
         from .phase_rotation import any_length_enabled
         fft_mode = DEDISP_FFT_ANY if (any_length_enabled() if any_length is None else any_length) else DEDISP_FFT
         self.lib = load_library()
@@ -253,6 +272,22 @@ class GpuSession:
             self._initial_delays(delay)
         if detrend is not None:
             self.set_detrend(*detrend)
+        self.pieces = None   # (mc, ms) while pieces are set
+        if detrend_pieces is not None:
+            self.set_detrend_pieces(*detrend_pieces)
+
+    def set_detrend_pieces(self, chan, subint):
+        """Piecewise detrending for the runs that follow (ic_set_detrend_pieces;
+        the definition is detrend.py): the pieces of the channel lines (over
+        the subints) and of the subint lines (over the channels), each None
+        (one piece), a count, "wN" (a piece every N entries) or a sequence of
+        starts.  With either given, detrended runs take the piecewise kernels;
+        (None, None) goes back to the whole-line ones.  Not on a channel shard."""
+        nsub, nchan, _ = self.shape
+        mc, cb = _piece_starts(chan, nsub)
+        ms, sb = _piece_starts(subint, nchan)
+        self._check(self.lib.ic_set_detrend_pieces(self.h, mc, _ptr(cb), ms, _ptr(sb)), "ic_set_detrend_pieces")
+        self.pieces = (max(mc, 1), max(ms, 1)) if (mc or ms) else None
 
     def set_detrend(self, chan_order, subint_order, rounds=4, clip=5.0):
         """Detrended scaling for the runs that follow (ic_set_detrend; the
@@ -264,8 +299,15 @@ class GpuSession:
     def trends(self):
         """The last iteration's trend coefficients (ic_get_trends): (chan
         (4, nchan, 4), subint (4, nsub, 4)) f64, a_0..a_3 per line, diagnostics
-        in the order std, mean, ptp, fftmax."""
+        in the order std, mean, ptp, fftmax.  While pieces are set
+        (set_detrend_pieces; ic_get_trends_pieces): (4, nchan, mc, 4) and
+        (4, nsub, ms, 4)."""
         nsub, nchan, _ = self.shape
+        if self.pieces is not None:
+            cc = np.empty((4, nchan, self.pieces[0], 4), np.float64)
+            sc = np.empty((4, nsub, self.pieces[1], 4), np.float64)
+            self._check(self.lib.ic_get_trends_pieces(self.h, _ptr(cc), _ptr(sc)), "ic_get_trends_pieces")
+            return cc, sc
         cc = np.empty((4, nchan, 4), np.float64)
         sc = np.empty((4, nsub, 4), np.float64)
         self._check(self.lib.ic_get_trends(self.h, _ptr(cc), _ptr(sc)), "ic_get_trends")
@@ -644,7 +686,7 @@ def rotate_profiles(cube, delay, sign=1, device=0, any_length=None):
 
 
 def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=0, diagnostics=False,
-                        rowstat_waves=8, rowstat_minlen=1024, detrend=None, data_f64=False):
+                        rowstat_waves=8, rowstat_minlen=1024, detrend=None, data_f64=False, detrend_pieces=None):
     """comprehensive_stats (iterative_cleaner.py:181-226) on the GPU for the
     (nsub, nchan, nbin) data and (nsub, nchan) weights the reference masks and
     weights at :111-117; returns test [, (std, mean, ptp, fftmax)].
@@ -653,7 +695,9 @@ def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=
     (ic_comprehensive_stats_detrend; detrend.py), with data_f64 the f64
     statistics of a psrchive build; returns test, (chan_coef (4, nchan, 4),
     subint_coef (4, nsub, 4)) [, (std, mean, ptp, fftmax)], ptp f64 with
-    data_f64."""
+    data_f64.  detrend_pieces = (chan, subint) (GpuSession.set_detrend_pieces;
+    needs detrend): the piecewise kernels (ic_comprehensive_stats_detrend_pieces),
+    the coefficients then (4, nchan, mc, 4) and (4, nsub, ms, 4)."""
     lib = load_library()
     data = np.ascontiguousarray(data, dtype=np.float32)
     if data.ndim != 3:
@@ -663,19 +707,31 @@ def comprehensive_stats(data, weights, chanthresh=5.0, subintthresh=5.0, device=
     test = np.empty((nsub, nchan), np.float64)
     if detrend is None and data_f64:
         raise ValueError("comprehensive_stats: data_f64 needs detrend")
+    if detrend is None and detrend_pieces is not None:
+        raise ValueError("comprehensive_stats: detrend_pieces needs detrend")
     if detrend is not None:
         t = tuple(detrend)
         co, so = t[:2]
         rounds, clip = (t[2] if len(t) > 2 else 4), (t[3] if len(t) > 3 else 5.0)
         sd, mn, pt, ff = (np.empty((nsub, nchan), np.float64) for _ in range(4))
-        cc = np.empty((4, nchan, 4), np.float64)
-        sc = np.empty((4, nsub, 4), np.float64)
-        rc = lib.ic_comprehensive_stats_detrend(int(device), nsub, nchan, nbin, _ptr(data), _ptr(w),
-                                                float(chanthresh), float(subintthresh), _ptr(test), _ptr(sd),
-                                                _ptr(mn), _ptr(pt), _ptr(ff), 1 if data_f64 else 0, int(co), int(so),
-                                                int(rounds), float(clip), _ptr(cc), _ptr(sc))
+        args = [int(device), nsub, nchan, nbin, _ptr(data), _ptr(w), float(chanthresh), float(subintthresh),
+                _ptr(test), _ptr(sd), _ptr(mn), _ptr(pt), _ptr(ff), 1 if data_f64 else 0, int(co), int(so),
+                int(rounds), float(clip)]
+        if detrend_pieces is not None:
+            chan, subint = detrend_pieces
+            mc, cb = _piece_starts(chan, nsub)
+            ms, sb = _piece_starts(subint, nchan)
+            cc = np.empty((4, nchan, max(mc, 1), 4), np.float64)
+            sc = np.empty((4, nsub, max(ms, 1), 4), np.float64)
+            name = "ic_comprehensive_stats_detrend_pieces"
+            rc = lib.ic_comprehensive_stats_detrend_pieces(*args, _ptr(cc), _ptr(sc), mc, _ptr(cb), ms, _ptr(sb))
+        else:
+            cc = np.empty((4, nchan, 4), np.float64)
+            sc = np.empty((4, nsub, 4), np.float64)
+            name = "ic_comprehensive_stats_detrend"
+            rc = lib.ic_comprehensive_stats_detrend(*args, _ptr(cc), _ptr(sc))
         if rc != 0:
-            raise NativeError("ic_comprehensive_stats_detrend: %s (rc=%d)" % (_err(lib), rc))
+            raise NativeError("%s: %s (rc=%d)" % (name, _err(lib), rc))
         if not data_f64:
             pt = pt.astype(np.float32)   # exact: f32 values
         return (test, (cc, sc), (sd, mn, pt, ff)) if diagnostics else (test, (cc, sc))

@@ -105,7 +105,7 @@ class _ResidualQueue:
         return out, j
 
 
-def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None):
+def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, detrend_pieces=None):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -132,9 +132,12 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None):
 
     detrend = (chan_order, subint_order[, rounds, clip]): set on the session
     before the first run (GpuSession.set_detrend); None leaves the session as
-    it is."""
+    it is.  detrend_pieces = (chan, subint): likewise
+    (GpuSession.set_detrend_pieces)."""
     if detrend is not None:
         session.set_detrend(*detrend)
+    if detrend_pieces is not None:
+        session.set_detrend_pieces(*detrend_pieces)
     rq = _ResidualQueue(session, _residual_slots(session, residuals)) if residuals is not None else None
 
     def after_run(out):
@@ -402,7 +405,8 @@ class _ResultRing:
 def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
-                any_length=None, residuals=False, residual_big_endian=True, detrend=None):
+                any_length=None, residuals=False, residual_big_endian=True, detrend=None,
+                detrend_pieces=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -444,9 +448,11 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
 
     detrend = (chan_order, subint_order[, rounds, clip]): the opt-in detrended
     scaling (detrend.py) on every lane's session; None reads the IC_DETREND
-    switch (unset, empty or 0: off)."""
-    from .detrend import normalise
+    switch (unset, empty or 0: off).  detrend_pieces = (chan, subint): piecewise
+    detrending (cleaner.run_loop's); None reads the IC_DETREND_PIECES switch."""
+    from .detrend import normalise, normalise_pieces
     detrend = normalise(detrend)
+    detrend_pieces = normalise_pieces(detrend_pieces, int(shape[0]), int(shape[1]), detrend)
     if dedisp not in ("shift", "fft"):
         raise ValueError("dedisp must be 'shift' or 'fft', not %r" % (dedisp,))
     fft = dedisp == "fft"
@@ -562,7 +568,8 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
             sessions.append(_native.GpuSession(nsub, nchan, nbin, max_iter, chanthresh, subintthresh,
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
-                                               dedisp_fft=fft, any_length=any_length, detrend=detrend))
+                                               dedisp_fft=fft, any_length=any_length, detrend=detrend,
+                                               detrend_pieces=detrend_pieces))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
                               residuals=[rr.triples() for rr in result_rings] if residuals else None)
         for k, out in enumerate(lanes_gen):

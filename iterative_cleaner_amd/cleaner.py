@@ -208,7 +208,7 @@ def _device() -> int:
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
              data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
-             detrend=None):
+             detrend=None, detrend_pieces=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -226,8 +226,12 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     ``residual`` is returned as ever).  ``detrend`` = (chan_order,
     subint_order[, rounds, clip]): the opt-in detrended scaling (detrend.py);
     None reads the switch IC_DETREND="chan,subint[,rounds,clip]" (unset, empty
-    or 0: off).  Not under channel sharding (ValueError)."""
-    from .detrend import normalise
+    or 0: off).  Not under channel sharding (ValueError).  ``detrend_pieces`` =
+    (chan, subint): piecewise detrending (detrend.py), each side None, a piece
+    count, "wN" (a piece every N entries) or the pieces' starts; None reads the
+    switch IC_DETREND_PIECES="<chan>;<subint>".  Without a detrend order in a
+    direction its pieces are ignored."""
+    from .detrend import normalise, normalise_pieces
     from .dist import channel_sharding
     detrend = normalise(detrend)
     if detrend is not None and channel_sharding():
@@ -238,6 +242,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
         cube = quantised[0]
     pols = cube.ndim == 4
     nsub, nchan, nbin = (cube.shape[0], cube.shape[2], cube.shape[3]) if pols else cube.shape
+    detrend_pieces = normalise_pieces(detrend_pieces, nsub, nchan, detrend)
     if channel_sharding():
         import torch
 
@@ -263,7 +268,8 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     with _native.GpuSession(nsub, nchan, nbin, args.max_iter, args.chanthresh, args.subintthresh,
                             args.pulse_region, baseline_duty,
                             device=_device() if device is None else device, data_f64=data_f64, delay=delay,
-                            input_dedispersed=input_dedispersed, detrend=detrend) as s:
+                            input_dedispersed=input_dedispersed, detrend=detrend,
+                            detrend_pieces=detrend_pieces) as s:
         if quantised is not None:
             s.upload_quantised(quantised[0], quantised[1], quantised[2], w0, shift, quantised[3])
         elif pols:
@@ -325,9 +331,10 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch, detrend=None):
-    """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend:
-    run_loop's (None = the IC_DETREND switch; there is no CLI flag).  Under
+def clean(ar, args, arch, detrend=None, detrend_pieces=None):
+    """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend,
+    detrend_pieces: run_loop's (None = the IC_DETREND / IC_DETREND_PIECES
+    switches; there is no CLI flag).  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -375,7 +382,7 @@ def clean(ar, args, arch, detrend=None):
     out = run_loop(cube, orig_weights, shift, args, want_residual=args.unload_res, baseline_duty=duty,
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
-                   residual_quantised=psrfits_res, detrend=detrend)
+                   residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces)
     del cube
 
     x = 0

@@ -155,6 +155,18 @@ struct TrendArgs {
     double *row_coef;   // [4][nsub][4]
 };
 
+// Piecewise detrending (ic_set_detrend_pieces; detrend.py): a direction's lines
+// are cut at the same starts, and every piece is fitted on its own abscissa.
+// With pieces the coefficient arrays of TrendArgs are [4][nchan][col_np][4] and
+// [4][nsub][row_np][4].  "col": the channel lines (over the subints, n = nsub);
+// "row": the subint lines (over the channels, n = nchan).
+constexpr int kMaxPieces = 512;   // the pieces' coefficients live in LDS: 512 x 32 B
+struct PieceArgs {
+    int col_np, row_np;                       // pieces per line, 1..kMaxPieces
+    const int32_t *col_starts, *row_starts;   // [np + 1]: the starts, then n
+    const int16_t *col_piece, *row_piece;     // [nsub], [nchan]: the piece of an entry
+};
+
 // Grid cap (session option IC_OPT_GRID_CAP): the launchers whose grid is
 // min(blocks the work needs, a constant) launch min(that, grid_cap) blocks when
 // grid_cap > 0, so that a small archive drives every grid-stride loop through
@@ -468,6 +480,15 @@ hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t 
                              const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
                              double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
                              int grid_cap = 0);
+// the piecewise forms (k_linetrend_pw, k_combine_pw), as the two above
+hipError_t launch_linetrend_pw(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pc,
+                               int which = 3);
+hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                             const PieceArgs &pc, int grid_cap = 0);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
 // bins, n even (<= 8192; 1/n and 4/n are rounded factors unless n is a power
 // of two): the phase rotation's multiplier

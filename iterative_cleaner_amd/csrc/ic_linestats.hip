@@ -1,6 +1,7 @@
 // ic_linestats.hip -- per channel / subint median and MAD (ic.py:229-256) and
 // the combine step (ic.py:221-225, :303-305, :127-141), with their launchers,
-// and the opt-in detrended forms of both (k_linetrend, k_combine_dt; detrend.py).
+// and the opt-in detrended forms of both (k_linetrend, k_combine_dt; detrend.py),
+// whole-line and piecewise (k_linetrend_pw, k_combine_pw).
 // The non-inlined wave_* / grp_* selection functions live here with all
 // their callers.
 #include <algorithm>
@@ -474,6 +475,10 @@ __device__ __forceinline__ double line_value(const LineStatsArgs &a, int diag, s
     return diag == 0 ? a.std_d[kk] : diag == 1 ? a.mean_d[kk] : diag == 2 ? a.ptp_d[kk] : a.fft_d[kk];
 }
 
+// the chains' halving tree and the elimination, below both fits: S, B hold a
+// lane's chain on entry.  false: a refused pivot
+template <int K> __device__ __forceinline__ bool trend_solve(double (&S)[2 * K + 1], double (&B)[K + 1], TrendCoef &out);
+
 // one fit of order K over the entries of `use` (bit j of use[j / 64]): the 64
 // chains are the wave's lanes, whatever the block's wave count (every wave of
 // the block computes the same sums).  false: the trend is zero.
@@ -501,6 +506,44 @@ __device__ bool trend_fit(const LineStatsArgs &a, int diag, int rows, int idx, i
             }
         }
     }
+    return trend_solve<K>(S, B, out);
+}
+
+// the statement's piecewise fit of one piece [b, b + L) of a line: trend_fit on
+// the piece's own abscissa, the 64 chains by the local index i = j - b.  false:
+// the piece is retired (<= K members, or a refused pivot).
+template <int K>
+__device__ bool piece_fit(const LineStatsArgs &a, int diag, int rows, int idx, int b, int L,
+                          const unsigned long long *use, int lane, TrendCoef &out)
+{
+    double S[2 * K + 1], B[K + 1];
+#pragma unroll
+    for (int p = 0; p <= 2 * K; ++p) S[p] = 0.0;
+#pragma unroll
+    for (int p = 0; p <= K; ++p) B[p] = 0.0;
+    int members = 0;
+    for (int i0 = 0; i0 < L; i0 += 64) {
+        const int i = i0 + lane, j = b + i;
+        const bool in = i < L && ((use[j >> 6] >> (j & 63)) & 1ull);
+        members += __popcll(__ballot(in));
+        if (in) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + j : (size_t)j * a.nchan + idx;
+            const double x = trend_x(i, L), y = line_value(a, diag, kk);
+            double xp = 1.0;
+#pragma unroll
+            for (int p = 0; p <= 2 * K; ++p) {
+                S[p] = S[p] + xp;
+                if (p <= K) B[p] = B[p] + xp * y;
+                xp = xp * x;
+            }
+        }
+    }
+    if (members <= K) return false;
+    return trend_solve<K>(S, B, out);
+}
+
+template <int K> __device__ __forceinline__ bool trend_solve(double (&S)[2 * K + 1], double (&B)[K + 1], TrendCoef &out)
+{
     // halving tree over the chains: t[l] = t[l] + t[l + h], h = 32 .. 1
 #pragma unroll
     for (int p = 0; p <= 2 * K; ++p) {
@@ -688,6 +731,177 @@ __global__ __launch_bounds__(64 * W) void k_linetrend(LineStatsArgs a, TrendArgs
     }
 }
 
+// ---- piecewise detrending (ic_set_detrend_pieces; detrend.py) ------------------
+// A direction's lines are cut at the same starts; every piece is fitted on its
+// own abscissa, the membership and the stop rules stay the line's.
+
+// entry q of a line: its piece p, its local index i and the piece's length L
+struct PieceAt {
+    int p, i, L;
+};
+__device__ __forceinline__ PieceAt piece_at(int q, const int16_t *__restrict__ piece, const int32_t *__restrict__ starts)
+{
+    const int p = piece[q], b = starts[p];
+    return PieceAt{p, q - b, starts[p + 1] - b};
+}
+
+// k_linetrend with the fit per piece.  LDS: k_linetrend's, then the line's piece
+// coefficients pc[m] and retired flags ret[m].  Piece p is fitted by wave p mod
+// W (the chains are that wave's lanes by the local index, so no sum depends on
+// W) and published through pc across a barrier; residuals, clipping and d' look
+// an entry's piece up in piece_of / starts.
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_linetrend_pw(LineStatsArgs a, TrendArgs t, PieceArgs pa, int rows, int len)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned *hist = (unsigned *)lsm;
+    GrpRed<W> g{(unsigned long long *)(lsm + 1024), wave, lane};
+    const int nline = rows ? a.nsub : a.nchan;
+    const int line = blockIdx.x;
+    const int diag = line / nline, idx = line % nline;
+    const bool f32 = diag == 2 && a.ptp_f32, plain = diag == 3;
+    const int k = rows ? t.subint_order : t.chan_order;
+    const int m = rows ? pa.row_np : pa.col_np;
+    const int32_t *__restrict__ starts = rows ? pa.row_starts : pa.col_starts;
+    const int16_t *__restrict__ piece = rows ? pa.row_piece : pa.col_piece;
+    const int seg = (((len + W - 1) / W) + 63) & ~63;
+    const int q0w = min(len, wave * seg), q1w = min(len, q0w + seg);
+    unsigned long long *keys = (unsigned long long *)(lsm + 1024 + 16 * W) + (size_t)wave * seg;
+    unsigned long long *use = (unsigned long long *)(lsm + 1024 + 16 * W) + (size_t)W * seg;
+    TrendCoef *pc = (TrendCoef *)(use + (len + 63) / 64);
+    unsigned char *ret = (unsigned char *)(pc + m);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const TrendCoef zero{0.0, 0.0, 0.0, 0.0};
+    for (int p = threadIdx.x; p < m; p += 64 * W) {
+        pc[p] = zero;
+        ret[p] = 0;
+    }
+    // membership = valid; any valid value not finite: no trend
+    int nv = 0, bad = 0;
+    for (int q0 = q0w; q0 < q1w; q0 += 64) {
+        const int q = q0 + lane;
+        bool v = false;
+        if (q < q1w) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            bad |= v && !isfinite(line_value(a, diag, kk));
+        }
+        const unsigned long long mk = __ballot(v);
+        if (lane == 0) use[q0 >> 6] = mk;
+        nv += __popcll(mk);
+    }
+    bad = g.sum_uniform(__any(bad) ? 1 : 0);   // the barrier also publishes the membership words, pc and ret
+    nv = g.sum_uniform(nv);
+    if (k > 0 && nv > 0 && !bad) {
+        int nuse = nv;
+        for (int r = 1; r <= t.rounds; ++r) {
+            for (int p = wave; p < m; p += W) {
+                if (ret[p]) continue;   // this wave's own flag, uniform
+                const int b = starts[p], L = starts[p + 1] - b;
+                TrendCoef c = zero;   // a retired piece's: piece_fit writes c only when it succeeds
+                const bool ok = k == 1   ? piece_fit<1>(a, diag, rows, idx, b, L, use, lane, c)
+                                : k == 2 ? piece_fit<2>(a, diag, rows, idx, b, L, use, lane, c)
+                                         : piece_fit<3>(a, diag, rows, idx, b, L, use, lane, c);
+                if (lane == 0) {
+                    pc[p] = c;
+                    if (!ok) ret[p] = 1;
+                }
+            }
+            __syncthreads();   // every piece's coefficients of this round
+            if (r == t.rounds || nuse == 0) break;
+            // e = y - p_q(x) over the membership, this wave's slice
+            int cnt = 0, nf = 0;
+            for (int q0 = q0w; q0 < q1w; q0 += 64) {
+                const int q = q0 + lane;
+                const bool in = q < q1w && ((use[q0 >> 6] >> lane) & 1ull);
+                double e = 0.0;
+                if (in) {
+                    const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+                    const PieceAt at = piece_at(q, piece, starts);
+                    e = line_value(a, diag, kk) - trend_poly(trend_x(at.i, at.L), pc[at.p], k);
+                }
+                const unsigned long long mk = __ballot(in);
+                if (in) keys[cnt + __popcll(mk & below)] = key64(e);
+                nf |= in && !isfinite(e);
+                cnt += __popcll(mk);
+            }
+            nf = g.sum_uniform(__any(nf) ? 1 : 0);
+            if (nf) break;
+            const double med = grp_median<W>(g, keys, cnt, nuse, false, hist);
+            for (int j = lane; j < cnt; j += 64) keys[j] = key64(fabs(unkey64(keys[j]) - med));
+            const double mad = grp_median<W>(g, keys, cnt, nuse, false, hist);
+            if (mad == 0.0) break;
+            const double lim = t.clip * mad;
+            int changed = 0, nn = 0;
+            for (int q0 = q0w; q0 < q1w; q0 += 64) {
+                const int q = q0 + lane;
+                bool in = false;
+                if (q < q1w) {
+                    const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+                    if (plain ? true : (a.valid[kk] != 0)) {
+                        const PieceAt at = piece_at(q, piece, starts);
+                        const double e = line_value(a, diag, kk) - trend_poly(trend_x(at.i, at.L), pc[at.p], k);
+                        in = fabs(e - med) <= lim;
+                    }
+                }
+                const unsigned long long mk = __ballot(in);
+                changed |= mk != use[q0 >> 6];
+                if (lane == 0) use[q0 >> 6] = mk;   // this wave's words: read by the others after the barrier below
+                nn += __popcll(mk);
+            }
+            changed = g.sum_uniform(changed);
+            nuse = g.sum_uniform(nn);
+            if (!changed) break;
+        }
+    }
+    // median and MAD of d', as k_linestats_grp takes them of d
+    int cnt = 0, nan = 0;
+    for (int q0 = q0w; q0 < q1w; q0 += 64) {
+        const int q = q0 + lane;
+        double d = 0.0;
+        bool v = false;
+        if (q < q1w) {
+            const size_t kk = rows ? (size_t)idx * a.nchan + q : (size_t)q * a.nchan + idx;
+            v = plain ? true : (a.valid[kk] != 0);
+            if (v) {
+                const PieceAt at = piece_at(q, piece, starts);
+                d = detrend_value(line_value(a, diag, kk), f32, at.i, at.L, pc[at.p], k);
+            }
+        }
+        const unsigned long long mk = __ballot(v);
+        if (v) keys[cnt + __popcll(mk & below)] = key64(d);
+        nan |= v && isnan(d);
+        cnt += __popcll(mk);
+    }
+    nan = g.sum_uniform(__any(nan) ? 1 : 0);
+    double med = NAN, mad = NAN;
+    if (nv > 0 && !nan) {
+        med = grp_median<W>(g, keys, cnt, nv, f32, hist);
+        int rnan = 0;
+        for (int j = lane; j < cnt; j += 64) {
+            const double d = unkey64(keys[j]);
+            const double r = f32 ? (double)fabsf((float)d - (float)med) : fabs(d - med);
+            rnan |= isnan(r);
+            keys[j] = key64(r);
+        }
+        rnan = g.sum_uniform(__any(rnan) ? 1 : 0);
+        if (!rnan) mad = grp_median<W>(g, keys, cnt, nv, f32, hist);
+    }
+    // the line's coefficients [m][4]; pc is final since the barrier after the last fit
+    double *coef = (rows ? t.row_coef : t.col_coef) + ((size_t)diag * nline + idx) * m * 4;
+    for (int i = threadIdx.x; i < 4 * m; i += 64 * W) coef[i] = ((const double *)pc)[i];
+    if (threadIdx.x == 0) {
+        if (!rows) {
+            a.col_med[diag * a.nchan + idx] = med;
+            a.col_mad[diag * a.nchan + idx] = mad;
+        } else {
+            a.row_med[diag * a.nsub + idx] = med;
+            a.row_mad[diag * a.nsub + idx] = mad;
+        }
+    }
+}
+
 // ============================================================ combine
 
 __device__ __forceinline__ double scale_masked_d(double dv, bool valid, double med, double mad, double thr)
@@ -743,13 +957,21 @@ constexpr double kNearTie = 1e-9;
 // direction's d' (detrend_value with the line's coefficients; invalid entries
 // keep d); the rest is k_combine's.  bdim / gdim: the kernel's blockDim.x /
 // gridDim.x, read in the kernel
+// TR = PieceView: the piecewise form (k_combine_pw): as TrendView, the d' of an
+// entry formed with its piece's coefficients on the piece's abscissa
 struct NoTrend {
-    static constexpr bool on = false;
+    static constexpr bool on = false, pieces = false;
 };
 struct TrendView {
-    static constexpr bool on = true;
+    static constexpr bool on = true, pieces = false;
     const TrendCoef *col_coef, *row_coef;   // [4][nchan], [4][nsub]
     int chan_order, subint_order;
+};
+struct PieceView {
+    static constexpr bool on = true, pieces = true;
+    const TrendCoef *col_coef, *row_coef;   // [4][nchan][col_np], [4][nsub][row_np]
+    int chan_order, subint_order;
+    PieceArgs pa;
 };
 template <class TR>
 __device__ __forceinline__ void combine_body(
@@ -778,14 +1000,30 @@ __device__ __forceinline__ void combine_body(
             // in its subint line (entry c of nchan)
             const double dv[4] = {std_d[k], mean_d[k], ptp_d[k], fft_d[k]};
             double dc[4], ds[4];
+            if constexpr (TR::pieces) {
+                // the same, on the abscissa and with the coefficients of the
+                // entry's piece of either line
+                const PieceAt ac = piece_at(s, tr.pa.col_piece, tr.pa.col_starts);
+                const PieceAt as = piece_at(c, tr.pa.row_piece, tr.pa.row_starts);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool f32 = q == 2 && ptp_f32;
-                const bool in = q == 3 || v;
-                dc[q] = in ? detrend_value(dv[q], f32, s, nsub, tr.col_coef[(size_t)q * nchan + c], tr.chan_order)
-                           : dv[q];
-                ds[q] = in ? detrend_value(dv[q], f32, c, nchan, tr.row_coef[(size_t)q * nsub + s], tr.subint_order)
-                           : dv[q];
+                for (int q = 0; q < 4; ++q) {
+                    const bool f32 = q == 2 && ptp_f32;
+                    const bool in = q == 3 || v;
+                    const TrendCoef *cc = tr.col_coef + ((size_t)q * nchan + c) * tr.pa.col_np + ac.p;
+                    const TrendCoef *rc = tr.row_coef + ((size_t)q * nsub + s) * tr.pa.row_np + as.p;
+                    dc[q] = in ? detrend_value(dv[q], f32, ac.i, ac.L, *cc, tr.chan_order) : dv[q];
+                    ds[q] = in ? detrend_value(dv[q], f32, as.i, as.L, *rc, tr.subint_order) : dv[q];
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool f32 = q == 2 && ptp_f32;
+                    const bool in = q == 3 || v;
+                    dc[q] = in ? detrend_value(dv[q], f32, s, nsub, tr.col_coef[(size_t)q * nchan + c], tr.chan_order)
+                               : dv[q];
+                    ds[q] = in ? detrend_value(dv[q], f32, c, nchan, tr.row_coef[(size_t)q * nsub + s], tr.subint_order)
+                               : dv[q];
+                }
             }
             S[0] = nanmax2(scale_masked_d(dc[0], v, col_med[c], col_mad[c], cth),
                            scale_masked_d(ds[0], v, row_med[s], row_mad[s], sth));
@@ -908,6 +1146,21 @@ __global__ __launch_bounds__(256) void k_combine_dt(
                  TrendView{(const TrendCoef *)t.col_coef, (const TrendCoef *)t.row_coef, t.chan_order, t.subint_order});
 }
 
+__global__ __launch_bounds__(256) void k_combine_pw(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters, TrendArgs t, PieceArgs pa)
+{
+    combine_body(nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad,
+                 cth, sth, test, W, hist, iter, counters, blockDim.x, gridDim.x,
+                 PieceView{(const TrendCoef *)t.col_coef, (const TrendCoef *)t.row_coef, t.chan_order, t.subint_order,
+                           pa});
+}
+
 // ============================================================ launchers
 
 hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
@@ -986,6 +1239,61 @@ hipError_t launch_linetrend(hipStream_t st, const LineStatsArgs &a, const TrendA
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// the piecewise line stage: launch_linetrend's shapes; LDS also holds a line's
+// piece coefficients (32 B each) and retired flags
+template <int W>
+static hipError_t launch_linetrend_pw_w(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pa,
+                                        int rows, int len, int lines, bool *done)
+{
+    const int seg = (((len + W - 1) / W) + 63) & ~63;
+    const size_t m = (size_t)(rows ? pa.row_np : pa.col_np);
+    const size_t shm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8 + (size_t)((len + 63) / 64) * 8 + m * 32 +
+                       ((m + 15) & ~(size_t)15);
+    *done = shm <= kLdsBlockMax;
+    if (!*done) return hipSuccess;
+    IC_GGL(k_linetrend_pw<W>, dim3(lines), dim3(64 * W), shm, st, a, t, pa, rows, len);
+    return hipGetLastError();
+}
+
+hipError_t launch_linetrend_pw(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pa,
+                               int which)
+{
+    if (pa.col_np < 1 || pa.col_np > kMaxPieces || pa.row_np < 1 || pa.row_np > kMaxPieces)
+        return hipErrorInvalidValue;
+    for (int rows = 0; rows < 2; ++rows) {
+        if (!((which >> rows) & 1)) continue;
+        const int len = rows ? a.nchan : a.nsub;
+        const int lines = 4 * (rows ? a.nsub : a.nchan);
+        if (lines == 0 || len == 0) continue;
+        bool done = false;
+        hipError_t e = hipSuccess;
+        if (lines < 8192 && len >= a.grp_minlen) {
+            if (a.grp_waves == 4) e = launch_linetrend_pw_w<4>(st, a, t, pa, rows, len, lines, &done);
+            if (a.grp_waves == 8) e = launch_linetrend_pw_w<8>(st, a, t, pa, rows, len, lines, &done);
+        }
+        if (!done) {
+            e = launch_linetrend_pw_w<1>(st, a, t, pa, rows, len, lines, &done);
+            if (!done) return hipErrorInvalidValue;
+        }
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                             const PieceArgs &pa, int grid_cap)
+{
+    const size_t P = (size_t)nsub * nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
+    IC_GGL(k_combine_pw, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
+           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t, pa);
+    return hipGetLastError();
 }
 
 hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,

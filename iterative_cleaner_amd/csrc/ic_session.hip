@@ -246,6 +246,17 @@ struct Session {
     double dt_clip = 5.0;
     double *trend = nullptr;
     bool trends_ran = false;
+    // piecewise detrending (ic_set_detrend_pieces): pw_on selects k_linetrend_pw /
+    // k_combine_pw for detrended runs; pw_cs / pw_ss: the starts of a channel
+    // line's / a subint line's pieces ({0}: one piece).  The device copies
+    // (pw_starts: both lists, each closed by its n; pw_piece: the piece of every
+    // subint, then of every channel; pw_trend: [4][nchan][mc][4] then
+    // [4][nsub][ms][4]) come from `mem` at the first run after a change
+    bool pw_on = false;
+    std::vector<int32_t> pw_cs{0}, pw_ss{0};
+    int32_t *pw_starts = nullptr;
+    int16_t *pw_piece = nullptr;
+    double *pw_trend = nullptr;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -1930,6 +1941,48 @@ DiagArgs diag_args(Session *s, int pr_start, int pr_end)
     return a;
 }
 
+// ---- piecewise detrending: the pieces of a direction (ic_set_detrend_pieces) ----
+// starts[0..np) of lines of n entries; np == 0 with no pointer: one piece.
+// 0 or the message
+const char *pieces_range(int np, const int32_t *starts, int n)
+{
+    if (np < 0 || np > kMaxPieces) return "npieces outside 0..512";
+    if (np == 0) return nullptr;
+    if (!starts) return "null starts with npieces > 0";
+    if (starts[0] != 0) return "the first start is not 0";
+    for (int q = 0; q < np; ++q) {
+        if (q > 0 && starts[q] <= starts[q - 1]) return "starts not strictly ascending";
+        if (starts[q] >= n) return "a start at or past the line's length";
+    }
+    return nullptr;
+}
+
+// the kernels' tables of checked pieces: both directions' starts, each list
+// closed by its n, and the piece of every subint, then of every channel
+struct PieceTables {
+    std::vector<int32_t> starts;
+    std::vector<int16_t> piece;
+};
+PieceTables piece_tables(const std::vector<int32_t> &cs, const std::vector<int32_t> &ss, int nsub, int nchan)
+{
+    PieceTables t;
+    for (int dir = 0; dir < 2; ++dir) {
+        const std::vector<int32_t> &b = dir ? ss : cs;
+        const int n = dir ? nchan : nsub;
+        t.starts.insert(t.starts.end(), b.begin(), b.end());
+        t.starts.push_back(n);
+        for (size_t q = 0; q < b.size(); ++q)
+            t.piece.insert(t.piece.end(), (size_t)((q + 1 < b.size() ? b[q + 1] : n) - b[q]), (int16_t)q);
+    }
+    return t;
+}
+// the tables on the device (starts: cs.size() + ss.size() + 2 words; piece: nsub + nchan)
+PieceArgs piece_args(const std::vector<int32_t> &cs, const std::vector<int32_t> &ss, int nsub, const int32_t *starts,
+                     const int16_t *piece)
+{
+    return PieceArgs{(int)cs.size(), (int)ss.size(), starts, starts + cs.size() + 1, piece, piece + nsub};
+}
+
 int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_out, int32_t *changed_out,
              int32_t *nzero_out, int32_t *n_iter_out, int32_t *converged_out)
 {
@@ -1992,10 +2045,32 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     la.row_mad = s->lstat + 8 * nchan + 4 * nsub;
     const bool detrend = s->dt_chan > 0 || s->dt_sub > 0;
     s->trends_ran = false;
-    if (detrend && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
+    if (detrend && !s->pw_on && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(trend coefficients: %zu doubles) failed", (size_t)16 * (nchan + nsub));
-    const TrendArgs ta{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
-                       s->trend ? s->trend + (size_t)16 * nchan : nullptr};
+    TrendArgs ta{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
+                 s->trend ? s->trend + (size_t)16 * nchan : nullptr};
+    // piecewise (ic_set_detrend_pieces): its own tables and coefficient arrays
+    const bool pieces = detrend && s->pw_on;
+    PieceArgs pa{};
+    if (pieces) {
+        const size_t mc = s->pw_cs.size(), ms = s->pw_ss.size();
+        if (!s->pw_trend) {   // allocated last: set once all three are there
+            const PieceTables pt = piece_tables(s->pw_cs, s->pw_ss, nsub, nchan);
+            if (s->mem.ensure(&s->pw_starts, pt.starts.size()) != hipSuccess ||
+                s->mem.ensure(&s->pw_piece, pt.piece.size()) != hipSuccess ||
+                s->mem.ensure(&s->pw_trend, 16 * ((size_t)nchan * mc + (size_t)nsub * ms)) != hipSuccess)
+                return fail(IC_ENOMEM, "hipMalloc(piecewise trends: %zu doubles) failed",
+                            16 * ((size_t)nchan * mc + (size_t)nsub * ms));
+            CK(hipMemcpyAsync(s->pw_starts, pt.starts.data(), sizeof(int32_t) * pt.starts.size(),
+                              hipMemcpyHostToDevice, s->stream));
+            CK(hipMemcpyAsync(s->pw_piece, pt.piece.data(), sizeof(int16_t) * pt.piece.size(), hipMemcpyHostToDevice,
+                              s->stream));
+            CK(hipStreamSynchronize(s->stream));   // pt goes out of scope
+        }
+        pa = piece_args(s->pw_cs, s->pw_ss, nsub, s->pw_starts, s->pw_piece);
+        ta.col_coef = s->pw_trend;
+        ta.row_coef = s->pw_trend + 16 * (size_t)nchan * mc;
+    }
     int32_t *cnt = s->h_small;   // [max_iter + 5] counters, then the run stats (pinned)
     s->bad_fits.clear();
     int x = 0, loops = -1, n_iter = 0, converged = 0;
@@ -2076,7 +2151,9 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
             LAUNCH(s, K_DIAG, launch_diag(s->stream, da));
         }
         // channel medians are local to a shard; row medians need whole rows
-        if (detrend) {   // never a shard (ic_set_detrend refuses those)
+        if (pieces) {
+            LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, la, ta, pa, 3));
+        } else if (detrend) {   // never a shard (ic_set_detrend refuses those)
             LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 3));
         } else {
             LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, la, s->comm ? 1 : 3));
@@ -2084,7 +2161,12 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
                 if (int rc = shard_rowstats(s, la)) return rc;
         }
         CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + 5), s->stream));
-        if (detrend) {
+        if (pieces) {
+            LAUNCH(s, K_COMBINE,
+                   launch_combine_pw(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
+                                     la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
+                                     p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, ta, pa, s->grid_cap));
+        } else if (detrend) {
             LAUNCH(s, K_COMBINE,
                    launch_combine_dt(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
                                      la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
@@ -2611,10 +2693,56 @@ int ic_get_trends(void *session, double *chan_coef, double *subint_coef)
     if (s->failed) return failed_session();
     if (!(s->dt_chan > 0 || s->dt_sub > 0)) return fail(IC_ESTATE, "detrending is off (ic_set_detrend)");
     if (!s->ran || !s->trends_ran) return fail(IC_ESTATE, "no completed detrended iteration");
+    if (s->pw_on && (s->pw_cs.size() > 1 || s->pw_ss.size() > 1))
+        return fail(IC_ESTATE, "a direction has more than one piece: ic_get_trends_pieces");
+    // one piece each: the piecewise arrays have this layout
+    const double *trend = s->pw_on ? s->pw_trend : s->trend;
     const size_t nc = (size_t)16 * s->nchan, ns = (size_t)16 * s->p.nsub;
-    if (chan_coef) CK(hipMemcpyAsync(chan_coef, s->trend, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
+    if (chan_coef) CK(hipMemcpyAsync(chan_coef, trend, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
     if (subint_coef)
-        CK(hipMemcpyAsync(subint_coef, s->trend + nc, sizeof(double) * ns, hipMemcpyDeviceToHost, s->stream));
+        CK(hipMemcpyAsync(subint_coef, trend + nc, sizeof(double) * ns, hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    return IC_OK;
+}
+
+int ic_set_detrend_pieces(void *session, int chan_npieces, const int32_t *chan_starts, int subint_npieces,
+                          const int32_t *subint_starts)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (s->comm || s->world > 1)
+        return fail(IC_EINVAL, "ic_set_detrend_pieces on a channel shard: detrended rows across shards are not supported");
+    if (const char *e = pieces_range(chan_npieces, chan_starts, s->p.nsub))
+        return fail(IC_EINVAL, "ic_set_detrend_pieces, channel lines (%d entries): %s", s->p.nsub, e);
+    if (const char *e = pieces_range(subint_npieces, subint_starts, s->nchan))
+        return fail(IC_EINVAL, "ic_set_detrend_pieces, subint lines (%d entries): %s", s->nchan, e);
+    s->pw_on = chan_npieces > 0 || subint_npieces > 0;
+    s->pw_cs.assign(1, 0);
+    s->pw_ss.assign(1, 0);
+    if (chan_npieces > 0) s->pw_cs.assign(chan_starts, chan_starts + chan_npieces);
+    if (subint_npieces > 0) s->pw_ss.assign(subint_starts, subint_starts + subint_npieces);
+    // the tables and coefficient arrays of the pieces before: a run ends
+    // synchronised, so nothing reads them; the next piecewise run allocates anew
+    s->mem.release(s->pw_starts);
+    s->mem.release(s->pw_piece);
+    s->mem.release(s->pw_trend);
+    s->trends_ran = false;
+    return IC_OK;
+}
+
+int ic_get_trends_pieces(void *session, double *chan_coef, double *subint_coef)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!(s->dt_chan > 0 || s->dt_sub > 0)) return fail(IC_ESTATE, "detrending is off (ic_set_detrend)");
+    if (!s->pw_on) return fail(IC_ESTATE, "no pieces are set (ic_set_detrend_pieces)");
+    if (!s->ran || !s->trends_ran) return fail(IC_ESTATE, "no completed detrended iteration");
+    const size_t nc = (size_t)16 * s->nchan * s->pw_cs.size(), ns = (size_t)16 * s->p.nsub * s->pw_ss.size();
+    if (chan_coef) CK(hipMemcpyAsync(chan_coef, s->pw_trend, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
+    if (subint_coef)
+        CK(hipMemcpyAsync(subint_coef, s->pw_trend + nc, sizeof(double) * ns, hipMemcpyDeviceToHost, s->stream));
     CK(hipStreamSynchronize(s->stream));
     return IC_OK;
 }
@@ -2686,12 +2814,16 @@ int ic_comprehensive_stats(int device, int nsub, int nchan, int nbin, const floa
 }
 
 // the one-shot statistics; dt (optional): detrended (k_linetrend, k_combine_dt),
-// its coefficient pointers host outputs (may be null).  ptp goes to ptp_o (f32)
-// or ptp64_o.
+// its coefficient pointers host outputs (may be null); pieces (optional, with
+// dt): checked starts of both directions, the piecewise kernels and coefficient
+// layout.  ptp goes to ptp_o (f32) or ptp64_o.
+struct PieceSpec {
+    std::vector<int32_t> cs, ss;
+};
 static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
                          double chanthresh, double subintthresh, double *test_out, double *std_o, double *mean_o,
                          float *ptp_o, double *ptp64_o, double *fftmax_o, int rowstat_waves, int rowstat_minlen,
-                         int data_f64, const TrendArgs *trend);
+                         int data_f64, const TrendArgs *trend, const PieceSpec *pieces = nullptr);
 
 int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, const float *data,
                                    const float *weights, double chanthresh, double subintthresh, double *test_out,
@@ -2716,10 +2848,33 @@ int ic_comprehensive_stats_detrend(int device, int nsub, int nchan, int nbin, co
                          nullptr, ptp_o, fftmax_o, 8, 1024, data_f64, &dt);
 }
 
+int ic_comprehensive_stats_detrend_pieces(int device, int nsub, int nchan, int nbin, const float *data,
+                                          const float *weights, double chanthresh, double subintthresh,
+                                          double *test_out, double *std_o, double *mean_o, double *ptp_o,
+                                          double *fftmax_o, int data_f64, int chan_order, int subint_order, int rounds,
+                                          double clip, double *chan_coef, double *subint_coef, int chan_npieces,
+                                          const int32_t *chan_starts, int subint_npieces, const int32_t *subint_starts)
+{
+    if (data_f64 != 0 && data_f64 != 1) return fail(IC_EINVAL, "data_f64=%d (0 or 1)", data_f64);
+    if (const char *e = detrend_range(chan_order, subint_order, rounds, clip))
+        return fail(IC_EINVAL, "ic_comprehensive_stats_detrend_pieces(%d, %d, %d, %g): %s", chan_order, subint_order,
+                    rounds, clip, e);
+    if (const char *e = pieces_range(chan_npieces, chan_starts, nsub))
+        return fail(IC_EINVAL, "ic_comprehensive_stats_detrend_pieces, channel lines (%d entries): %s", nsub, e);
+    if (const char *e = pieces_range(subint_npieces, subint_starts, nchan))
+        return fail(IC_EINVAL, "ic_comprehensive_stats_detrend_pieces, subint lines (%d entries): %s", nchan, e);
+    PieceSpec ps{{0}, {0}};
+    if (chan_npieces > 0) ps.cs.assign(chan_starts, chan_starts + chan_npieces);
+    if (subint_npieces > 0) ps.ss.assign(subint_starts, subint_starts + subint_npieces);
+    const TrendArgs dt{chan_order, subint_order, rounds, clip, chan_coef, subint_coef};
+    return stats_oneshot(device, nsub, nchan, nbin, data, weights, chanthresh, subintthresh, test_out, std_o, mean_o,
+                         nullptr, ptp_o, fftmax_o, 8, 1024, data_f64, &dt, &ps);
+}
+
 static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float *data, const float *weights,
                          double chanthresh, double subintthresh, double *test_out, double *std_o, double *mean_o,
                          float *ptp_o, double *ptp64_o, double *fftmax_o, int rowstat_waves, int rowstat_minlen,
-                         int data_f64, const TrendArgs *trend)
+                         int data_f64, const TrendArgs *trend, const PieceSpec *pieces)
 {
     if (!data || !weights || !test_out) return fail(IC_EINVAL, "null argument");
     if (rowstat_waves != 0 && rowstat_waves != 4 && rowstat_waves != 8)
@@ -2740,7 +2895,10 @@ static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float 
     float *D, *w0, *W, *hist;
     uint8_t *valid;
     double *sd, *mn, *ff, *pt, *test, *lstat, *coef;
-    int32_t *cnt;
+    int32_t *cnt, *pstarts;
+    int16_t *ppiece;
+    const size_t mc = pieces ? pieces->cs.size() : 1, ms = pieces ? pieces->ss.size() : 1;
+    const PieceTables ptab = pieces ? piece_tables(pieces->cs, pieces->ss, nsub, nchan) : PieceTables();
     double2 *dtw, *dtw2, *ddt;
     PwPlan *dplan;
     struct {
@@ -2751,7 +2909,8 @@ static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float 
               {(void **)&pt, 8 * P},    {(void **)&test, 8 * P}, {(void **)&lstat, 8 * 16 * ((size_t)nsub + nchan)},
               {(void **)&cnt, 4 * 8},   {(void **)&dtw, 16 * (size_t)nbin}, {(void **)&dtw2, 16 * (size_t)nbin + 16},
               {(void **)&dplan, sizeof plan}, {(void **)&ddt, 16 * dt.size()},
-              {(void **)&coef, trend ? 8 * 16 * ((size_t)nsub + nchan) : 0}};
+              {(void **)&coef, trend ? 8 * 16 * ((size_t)nsub * ms + (size_t)nchan * mc) : 0},
+              {(void **)&pstarts, 4 * ptab.starts.size()}, {(void **)&ppiece, 2 * ptab.piece.size()}};
     for (auto &x : al)
         if (sc.mem.alloc_bytes(x.p, x.bytes + 16) != hipSuccess) return fail(IC_ENOMEM, "hipMalloc(%zu) failed", x.bytes);
     CK(hipMemcpyAsync(D, data, 4 * N, hipMemcpyHostToDevice, st));
@@ -2798,14 +2957,25 @@ static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float 
     if (trend) {
         TrendArgs ta = *trend;
         ta.col_coef = coef;
-        ta.row_coef = coef + (size_t)16 * nchan;
-        CK(launch_linetrend(st, la, ta, 3));
-        CK(launch_combine_dt(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med, la.col_mad,
-                             la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt, ta));
+        ta.row_coef = coef + (size_t)16 * nchan * mc;
+        if (pieces) {
+            CK(hipMemcpyAsync(pstarts, ptab.starts.data(), 4 * ptab.starts.size(), hipMemcpyHostToDevice, st));
+            CK(hipMemcpyAsync(ppiece, ptab.piece.data(), 2 * ptab.piece.size(), hipMemcpyHostToDevice, st));
+            const PieceArgs pa = piece_args(pieces->cs, pieces->ss, nsub, pstarts, ppiece);
+            CK(launch_linetrend_pw(st, la, ta, pa, 3));
+            CK(launch_combine_pw(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med,
+                                 la.col_mad, la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt,
+                                 ta, pa));
+        } else {
+            CK(launch_linetrend(st, la, ta, 3));
+            CK(launch_combine_dt(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med,
+                                 la.col_mad, la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt,
+                                 ta));
+        }
         if (trend->col_coef)
-            CK(hipMemcpyAsync(trend->col_coef, ta.col_coef, 8 * 16 * (size_t)nchan, hipMemcpyDeviceToHost, st));
+            CK(hipMemcpyAsync(trend->col_coef, ta.col_coef, 8 * 16 * (size_t)nchan * mc, hipMemcpyDeviceToHost, st));
         if (trend->row_coef)
-            CK(hipMemcpyAsync(trend->row_coef, ta.row_coef, 8 * 16 * (size_t)nsub, hipMemcpyDeviceToHost, st));
+            CK(hipMemcpyAsync(trend->row_coef, ta.row_coef, 8 * 16 * (size_t)nsub * ms, hipMemcpyDeviceToHost, st));
     } else {
         CK(launch_linestats(st, la, 3));
         CK(launch_combine(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, 1, ff, la.col_med, la.col_mad, la.row_med,

@@ -516,8 +516,9 @@ int ic_comprehensive_stats_rowstat(int device, int nsub, int nchan, int nbin, co
  * ic_set_detrend: after create; holds for the ic_runs that follow; (0, 0, ..)
  * switches it off, and a session on which it is off or was never called
  * launches and computes exactly what it always did.  IC_EINVAL for a value out
- * of range and on a channel-shard session.  It is no ic_set_option option:
- * those never change the arithmetic.
+ * of range and on a channel-shard session that has not opted in
+ * (ic_shard_enable_detrend, below).  It is no ic_set_option option: those
+ * never change the arithmetic.
  * ic_get_trends: the last iteration's coefficients a_0..a_3 per line,
  * chan_coef [4][nchan][4] and subint_coef [4][nsub][4] (diagnostics in the
  * order std, mean, ptp, fftmax); either may be NULL.  IC_ESTATE before a
@@ -563,7 +564,9 @@ int ic_comprehensive_stats_detrend(int device, int nsub, int nchan, int nbin, co
  * whole-line kernels.  While detrending is off, pieces change nothing.
  * IC_EINVAL: starts[0] != 0, starts not strictly ascending, a start >= n,
  * npieces outside 0..512, a NULL pointer with npieces > 0, a channel-shard
- * session.  IC_ENOMEM (from the run) when the pieces' buffers cannot be had.
+ * session that has not opted in (ic_shard_enable_detrend; there n of the
+ * subint lines is the archive's nchan, not the shard's).  IC_ENOMEM (from the
+ * run) when the pieces' buffers cannot be had.
  * ic_get_trends_pieces: chan_coef [4][nchan][mc][4], subint_coef
  * [4][nsub][ms][4] (mc, ms: the directions' piece counts); either may be NULL.
  * IC_ESTATE as ic_get_trends, and when no pieces are set.  ic_get_trends
@@ -581,6 +584,35 @@ int ic_comprehensive_stats_detrend_pieces(int device, int nsub, int nchan, int n
                                           int rounds, double clip, double *chan_coef, double *subint_coef,
                                           int chan_npieces, const int32_t *chan_starts, int subint_npieces,
                                           const int32_t *subint_starts);
+
+/* ------------------------------------------------------------------------
+ * Detrended scaling on channel shards (opt-in on top of the two above; the
+ * shard sessions are described below).  A channel line lies whole on its
+ * shard; a subint line is fitted by the row's owner, which already holds the
+ * whole row, and every iteration then all-gathers one slot per rank with the
+ * owned rows' median, MAD and coefficients: rows_pad * (8 + 16 ms) doubles,
+ * rows_pad = ceil(nsub / world), ms = the subint pieces (1 when unpieced).
+ * 1024 subints on 8 ranks with 512 pieces: 8.4 MB per slot, 67 MB gathered on
+ * every rank.  The result equals the unsharded detrended clean bit for bit.
+ *
+ * ic_shard_enable_detrend: on a shard session, ic_set_detrend,
+ * ic_set_detrend_pieces, ic_get_trends and ic_get_trends_pieces are legal from
+ * then on; on an unsharded session IC_OK and nothing else.  EVERY rank of a
+ * group must call it and then set the same orders, rounds, clip and pieces:
+ * ranks that disagree exchange different sizes (the transport fails, or
+ * blocks until its timeout).  The library issues no exchange of its own to
+ * check the agreement, so a shard run without detrending issues exactly the
+ * exchanges it always did.
+ * ic_set_detrend_pieces on such a session: subint_starts are the starts of the
+ * archive's whole subint lines (validated against the archive's nchan, and the
+ * same on every rank); chan_starts against nsub as ever.
+ * ic_get_trends[_pieces] on such a session: chan_coef holds the shard's own
+ * channels, [4][nchan_r][mc][4]; subint_coef all nsub rows, [4][nsub][ms][4],
+ * identical on every rank.
+ * The slots are exchange buffers: with ic_comm_ops the host's alloc / release
+ * are called from the first detrended ic_run after enabling (and after a change
+ * of pieces), not only from the create call. */
+int ic_shard_enable_detrend(void *session);
 
 /* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
@@ -661,7 +693,10 @@ int ic_rccl_set_init_timeout(int64_t ms);
 
 /* In-process shard group: `world` shards driven by `world` host threads of one
  * process (one or several devices), exchanging by device-to-device / peer
- * copies.  Destroy the group after all its sessions. */
+ * copies.  Destroy the group after all its sessions; a session that a host's
+ * error path destroys after its group is still destroyed safely (the group's
+ * memory lives until its last session is gone), but no session may be created
+ * on, or run with, a destroyed group. */
 int ic_group_create(int world, void **group);
 void ic_group_destroy(void *group);
 int ic_session_create_grouped(const ic_params *params, int device, void *group, int rank, void **session);

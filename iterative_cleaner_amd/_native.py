@@ -30,7 +30,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_decode_profiles", "ic_upload_delays_async", "ic_encode_profiles", "ic_get_residual_quantised",
            "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait",
            "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend",
-           "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces")
+           "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces",
+           "ic_shard_enable_detrend")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -187,6 +188,7 @@ def load_library(path: str = LIB_PATH):
                                                    C.c_double, vp, vp]
     lib.ic_set_detrend_pieces.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.ic_get_trends_pieces.argtypes = [vp, vp, vp]
+    lib.ic_shard_enable_detrend.argtypes = [vp]
     lib.ic_comprehensive_stats_detrend_pieces.argtypes = (list(lib.ic_comprehensive_stats_detrend.argtypes)
                                                           + [C.c_int, vp, C.c_int, vp])
     if lib.ic_abi_version() != ABI_VERSION:
@@ -266,15 +268,19 @@ class GpuSession:
         if rc != 0:
             raise NativeError("%s: %s (rc=%d)" % (self._create_name, _err(self.lib), rc))
         self.h = h
-        for name, value in (options or {}).items():
-            self.set_option(name, value)
-        if delay is not None:
-            self._initial_delays(delay)
-        if detrend is not None:
-            self.set_detrend(*detrend)
         self.pieces = None   # (mc, ms) while pieces are set
-        if detrend_pieces is not None:
-            self.set_detrend_pieces(*detrend_pieces)
+        try:
+            for name, value in (options or {}).items():
+                self.set_option(name, value)
+            if delay is not None:
+                self._initial_delays(delay)
+            if detrend is not None:
+                self.set_detrend(*detrend)
+            if detrend_pieces is not None:
+                self.set_detrend_pieces(*detrend_pieces)
+        except Exception:
+            self.close()   # no half-made session is left for the collector (a shard's must go before its group)
+            raise
 
     def set_detrend_pieces(self, chan, subint):
         """Piecewise detrending for the runs that follow (ic_set_detrend_pieces;
@@ -282,8 +288,10 @@ class GpuSession:
         the subints) and of the subint lines (over the channels), each None
         (one piece), a count, "wN" (a piece every N entries) or a sequence of
         starts.  With either given, detrended runs take the piecewise kernels;
-        (None, None) goes back to the whole-line ones.  Not on a channel shard."""
-        nsub, nchan, _ = self.shape
+        (None, None) goes back to the whole-line ones.  On a channel shard only
+        with shard_detrend (ShardSession); the subint pieces are then those of
+        the archive's whole subint lines, the same on every rank."""
+        nsub, nchan, _ = getattr(self, "global_shape", self.shape)
         mc, cb = _piece_starts(chan, nsub)
         ms, sb = _piece_starts(subint, nchan)
         self._check(self.lib.ic_set_detrend_pieces(self.h, mc, _ptr(cb), ms, _ptr(sb)), "ic_set_detrend_pieces")
@@ -292,7 +300,8 @@ class GpuSession:
     def set_detrend(self, chan_order, subint_order, rounds=4, clip=5.0):
         """Detrended scaling for the runs that follow (ic_set_detrend; the
         definition is detrend.py): polynomial orders 0..3 of the channel lines
-        and of the subint lines, (0, 0) = off; not on a channel shard."""
+        and of the subint lines, (0, 0) = off; on a channel shard only with
+        shard_detrend (ShardSession)."""
         self._check(self.lib.ic_set_detrend(self.h, int(chan_order), int(subint_order), int(rounds), float(clip)),
                     "ic_set_detrend")
 
@@ -301,7 +310,8 @@ class GpuSession:
         (4, nchan, 4), subint (4, nsub, 4)) f64, a_0..a_3 per line, diagnostics
         in the order std, mean, ptp, fftmax.  While pieces are set
         (set_detrend_pieces; ic_get_trends_pieces): (4, nchan, mc, 4) and
-        (4, nsub, ms, 4)."""
+        (4, nsub, ms, 4).  On a channel shard (shard_detrend): the shard's own
+        channels and all nsub rows (the rows are the same on every rank)."""
         nsub, nchan, _ = self.shape
         if self.pieces is not None:
             cc = np.empty((4, nchan, self.pieces[0], 4), np.float64)
@@ -862,11 +872,16 @@ class ShardSession(GpuSession):
     Exchanges go through `group` (a ShardGroup: in-process), `comm` (an object
     with ``ops()`` returning a CommOps, e.g. dist.TorchComm: host callbacks) or
     `rccl_id` (rank 0's rccl_unique_id(): the library's own RCCL communicator,
-    every collective issued from C++ on the session stream)."""
+    every collective issued from C++ on the session stream).
+    shard_detrend=True opts in to detrending on shards (ic_shard_enable_detrend)
+    before detrend= / detrend_pieces= are applied; every rank of the group must
+    pass it with the same detrend settings, and detrend_pieces then cut the
+    archive's whole subint lines (global nchan)."""
 
     _create_name = "ic_session_create_shard"
 
-    def __init__(self, nsub, nchan, nbin, rank, world, group=None, comm=None, rccl_id=None, **kw):
+    def __init__(self, nsub, nchan, nbin, rank, world, group=None, comm=None, rccl_id=None, shard_detrend=False,
+                 **kw):
         if sum(x is not None for x in (group, comm, rccl_id)) != 1:
             raise ValueError("ShardSession needs exactly one of group / comm / rccl_id")
         if rccl_id is not None and len(rccl_id) != 128:
@@ -878,11 +893,22 @@ class ShardSession(GpuSession):
         self.row_range = rows[self.rank]
         self.global_shape = (int(nsub), int(nchan), int(nbin))
         self._delay = None
+        detrend, pieces = kw.pop("detrend", None), kw.pop("detrend_pieces", None)
         super().__init__(nsub, nchan, nbin, **kw)
-        c0, c1 = self.chan_range
-        self.shape = (int(nsub), c1 - c0, int(nbin))
-        if self._delay is not None:   # the shard's own channels
-            self.set_delays(self._delay)
+        try:
+            if shard_detrend:
+                self._check(self.lib.ic_shard_enable_detrend(self.h), "ic_shard_enable_detrend")
+            if detrend is not None:
+                self.set_detrend(*detrend)
+            if pieces is not None:
+                self.set_detrend_pieces(*pieces)
+            c0, c1 = self.chan_range
+            self.shape = (int(nsub), c1 - c0, int(nbin))
+            if self._delay is not None:   # the shard's own channels
+                self.set_delays(self._delay)
+        except Exception:
+            self.close()
+            raise
 
     def _initial_delays(self, delay):
         self._delay = delay

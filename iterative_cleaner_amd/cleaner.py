@@ -208,7 +208,7 @@ def _device() -> int:
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
              data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
-             detrend=None, detrend_pieces=None):
+             detrend=None, detrend_pieces=None, detrend_shards=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -226,24 +226,33 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     ``residual`` is returned as ever).  ``detrend`` = (chan_order,
     subint_order[, rounds, clip]): the opt-in detrended scaling (detrend.py);
     None reads the switch IC_DETREND="chan,subint[,rounds,clip]" (unset, empty
-    or 0: off).  Not under channel sharding (ValueError).  ``detrend_pieces`` =
+    or 0: off).  Under channel sharding only with the opt-in ``detrend_shards``
+    =True (None reads the switch IC_DETREND_SHARDS=1; every rank must agree,
+    which the environment torchrun hands on sees to), else ValueError; the
+    pieces then cut the archive's whole lines.  ``detrend_pieces`` =
     (chan, subint): piecewise detrending (detrend.py), each side None, a piece
     count, "wN" (a piece every N entries) or the pieces' starts; None reads the
     switch IC_DETREND_PIECES="<chan>;<subint>".  Without a detrend order in a
     direction its pieces are ignored."""
-    from .detrend import normalise, normalise_pieces
+    from .detrend import normalise, normalise_pieces, shards_enabled
     from .dist import channel_sharding
     detrend = normalise(detrend)
-    if detrend is not None and channel_sharding():
-        raise ValueError("detrended scaling (detrend / IC_DETREND) is not available under channel sharding")
+    if detrend_shards is None:
+        detrend_shards = shards_enabled()
+    if detrend is not None and not detrend_shards and channel_sharding():
+        raise ValueError("detrended scaling (detrend / IC_DETREND) is not available under channel sharding "
+                         "(unless opted in on every rank: IC_DETREND_SHARDS=1 or detrend_shards=True)")
     if quantised is not None:
         if cube is not None or channel_sharding():
             raise ValueError("quantised input takes no f32 cube and no channel sharding")
         cube = quantised[0]
     pols = cube.ndim == 4
     nsub, nchan, nbin = (cube.shape[0], cube.shape[2], cube.shape[3]) if pols else cube.shape
-    detrend_pieces = normalise_pieces(detrend_pieces, nsub, nchan, detrend)
-    if channel_sharding():
+    sharding = channel_sharding()
+    # a shard's pieces are those of the archive's whole lines, the same on every rank
+    detrend_pieces = normalise_pieces(detrend_pieces, nsub, nchan_total if sharding and nchan_total else nchan,
+                                      detrend)
+    if sharding:
         import torch
 
         from . import sharded
@@ -262,7 +271,8 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
             dev, want_residual=want_residual,
             max_iter=args.max_iter, chanthresh=args.chanthresh, subintthresh=args.subintthresh,
             pulse_region=args.pulse_region, baseline_duty=baseline_duty, data_f64=data_f64, delay=delay,
-            input_dedispersed=input_dedispersed)
+            input_dedispersed=input_dedispersed,
+            **(dict(detrend=detrend, detrend_pieces=detrend_pieces, shard_detrend=True) if detrend is not None else {}))
     if nchan_total is not None and nchan_total != nchan:
         raise ValueError("a channel slice of an archive needs channel sharding")
     with _native.GpuSession(nsub, nchan, nbin, args.max_iter, args.chanthresh, args.subintthresh,
@@ -331,10 +341,10 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch, detrend=None, detrend_pieces=None):
+def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None):
     """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend,
-    detrend_pieces: run_loop's (None = the IC_DETREND / IC_DETREND_PIECES
-    switches; there is no CLI flag).  Under
+    detrend_pieces, detrend_shards: run_loop's (None = the IC_DETREND /
+    IC_DETREND_PIECES / IC_DETREND_SHARDS switches; there is no CLI flag).  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -382,7 +392,8 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None):
     out = run_loop(cube, orig_weights, shift, args, want_residual=args.unload_res, baseline_duty=duty,
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
-                   residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces)
+                   residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces,
+                   detrend_shards=detrend_shards)
     del cube
 
     x = 0

@@ -4,8 +4,14 @@
 // cleaning iteration (DESIGN.md "Channel-sharded large archive"): per-subint
 // channel-sum roots (all-gather), diagnostics rows to their row owners
 // (all-to-all), row medians/MADs (all-gather) and convergence counters
-// (all-reduce).  Every exchange is issued in stream order on the session's
-// stream; no host synchronisation is implied.
+// (all-reduce).  With detrending enabled on the shards (ic_shard_enable_detrend)
+// and on, the row all-gather carries each owner's slot of medians, MADs and
+// trend coefficients instead (rows_pad * (8 + 16 ms) doubles per rank, ms the
+// subint pieces): the same number and order of exchanges, one of them larger;
+// its buffers are the only ones allocated after the session's creation (alloc
+// from the first detrended run, release when the pieces change).  Every
+// exchange is issued in stream order on the session's stream; no host
+// synchronisation is implied.
 //
 // Transports:
 //   RcclComm     — native RCCL over xGMI (one process per GPU): a

@@ -63,6 +63,10 @@ struct LocalGroup {
         bool taken = false;
     };
     int world = 0;
+    // owners: the host's handle (until local_group_destroy) and every LocalComm
+    // made on the group.  A session that outlives the host's handle (a host
+    // error path that destroys the group first) still finds its group.
+    int refs = 1;
     std::mutex mu;
     std::condition_variable cv;
     int arrived = 0;
@@ -104,7 +108,21 @@ LocalGroup *local_group_create(int world)
     return g;
 }
 
-void local_group_destroy(LocalGroup *g) { delete g; }
+// drop one owner; the last one frees the group
+static void local_group_unref(LocalGroup *g)
+{
+    bool last;
+    {
+        std::lock_guard<std::mutex> lk(g->mu);
+        last = --g->refs == 0;
+    }
+    if (last) delete g;
+}
+
+void local_group_destroy(LocalGroup *g)
+{
+    if (g) local_group_unref(g);
+}
 
 int local_group_world(const LocalGroup *g) { return g ? g->world : 0; }
 
@@ -121,8 +139,11 @@ public:
         if (me.ready) (void)hipEventDestroy(me.ready);
         if (me.done) (void)hipEventDestroy(me.done);
         if (tmp) (void)hipFree(tmp);
-        std::lock_guard<std::mutex> lk(g->mu);
-        me = LocalGroup::Slot();
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            me = LocalGroup::Slot();
+        }
+        local_group_unref(g);
     }
     int init()
     {
@@ -241,6 +262,7 @@ Comm *make_local_comm(LocalGroup *g, int rank, int device, const char **err)
             return nullptr;
         }
         g->slot[rank].taken = true;
+        ++g->refs;   // this LocalComm's, dropped by its destructor
     }
     auto *c = new LocalComm(g, rank, device);
     if (c->init()) {

@@ -250,6 +250,11 @@ hipError_t launch_assemble_rows(hipStream_t st, const ShardGeom &g, const unsign
 // gathered [world][8 * rows_pad] (rank p: med [4][rows_p], mad [4][rows_p]) -> row_med/row_mad [4][nsub]
 hipError_t launch_unpack_rowstats(hipStream_t st, const ShardGeom &g, int rows_pad, const double *recv,
                                   double *row_med, double *row_mad);
+// gathered detrended row statistics [world][rows_pad * (8 + 16 ms)] (rank p: med
+// [4][rows_p], mad [4][rows_p], coefficients [4][rows_p][ms][4]) -> row_med / row_mad
+// [4][nsub], row_coef [4][nsub][ms][4]
+hipError_t launch_unpack_rowtrends(hipStream_t st, const ShardGeom &g, int rows_pad, int ms, const double *recv,
+                                   double *row_med, double *row_mad, double *row_coef, int grid_cap = 0);
 // buf[i] = sum_r gathered[r][i]
 hipError_t launch_sum_i32(hipStream_t st, const int32_t *gathered, int world, int n, int32_t *buf);
 // T2 (optional): [2 nbin] receives T64[0..nbin) twice
@@ -489,6 +494,21 @@ hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t 
                              const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
                              double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
                              const PieceArgs &pc, int grid_cap = 0);
+// the two combines on a channel shard (k_combine_dt_sh, k_combine_pw_sh): nchan
+// is the shard's, its channels chan0 .. chan0 + nchan of nchan_g; t.row_coef (and
+// pc's row tables) are whole subint lines', t.col_coef the shard's channels'
+hipError_t launch_combine_dt_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                                int chan0, int nchan_g, int grid_cap = 0);
+hipError_t launch_combine_pw_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                                const PieceArgs &pc, int chan0, int nchan_g, int grid_cap = 0);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
 // bins, n even (<= 8192; 1/n and 4/n are rounded factors unless n is a power
 // of two): the phase rotation's multiplier

@@ -959,19 +959,38 @@ constexpr double kNearTie = 1e-9;
 // gridDim.x, read in the kernel
 // TR = PieceView: the piecewise form (k_combine_pw): as TrendView, the d' of an
 // entry formed with its piece's coefficients on the piece's abscissa
+// TR = ShardTrendView / ShardPieceView: the two on a channel shard
+// (k_combine_dt_sh, k_combine_pw_sh; ic_shard_enable_detrend): the shard's nchan
+// channels are chan0 .. chan0 + nchan of a subint line of nchan_g, so the subint
+// direction's d' of local entry (s, c) is formed at chan0 + c of nchan_g (in
+// pieces: looked up there in the full-length table) with the row's gathered
+// coefficients; the channel direction is the unsharded one
 struct NoTrend {
-    static constexpr bool on = false, pieces = false;
+    static constexpr bool on = false, pieces = false, shard = false;
 };
 struct TrendView {
-    static constexpr bool on = true, pieces = false;
+    static constexpr bool on = true, pieces = false, shard = false;
     const TrendCoef *col_coef, *row_coef;   // [4][nchan], [4][nsub]
     int chan_order, subint_order;
 };
 struct PieceView {
-    static constexpr bool on = true, pieces = true;
+    static constexpr bool on = true, pieces = true, shard = false;
     const TrendCoef *col_coef, *row_coef;   // [4][nchan][col_np], [4][nsub][row_np]
     int chan_order, subint_order;
     PieceArgs pa;
+};
+struct ShardTrendView {
+    static constexpr bool on = true, pieces = false, shard = true;
+    const TrendCoef *col_coef, *row_coef;   // [4][nchan] (the shard's), [4][nsub]
+    int chan_order, subint_order;
+    int chan0, nchan_g;
+};
+struct ShardPieceView {
+    static constexpr bool on = true, pieces = true, shard = true;
+    const TrendCoef *col_coef, *row_coef;   // [4][nchan][col_np] (the shard's), [4][nsub][row_np]
+    int chan_order, subint_order;
+    PieceArgs pa;                           // row_starts / row_piece: over nchan_g
+    int chan0, nchan_g;
 };
 template <class TR>
 __device__ __forceinline__ void combine_body(
@@ -1000,11 +1019,17 @@ __device__ __forceinline__ void combine_body(
             // in its subint line (entry c of nchan)
             const double dv[4] = {std_d[k], mean_d[k], ptp_d[k], fft_d[k]};
             double dc[4], ds[4];
+            // the entry's place in its subint line, and the line's length
+            int cg = c, ng = nchan;
+            if constexpr (TR::shard) {
+                cg = tr.chan0 + c;
+                ng = tr.nchan_g;
+            }
             if constexpr (TR::pieces) {
                 // the same, on the abscissa and with the coefficients of the
                 // entry's piece of either line
                 const PieceAt ac = piece_at(s, tr.pa.col_piece, tr.pa.col_starts);
-                const PieceAt as = piece_at(c, tr.pa.row_piece, tr.pa.row_starts);
+                const PieceAt as = piece_at(cg, tr.pa.row_piece, tr.pa.row_starts);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const bool f32 = q == 2 && ptp_f32;
@@ -1021,7 +1046,7 @@ __device__ __forceinline__ void combine_body(
                     const bool in = q == 3 || v;
                     dc[q] = in ? detrend_value(dv[q], f32, s, nsub, tr.col_coef[(size_t)q * nchan + c], tr.chan_order)
                                : dv[q];
-                    ds[q] = in ? detrend_value(dv[q], f32, c, nchan, tr.row_coef[(size_t)q * nsub + s], tr.subint_order)
+                    ds[q] = in ? detrend_value(dv[q], f32, cg, ng, tr.row_coef[(size_t)q * nsub + s], tr.subint_order)
                                : dv[q];
                 }
             }
@@ -1161,6 +1186,37 @@ __global__ __launch_bounds__(256) void k_combine_pw(
                            pa});
 }
 
+// the two on a channel shard: the subint direction at chan0 + c of nchan_g
+__global__ __launch_bounds__(256) void k_combine_dt_sh(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters, TrendArgs t, int chan0, int nchan_g)
+{
+    combine_body(nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad,
+                 cth, sth, test, W, hist, iter, counters, blockDim.x, gridDim.x,
+                 ShardTrendView{(const TrendCoef *)t.col_coef, (const TrendCoef *)t.row_coef, t.chan_order,
+                                t.subint_order, chan0, nchan_g});
+}
+
+__global__ __launch_bounds__(256) void k_combine_pw_sh(
+    int nsub, int nchan, const uint8_t *__restrict__ valid, const int32_t *__restrict__ info,
+    const float *__restrict__ w0,
+    const double *__restrict__ std_d, const double *__restrict__ mean_d, const double *__restrict__ ptp_d, int ptp_f32,
+    const double *__restrict__ fft_d, const double *__restrict__ col_med, const double *__restrict__ col_mad,
+    const double *__restrict__ row_med, const double *__restrict__ row_mad, double cth, double sth,
+    double *__restrict__ test, float *__restrict__ W, float *__restrict__ hist, int iter,
+    int32_t *__restrict__ counters, TrendArgs t, PieceArgs pa, int chan0, int nchan_g)
+{
+    combine_body(nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad,
+                 cth, sth, test, W, hist, iter, counters, blockDim.x, gridDim.x,
+                 ShardPieceView{(const TrendCoef *)t.col_coef, (const TrendCoef *)t.row_coef, t.chan_order,
+                                t.subint_order, pa, chan0, nchan_g});
+}
+
 // ============================================================ launchers
 
 hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
@@ -1293,6 +1349,38 @@ hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t 
     const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
     IC_GGL(k_combine_pw, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
            fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t, pa);
+    return hipGetLastError();
+}
+
+hipError_t launch_combine_pw_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                                const PieceArgs &pa, int chan0, int nchan_g, int grid_cap)
+{
+    if (chan0 < 0 || nchan < 0 || chan0 + nchan > nchan_g) return hipErrorInvalidValue;
+    const size_t P = (size_t)nsub * nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
+    IC_GGL(k_combine_pw_sh, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
+           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t, pa,
+           chan0, nchan_g);
+    return hipGetLastError();
+}
+
+hipError_t launch_combine_dt_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
+                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
+                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
+                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
+                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
+                                int chan0, int nchan_g, int grid_cap)
+{
+    if (chan0 < 0 || nchan < 0 || chan0 + nchan > nchan_g) return hipErrorInvalidValue;
+    const size_t P = (size_t)nsub * nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
+    IC_GGL(k_combine_dt_sh, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
+           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t,
+           chan0, nchan_g);
     return hipGetLastError();
 }
 

@@ -257,6 +257,17 @@ struct Session {
     int32_t *pw_starts = nullptr;
     int16_t *pw_piece = nullptr;
     double *pw_trend = nullptr;
+    // detrending on a channel shard (ic_shard_enable_detrend): sh_dt makes the
+    // setters legal; there the subint pieces (pw_ss, the row half of pw_starts /
+    // pw_piece) are those of the archive's whole subint lines (p.nchan entries),
+    // the channel coefficients the shard's channels', the subint coefficients all
+    // nsub rows'.  xt_send / xt_recv: the owner's slot of detrended row statistics
+    // (rows_pad * (8 + 16 ms) doubles: med, MAD, coefficients) and the world
+    // slots gathered; the transport's, from the first detrended run after
+    // enabling or after a piece change (xt_ms: the ms they were sized for)
+    bool sh_dt = false;
+    double *xt_send = nullptr, *xt_recv = nullptr;
+    size_t xt_ms = 0;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -669,7 +680,8 @@ void free_all(Session *s)
     s->mem.free_all();
     if (s->comm) {   // the transport's buffers
         void *xbufs[] = {s->xw_send, s->xw_recv, s->xf_send, s->xf_recv, s->xwg_send, s->xwg_recv, s->xfg_send,
-                         s->xfg_recv, s->xd_send, s->xd_recv, s->xr_send, s->xr_recv, s->counters};
+                         s->xfg_recv, s->xd_send, s->xd_recv, s->xr_send, s->xr_recv, s->xt_send, s->xt_recv,
+                         s->counters};
         for (void *b : xbufs)
             if (b) s->comm->release(b);
         s->counters = nullptr;
@@ -1000,7 +1012,8 @@ int iteration_template(Session *s, int iter)
 // Row medians/MADs of a shard: the diagnostics rows go to their owners
 // (all-to-all), each owner runs the row selections over whole rows, and the
 // results are all-gathered into row_med/row_mad [4][nsub].
-int shard_rowstats(Session *s, const LineStatsArgs &la)
+// its first half, shared with shard_rowtrends: the rows to their owners
+int shard_rows_to_owners(Session *s)
 {
     LAUNCH(s, K_SHARD_PACK,
            launch_pack_rows(s->stream, s->geom, s->nchan, s->std_, s->mean, s->fft, s->ptp, nullptr, s->xd_send,
@@ -1009,6 +1022,11 @@ int shard_rowstats(Session *s, const LineStatsArgs &la)
     LAUNCH(s, K_SHARD_PACK,
            launch_assemble_rows(s->stream, s->geom, s->xd_recv, s->std_r, s->mean_r, s->fft_r, s->ptp_r, nullptr,
                                 s->grid_cap));
+    return 0;
+}
+// the owner's whole rows as lines; med / MAD [4][rows_own] go to `slot`
+LineStatsArgs owned_rows_args(Session *s, const LineStatsArgs &la, double *slot)
+{
     LineStatsArgs lr;
     lr.nsub = s->rows_own;
     lr.nchan = s->geom.nchan_g;
@@ -1021,11 +1039,47 @@ int shard_rowstats(Session *s, const LineStatsArgs &la)
     lr.grp_waves = la.grp_waves;
     lr.grp_minlen = la.grp_minlen;
     lr.col_med = lr.col_mad = nullptr;
-    lr.row_med = s->xr_send;
-    lr.row_mad = s->xr_send + 4 * s->rows_own;
+    lr.row_med = slot;
+    lr.row_mad = slot + 4 * s->rows_own;
+    return lr;
+}
+int shard_rowstats(Session *s, const LineStatsArgs &la)
+{
+    if (int rc = shard_rows_to_owners(s)) return rc;
+    const LineStatsArgs lr = owned_rows_args(s, la, s->xr_send);
     LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, lr, 2));
     CM(s, s->comm->allgather(s->xr_send, s->xr_recv, sizeof(double) * 8 * s->rows_pad, s->stream), "row statistics");
     LAUNCH(s, K_SHARD_PACK, launch_unpack_rowstats(s->stream, s->geom, s->rows_pad, s->xr_recv, la.row_med, la.row_mad));
+    return 0;
+}
+
+// The detrended sibling (ic_shard_enable_detrend): the same rows to the same
+// owners; each owner fits its whole rows (length nchan_g, as one GPU would) and
+// writes med, MAD and coefficients straight into its slot of xt_send (med
+// [4][rows_own], mad [4][rows_own], TrendCoef [4][rows_own][ms]; ms = 1 when
+// unpieced); one all-gather of the slots, scattered by row owner into la.row_med /
+// la.row_mad [4][nsub] and ta.row_coef [4][nsub][ms][4].  pa == nullptr: whole
+// lines.  A rank that owns no rows launches no fit and still joins the collective.
+int shard_rowtrends(Session *s, const LineStatsArgs &la, const TrendArgs &ta, const PieceArgs *pa)
+{
+    if (int rc = shard_rows_to_owners(s)) return rc;
+    const size_t ms = pa ? (size_t)pa->row_np : 1;
+    const size_t slot = (size_t)s->rows_pad * (8 + 16 * ms);
+    if (!s->xt_send || !s->xt_recv || s->xt_ms != ms) return fail(IC_ESTATE, "no exchange buffers for the row trends");
+    if (s->rows_own > 0) {
+        const LineStatsArgs lr = owned_rows_args(s, la, s->xt_send);
+        TrendArgs tr = ta;
+        tr.col_coef = nullptr;
+        tr.row_coef = s->xt_send + 8 * (size_t)s->rows_own;
+        if (pa)
+            LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, lr, tr, *pa, 2));
+        else
+            LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, lr, tr, 2));
+    }
+    CM(s, s->comm->allgather(s->xt_send, s->xt_recv, sizeof(double) * slot, s->stream), "row trends");
+    LAUNCH(s, K_SHARD_PACK,
+           launch_unpack_rowtrends(s->stream, s->geom, s->rows_pad, (int)ms, s->xt_recv, la.row_med, la.row_mad,
+                                   ta.row_coef, s->grid_cap));
     return 0;
 }
 
@@ -2055,7 +2109,8 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     if (pieces) {
         const size_t mc = s->pw_cs.size(), ms = s->pw_ss.size();
         if (!s->pw_trend) {   // allocated last: set once all three are there
-            const PieceTables pt = piece_tables(s->pw_cs, s->pw_ss, nsub, nchan);
+            // (a shard's subint pieces: those of the whole subint line, on every rank)
+            const PieceTables pt = piece_tables(s->pw_cs, s->pw_ss, nsub, p.nchan);
             if (s->mem.ensure(&s->pw_starts, pt.starts.size()) != hipSuccess ||
                 s->mem.ensure(&s->pw_piece, pt.piece.size()) != hipSuccess ||
                 s->mem.ensure(&s->pw_trend, 16 * ((size_t)nchan * mc + (size_t)nsub * ms)) != hipSuccess)
@@ -2070,6 +2125,25 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
         pa = piece_args(s->pw_cs, s->pw_ss, nsub, s->pw_starts, s->pw_piece);
         ta.col_coef = s->pw_trend;
         ta.row_coef = s->pw_trend + 16 * (size_t)nchan * mc;
+    }
+    // a shard's slots of detrended row statistics (shard_rowtrends): the
+    // transport's, sized for this run's subint pieces
+    if (detrend && s->comm) {
+        if (!s->sh_dt) return fail(IC_ESTATE, "detrending on a channel shard without ic_shard_enable_detrend");
+        const size_t ms = pieces ? s->pw_ss.size() : 1;
+        if (s->xt_ms != ms) {
+            s->comm->release(s->xt_send);
+            s->comm->release(s->xt_recv);
+            s->xt_send = s->xt_recv = nullptr;
+            s->xt_ms = 0;
+        }
+        if (!s->xt_send) {
+            const size_t slot = sizeof(double) * (size_t)s->rows_pad * (8 + 16 * ms);
+            if (s->comm->alloc((void **)&s->xt_send, slot + 16) != 0 || !s->xt_send ||
+                s->comm->alloc((void **)&s->xt_recv, slot * s->world + 16) != 0 || !s->xt_recv)
+                return fail(IC_ENOMEM, "exchange buffer (row trends, %zu bytes gathered) failed", slot * s->world);
+            s->xt_ms = ms;
+        }
     }
     int32_t *cnt = s->h_small;   // [max_iter + 5] counters, then the run stats (pinned)
     s->bad_fits.clear();
@@ -2151,9 +2225,17 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
             LAUNCH(s, K_DIAG, launch_diag(s->stream, da));
         }
         // channel medians are local to a shard; row medians need whole rows
-        if (pieces) {
+        if (detrend && s->comm) {
+            // (ic_shard_enable_detrend) a channel line is whole on its shard; the
+            // subint lines are fitted by their row owners
+            if (pieces)
+                LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, la, ta, pa, 1));
+            else
+                LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 1));
+            if (int rc = shard_rowtrends(s, la, ta, pieces ? &pa : nullptr)) return rc;
+        } else if (pieces) {
             LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, la, ta, pa, 3));
-        } else if (detrend) {   // never a shard (ic_set_detrend refuses those)
+        } else if (detrend) {
             LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 3));
         } else {
             LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, la, s->comm ? 1 : 3));
@@ -2161,7 +2243,20 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
                 if (int rc = shard_rowstats(s, la)) return rc;
         }
         CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + 5), s->stream));
-        if (pieces) {
+        if (detrend && s->comm) {
+            if (pieces)
+                LAUNCH(s, K_COMBINE,
+                       launch_combine_pw_sh(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
+                                            la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad,
+                                            p.chanthresh, p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters,
+                                            ta, pa, s->c0, p.nchan, s->grid_cap));
+            else
+                LAUNCH(s, K_COMBINE,
+                       launch_combine_dt_sh(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
+                                            la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad,
+                                            p.chanthresh, p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters,
+                                            ta, s->c0, p.nchan, s->grid_cap));
+        } else if (pieces) {
             LAUNCH(s, K_COMBINE,
                    launch_combine_pw(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
                                      la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
@@ -2676,8 +2771,9 @@ int ic_set_detrend(void *session, int chan_order, int subint_order, int rounds, 
     if (s->failed) return failed_session();
     if (const char *e = detrend_range(chan_order, subint_order, rounds, clip))
         return fail(IC_EINVAL, "ic_set_detrend(%d, %d, %d, %g): %s", chan_order, subint_order, rounds, clip, e);
-    if (s->comm || s->world > 1)
-        return fail(IC_EINVAL, "ic_set_detrend on a channel shard: detrended rows across shards are not supported");
+    if ((s->comm || s->world > 1) && !s->sh_dt)
+        return fail(IC_EINVAL, "ic_set_detrend on a channel shard: detrended rows across shards are not supported "
+                               "(unless every rank opts in first: ic_shard_enable_detrend)");
     s->dt_chan = chan_order;
     s->dt_sub = subint_order;
     s->dt_rounds = rounds;
@@ -2711,12 +2807,14 @@ int ic_set_detrend_pieces(void *session, int chan_npieces, const int32_t *chan_s
     Session *s = (Session *)session;
     if (!s) return fail(IC_EINVAL, "null session");
     if (s->failed) return failed_session();
-    if (s->comm || s->world > 1)
-        return fail(IC_EINVAL, "ic_set_detrend_pieces on a channel shard: detrended rows across shards are not supported");
+    if ((s->comm || s->world > 1) && !s->sh_dt)
+        return fail(IC_EINVAL, "ic_set_detrend_pieces on a channel shard: detrended rows across shards are not supported "
+                               "(unless every rank opts in first: ic_shard_enable_detrend)");
     if (const char *e = pieces_range(chan_npieces, chan_starts, s->p.nsub))
         return fail(IC_EINVAL, "ic_set_detrend_pieces, channel lines (%d entries): %s", s->p.nsub, e);
-    if (const char *e = pieces_range(subint_npieces, subint_starts, s->nchan))
-        return fail(IC_EINVAL, "ic_set_detrend_pieces, subint lines (%d entries): %s", s->nchan, e);
+    // a subint line is the archive's (p.nchan == nchan unless this is a shard)
+    if (const char *e = pieces_range(subint_npieces, subint_starts, s->p.nchan))
+        return fail(IC_EINVAL, "ic_set_detrend_pieces, subint lines (%d entries): %s", s->p.nchan, e);
     s->pw_on = chan_npieces > 0 || subint_npieces > 0;
     s->pw_cs.assign(1, 0);
     s->pw_ss.assign(1, 0);
@@ -2727,7 +2825,22 @@ int ic_set_detrend_pieces(void *session, int chan_npieces, const int32_t *chan_s
     s->mem.release(s->pw_starts);
     s->mem.release(s->pw_piece);
     s->mem.release(s->pw_trend);
+    if (s->comm) {   // a shard's slots were sized for the pieces before
+        s->comm->release(s->xt_send);
+        s->comm->release(s->xt_recv);
+        s->xt_send = s->xt_recv = nullptr;
+        s->xt_ms = 0;
+    }
     s->trends_ran = false;
+    return IC_OK;
+}
+
+int ic_shard_enable_detrend(void *session)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (s->comm || s->world > 1) s->sh_dt = true;
     return IC_OK;
 }
 

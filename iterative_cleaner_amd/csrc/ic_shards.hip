@@ -101,6 +101,39 @@ __global__ __launch_bounds__(256) void k_unpack_rowstats(ShardGeom g, int rows_p
     row_mad[k] = slot[4 * rows_p + q * rows_p + r];
 }
 
+// gathered detrended row statistics (ic_shard_enable_detrend): rank p's slot
+// (rows_pad * (8 + 16 ms) doubles) holds med [4][rows_p], mad [4][rows_p], then
+// the coefficients [4][rows_p][ms][4] of its rows_p owned rows.  One entry per
+// (diagnostic, subint, piece): its four coefficients, and the piece 0 entry its
+// row's median and MAD
+__global__ __launch_bounds__(256) void k_unpack_rowtrends(ShardGeom g, int rows_pad, int ms,
+                                                          const double *__restrict__ recv,
+                                                          double *__restrict__ row_med, double *__restrict__ row_mad,
+                                                          double *__restrict__ row_coef)
+{
+    const size_t n = (size_t)4 * g.nsub * ms;
+    const size_t slot_n = (size_t)rows_pad * (8 + 16 * (size_t)ms);
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(k % ms);
+        const int qs = (int)(k / ms);   // q * nsub + s
+        const int q = qs / g.nsub, s = qs % g.nsub;
+        const int p = geom_row_owner(g, s);
+        const int rows_p = g.row0[p + 1] - g.row0[p];
+        const int r = s - g.row0[p];
+        const double *slot = recv + (size_t)p * slot_n;
+        const double *src = slot + 8 * (size_t)rows_p + (((size_t)q * rows_p + r) * ms + m) * 4;
+        double *dst = row_coef + k * 4;
+        dst[0] = src[0];
+        dst[1] = src[1];
+        dst[2] = src[2];
+        dst[3] = src[3];
+        if (m == 0) {
+            row_med[qs] = slot[q * rows_p + r];
+            row_mad[qs] = slot[4 * rows_p + q * rows_p + r];
+        }
+    }
+}
+
 // Window positions gathered from the row owners (blocks of `blk` ints per
 // rank) -> win[nsub] on every rank; flags (optional): moved per subint and the
 // moves counter flags[nsub], as k_window does unsharded.
@@ -188,6 +221,17 @@ hipError_t launch_unpack_rowstats(hipStream_t st, const ShardGeom &g, int rows_p
 {
     IC_GGL(k_unpack_rowstats, dim3(cdiv(4 * (size_t)g.nsub, 256)), dim3(256), 0, st, g, rows_pad, recv,
                        row_med, row_mad);
+    return hipGetLastError();
+}
+
+hipError_t launch_unpack_rowtrends(hipStream_t st, const ShardGeom &g, int rows_pad, int ms, const double *recv,
+                                   double *row_med, double *row_mad, double *row_coef, int grid_cap)
+{
+    if (ms < 1 || ms > kMaxPieces) return hipErrorInvalidValue;
+    const size_t n = (size_t)4 * g.nsub * ms;
+    if (n == 0) return hipSuccess;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(n, 256), 4096), grid_cap);
+    IC_GGL(k_unpack_rowtrends, dim3(grid), dim3(256), 0, st, g, rows_pad, ms, recv, row_med, row_mad, row_coef);
     return hipGetLastError();
 }
 

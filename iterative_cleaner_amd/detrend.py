@@ -177,6 +177,14 @@ def env_detrend():
     return parse_detrend(os.environ.get("IC_DETREND", ""))
 
 
+def shards_enabled() -> bool:
+    """The opt-in switch of detrending under channel sharding: the environment
+    variable IC_DETREND_SHARDS (unset, empty or ``0`` = off), read at every call.
+    torchrun hands the environment to every rank, which is how the ranks of a
+    group agree (ic_shard_enable_detrend must be called on all of them)."""
+    return os.environ.get("IC_DETREND_SHARDS", "") not in ("", "0")
+
+
 def normalise(detrend):
     """A detrend argument (None = the IC_DETREND switch; a tuple (chan, subint[,
     rounds, clip])) -> None (off) or the validated four."""

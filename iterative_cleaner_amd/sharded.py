@@ -26,34 +26,73 @@ def _gather_cols(parts, ranges, shape, dtype):
     return out
 
 
-def _loop_kwargs(args):
-    return dict(max_iter=args.get("max_iter", 5), chanthresh=args.get("chanthresh", 5.0),
-                subintthresh=args.get("subintthresh", 5.0),
-                pulse_region=args.get("pulse_region", (0, 0, 1)),
-                baseline_duty=args.get("baseline_duty", 0.15), fit_mode=args.get("fit_mode", 0),
-                data_f64=args.get("data_f64", False), options=args.get("options"),
-                input_dedispersed=args.get("input_dedispersed", False), any_length=args.get("any_length"))
+# the keywords of **args: the session's (_loop_kwargs), and `delay`, which the
+# callers slice per rank themselves
+_LOOP_KEYS = ("max_iter", "chanthresh", "subintthresh", "pulse_region", "baseline_duty", "fit_mode", "data_f64",
+              "options", "input_dedispersed", "any_length", "detrend", "detrend_pieces", "shard_detrend")
+
+
+def _loop_kwargs(args, global_shape=None):
+    """The ShardSession keywords of a clean_cube_* call's **args.  An unknown
+    keyword is an error, not dropped.  detrend (detrend.normalise's forms) needs
+    shard_detrend=True, the opt-in every rank must give (ic_shard_enable_detrend);
+    detrend_pieces are resolved once against the global (nsub, nchan), so every
+    rank gets the same starts."""
+    unknown = sorted(set(args) - set(_LOOP_KEYS) - {"delay"})
+    if unknown:
+        raise TypeError("unknown keyword(s) for a sharded clean: %s" % ", ".join(unknown))
+    kw = dict(max_iter=args.get("max_iter", 5), chanthresh=args.get("chanthresh", 5.0),
+              subintthresh=args.get("subintthresh", 5.0),
+              pulse_region=args.get("pulse_region", (0, 0, 1)),
+              baseline_duty=args.get("baseline_duty", 0.15), fit_mode=args.get("fit_mode", 0),
+              data_f64=args.get("data_f64", False), options=args.get("options"),
+              input_dedispersed=args.get("input_dedispersed", False), any_length=args.get("any_length"))
+    shard_detrend = bool(args.get("shard_detrend", False))
+    detrend, pieces = args.get("detrend"), args.get("detrend_pieces")
+    if detrend is not None and not shard_detrend:
+        raise ValueError("detrend on channel shards needs the opt-in shard_detrend=True on every rank "
+                         "(ic_shard_enable_detrend)")
+    if pieces is not None and detrend is None:
+        raise ValueError("detrend_pieces needs detrend")
+    if shard_detrend:
+        kw["shard_detrend"] = True
+    if detrend is not None:
+        from .detrend import check_params, normalise_pieces
+        detrend = check_params(*detrend)
+        kw["detrend"] = detrend
+        if pieces is not None:
+            if global_shape is None:
+                raise ValueError("detrend_pieces need the archive's global shape")
+            pieces = normalise_pieces(pieces, global_shape[0], global_shape[1], detrend)
+            if pieces is not None:
+                kw["detrend_pieces"] = tuple(None if b is None else tuple(int(v) for v in b) for b in pieces)
+    return kw
 
 
 def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, fit_tail=None, **args):
     """Clean a (nsub, nchan, nbin) f32 cube as `world` in-process channel shards.
     Returns the ic_run dict with full-archive ``test`` / ``weights`` (and, with
-    want_details, ``amp``, ``info``, ``std``, ``mean``, ``ptp``, ``fft``, ``T``)."""
+    want_details, ``amp``, ``info``, ``std``, ``mean``, ``ptp``, ``fft``, ``T``).
+    ``detrend`` / ``detrend_pieces`` (GpuSession's) with ``shard_detrend=True``:
+    the detrended scaling on shards; want_details then adds ``trend_chan``
+    (every shard's channel coefficients, joined along the channels) and
+    ``trend_subint`` (all rows', checked equal across the shards)."""
     nsub, nchan, nbin = cube.shape
     devices = list(devices) if devices is not None else [0] * world
     if len(devices) != world:
         raise ValueError("need one device per shard")
     chans, _ = _native.shard_layout(nsub, nchan, world)
-    kw = _loop_kwargs(args)
+    kw = _loop_kwargs(args, (nsub, nchan))
     delay = args.get("delay")
     results = [None] * world
     errors = []
     with _native.ShardGroup(world) as group:
-        sessions = [_native.ShardSession(nsub, nchan, nbin, r, world, group=group, device=devices[r],
-                                         delay=None if delay is None else np.asarray(delay)[..., chans[r][0]:chans[r][1]],
-                                         **kw)
-                    for r in range(world)]
+        sessions = []
         try:
+            for r in range(world):   # (inside the try: a shard that cannot be made closes the ones before it)
+                sessions.append(_native.ShardSession(
+                    nsub, nchan, nbin, r, world, group=group, device=devices[r],
+                    delay=None if delay is None else np.asarray(delay)[..., chans[r][0]:chans[r][1]], **kw))
             for r, s in enumerate(sessions):
                 c0, c1 = chans[r]
                 if fit_tail is not None:
@@ -68,6 +107,8 @@ def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, f
                         out["amp"], out["info"] = s.fit()
                         out["std"], out["mean"], out["ptp"], out["fft"] = s.diagnostics()
                         out["T"] = s.template()
+                        if kw.get("detrend") is not None and any(kw["detrend"][:2]):
+                            out["trend_chan"], out["trend_subint"] = s.trends()
                     results[r] = out
                 except Exception as e:  # noqa: BLE001 - re-raised below
                     errors.append((r, e))
@@ -100,11 +141,16 @@ def _merge(results, chans, shape2, want_details):
     merged["weights"] = _gather_cols([o["weights"] for o in results], chans, shape2, np.float32)
     if want_details and "amp" in first:
         for key, dt in (("amp", np.float64), ("info", np.int32), ("std", np.float64),
-                        ("mean", np.float64), ("ptp", np.float32), ("fft", np.float64)):
+                        ("mean", np.float64), ("ptp", first["ptp"].dtype), ("fft", np.float64)):
             merged[key] = _gather_cols([o[key] for o in results], chans, shape2, dt)
         for r, o in enumerate(results[1:], 1):
             if o["T"].tobytes() != first["T"].tobytes():
                 raise _native.NativeError("shard %d has a different template" % r)
+        if "trend_chan" in first:
+            merged["trend_chan"] = np.concatenate([o["trend_chan"] for o in results], axis=1)
+            for r, o in enumerate(results[1:], 1):
+                if o["trend_subint"].tobytes() != first["trend_subint"].tobytes():
+                    raise _native.NativeError("shard %d has different subint trends" % r)
     return merged
 
 
@@ -114,7 +160,9 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     `cube_slice` etc. are the rank's channel range (``_native.shard_layout``);
     returns the merged full-archive dict on every rank (with want_residual, the
     full residual cube on rank 0 only).  ``delay`` (in args): the slice's
-    fractional delays (FFT-rotation dedispersion; (nchan_r,) or (nsub, nchan_r))."""
+    fractional delays (FFT-rotation dedispersion; (nchan_r,) or (nsub, nchan_r)).
+    ``detrend`` / ``detrend_pieces`` with ``shard_detrend=True``: as
+    clean_cube_local; the pieces are resolved against `global_shape`."""
     import torch.distributed as dist
 
     from .dist import TorchComm
@@ -124,7 +172,7 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     chans, _ = _native.shard_layout(nsub, nchan, world)
     try:
         with _native.ShardSession(nsub, nchan, nbin, rank, world, comm=comm, device=_device_index(device),
-                                  delay=args.get("delay"), **_loop_kwargs(args)) as s:
+                                  delay=args.get("delay"), **_loop_kwargs(args, (nsub, nchan))) as s:
             if np.ndim(cube_slice) == 4:   # full-pol: pscrunched on the GPU
                 s.upload_pols(cube_slice, w0_slice, shift_slice)
             else:

@@ -8,6 +8,12 @@ process; several ranks may share one GPU with --backend gloo).
 Every rank cleans its channel shard through dist.TorchComm; rank 0 then cleans
 the whole archive in one unsharded session and asserts the zap mask, test
 values and loop counters are bit-identical.  Prints one JSON line on rank 0.
+
+--detrend "chan,subint[,rounds,clip]" (with --detrend-pieces "<chan>;<subint>",
+IC_DETREND_PIECES' form, cut on the whole archive's lines) runs both the shards
+and the one-session reference with the detrended scaling, on a cube with a 3x
+bandpass slope; the shards need the opt-in --detrend-shards on every rank
+(ShardSession shard_detrend), without it the sharded call raises.
 """
 from __future__ import annotations
 
@@ -35,6 +41,9 @@ def main():
     ap.add_argument("--fail-at", type=int, default=3)
     ap.add_argument("--out", default="", help="directory for one JSON result file per rank")
     ap.add_argument("--cli-suffix", default=".ar", help="--cli: archive file suffix (.ar npz, .sf PSRFITS)")
+    ap.add_argument("--detrend", default="", help="chan,subint[,rounds,clip]: detrended scaling on both sides")
+    ap.add_argument("--detrend-pieces", default="", help="<chan>;<subint>: piecewise detrending (needs --detrend)")
+    ap.add_argument("--detrend-shards", action="store_true", help="opt in to detrending on shards")
     a = ap.parse_args()
     if a.cli:
         return cli_check(a)
@@ -58,13 +67,20 @@ def main():
     nsub, nchan, nbin = a.shape
     data, w0, shift = synth.make_cube(nsub, nchan, nbin, a.seed, 0.2)
     raw = np.ascontiguousarray(data[:, 0])
+    from iterative_cleaner_amd import detrend as dt
+    detrend = dt.parse_detrend(a.detrend)
+    pieces = dt.normalise_pieces(dt.parse_pieces(a.detrend_pieces), nsub, nchan, detrend) if a.detrend_pieces else None
+    dkw = {}
+    if detrend is not None:
+        raw = np.ascontiguousarray((raw * np.linspace(3.0, 1.0, nchan)[None, :, None]).astype(np.float32))
+        dkw = dict(detrend=detrend, detrend_pieces=pieces)
     chans, _ = _native.shard_layout(nsub, nchan, world)
     c0, c1 = chans[rank]
     t0 = time.perf_counter()
     fail_at = a.fail_at if rank == a.fail_rank else None
     try:
         out = sharded.clean_cube_dist(raw[:, c0:c1], w0[:, c0:c1], shift[c0:c1], (nsub, nchan, nbin), dev,
-                                      fail_at=fail_at, fit_mode=a.fit_mode)
+                                      fail_at=fail_at, fit_mode=a.fit_mode, shard_detrend=a.detrend_shards, **dkw)
     except _native.NativeError as e:
         # a failed shard (injected, or a peer that failed): report and leave
         rec = {"rank": rank, "world": world, "failed": True, "error": str(e),
@@ -76,8 +92,11 @@ def main():
     ok = None
     rec = {"rank": rank, "backend": a.backend, "world": world, "shape": a.shape, "loops": out["loops"],
            "zapped": int((out["weights"] == 0).sum()), "seconds": round(dt, 3), "failed": False}
+    if detrend is not None:
+        rec["detrend"] = list(detrend)
+        rec["pieces"] = None if pieces is None else [1 if b is None else len(b) for b in pieces]
     if rank == 0:
-        with _native.GpuSession(nsub, nchan, nbin, device=dev.index, fit_mode=a.fit_mode) as s:
+        with _native.GpuSession(nsub, nchan, nbin, device=dev.index, fit_mode=a.fit_mode, **dkw) as s:
             s.upload(raw, w0, shift)
             one = s.run()
         ok = (out["weights"].tobytes() == one["weights"].tobytes()

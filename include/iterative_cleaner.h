@@ -615,6 +615,59 @@ int ic_comprehensive_stats_detrend_pieces(int device, int nsub, int nchan, int n
 int ic_shard_enable_detrend(void *session);
 
 /* ------------------------------------------------------------------------
+ * Standard template (opt-in): clean against a supplied profile of the pulsar
+ * instead of the template the loop builds from the archive itself.  The written
+ * definition is iterative_cleaner_amd/std_template.py, which the kernels
+ * (k_std_ccf, k_std_peak, k_std_install) follow bit for bit; the ABI version
+ * stays 9 (additions only).
+ *
+ * ic_set_std_template: T [nbin] f32 is the standard, used as given (no x10000,
+ * no normalisation: the fit's amplitude absorbs the scale); align is how it is
+ * brought onto the archive's pulse phase in every run:
+ *   IC_ALIGN_NONE  as given (no cross-correlation is made);
+ *   IC_ALIGN_INT   rolled by the lag of the cross-correlation peak with the
+ *                  archive's own first template (the original samples, exact);
+ *   IC_ALIGN_FRAC  rotated by lag + the parabola's sub-bin part, by the FFT
+ *                  phase rotation of ic_rotate_profiles2; only at the lengths
+ *                  that rotation serves (IC_EINVAL elsewhere, naming IC_ALIGN_INT).
+ * T == NULL clears it: the session is back to the iterative template, bit for
+ * bit.  IC_EINVAL: nbin != the session's, nbin < 4, a non-finite value, a
+ * constant profile, an unknown align.  The standard is kept across uploads (a
+ * batch lane sets it once); the alignment is redone for every archive, on the
+ * session's stream, with no host read.  A failed alignment (a non-finite
+ * correlation, e.g. from a NaN sample in the archive, no positive peak, or a
+ * trough deeper than the peak: an anti-correlated standard) is not an error of
+ * the run: the standard is then used as given and aligned = 0
+ * is reported.
+ * ic_run with a standard set is ONE pass: nothing in an iteration depends on
+ * the previous mask, so if iteration 1 changes the weights and max_iter >= 2,
+ * iteration 2 is reported without being launched (loops = 2, converged = 1,
+ * changed[1] = 0, nzero[1] = nzero[0], the same bad-fit count); an unchanged
+ * mask ends with loops = 1 and max_iter = 1 with loops = 1, not converged, as
+ * ever.  ic_get_template then returns the template in use: the aligned
+ * standard.  Every other mode (closed-form fit, data_f64, both dedispersion
+ * modes, detrended scaling, quantised uploads, residuals) is unchanged.
+ * On channel shards every rank must set the same standard and mode; each rank
+ * aligns for itself against the same scrunched template and gets the same
+ * bits, the result equals one GPU's.  Ranks that disagree are detected: the
+ * counters' all-reduce of every shard run carries two more words, a hash of
+ * the standard and mode, or zeros where none is set, and ic_run fails with
+ * IC_EINVAL on a rank whose words differ from the sum's share (different
+ * standards, different modes, or a standard on only some ranks).
+ * ic_get_std_alignment: the last run's aligned (0 / 1), lag (bins) and shift
+ * (bins, lag + sub-bin part; IC_ALIGN_INT reports it too); any may be NULL;
+ * all zero with IC_ALIGN_NONE.  IC_ESTATE without a standard or before a run.
+ * ic_align_template: a one-shot of the same kernels: S the standard, A the
+ * template to align against, out [nbin] the template the loop would install. */
+#define IC_ALIGN_NONE 0
+#define IC_ALIGN_INT 1
+#define IC_ALIGN_FRAC 2
+int ic_set_std_template(void *session, const float *T, int nbin, int align);
+int ic_get_std_alignment(void *session, int32_t *aligned, int32_t *lag, double *shift);
+int ic_align_template(int device, int nbin, const float *S, const float *A, int align, float *out, int32_t *aligned,
+                      int32_t *lag, double *shift);
+
+/* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
  * SURVEY.md §8(e)).  The reference cleans an archive in one process
  * (iterative_cleaner.py:83-146); these entry points split the same loop by

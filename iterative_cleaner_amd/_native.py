@@ -31,7 +31,7 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait",
            "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend",
            "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces",
-           "ic_shard_enable_detrend")
+           "ic_shard_enable_detrend", "ic_set_std_template", "ic_get_std_alignment", "ic_align_template")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -189,6 +189,9 @@ def load_library(path: str = LIB_PATH):
     lib.ic_set_detrend_pieces.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.ic_get_trends_pieces.argtypes = [vp, vp, vp]
     lib.ic_shard_enable_detrend.argtypes = [vp]
+    lib.ic_set_std_template.argtypes = [vp, vp, C.c_int, C.c_int]
+    lib.ic_get_std_alignment.argtypes = [vp, vp, vp, vp]
+    lib.ic_align_template.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.ic_comprehensive_stats_detrend_pieces.argtypes = (list(lib.ic_comprehensive_stats_detrend.argtypes)
                                                           + [C.c_int, vp, C.c_int, vp])
     if lib.ic_abi_version() != ABI_VERSION:
@@ -239,7 +242,7 @@ class GpuSession:
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
                  delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None,
-                 detrend=None, detrend_pieces=None):
+                 detrend=None, detrend_pieces=None, std_template=None):
         """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
         with these delays (set_delays).  dedisp_fft=True: the same mode without
         delays yet: they come with set_delays, or with each archive
@@ -250,7 +253,10 @@ class GpuSession:
         detrend = (chan_order, subint_order[, rounds, clip]): detrended scaling
         (set_detrend; detrend.py); None: ic_set_detrend is never called.
         detrend_pieces = (chan, subint): piecewise detrending
-        (set_detrend_pieces); None: ic_set_detrend_pieces is never called."""
+        (set_detrend_pieces); None: ic_set_detrend_pieces is never called.
+        std_template = the standard profile (nbin,) or (profile, align): the
+        opt-in cleaning against a supplied template (set_std_template;
+        std_template.py); None: ic_set_std_template is never called."""
         from .phase_rotation import any_length_enabled
         fft_mode = DEDISP_FFT_ANY if (any_length_enabled() if any_length is None else any_length) else DEDISP_FFT
         self.lib = load_library()
@@ -269,6 +275,7 @@ class GpuSession:
             raise NativeError("%s: %s (rc=%d)" % (self._create_name, _err(self.lib), rc))
         self.h = h
         self.pieces = None   # (mc, ms) while pieces are set
+        self.std_mode = None   # IC_ALIGN_* while a standard template is set
         try:
             for name, value in (options or {}).items():
                 self.set_option(name, value)
@@ -278,6 +285,8 @@ class GpuSession:
                 self.set_detrend(*detrend)
             if detrend_pieces is not None:
                 self.set_detrend_pieces(*detrend_pieces)
+            if std_template is not None:
+                self.set_std_template(*_std_pair(std_template))
         except Exception:
             self.close()   # no half-made session is left for the collector (a shard's must go before its group)
             raise
@@ -296,6 +305,35 @@ class GpuSession:
         ms, sb = _piece_starts(subint, nchan)
         self._check(self.lib.ic_set_detrend_pieces(self.h, mc, _ptr(cb), ms, _ptr(sb)), "ic_set_detrend_pieces")
         self.pieces = (max(mc, 1), max(ms, 1)) if (mc or ms) else None
+
+    def set_std_template(self, T, align="auto"):
+        """Clean against the standard profile T (nbin,) in the runs that follow
+        (ic_set_std_template; the definition is std_template.py): align "none"
+        (as given), "int" (rolled by the cross-correlation lag), "frac" (rotated
+        by lag + sub-bin part; only where the FFT rotation serves nbin) or
+        "auto" (frac where available, else int).  The standard stays set across
+        uploads; every run aligns it against that archive and is one pass.  On a
+        channel shard every rank must set the same standard and mode."""
+        from . import std_template as st
+        nbin = self.shape[2]
+        S = st.check(T, nbin)
+        mode = st.resolve_align(align, nbin)
+        self._check(self.lib.ic_set_std_template(self.h, _ptr(S), nbin, mode), "ic_set_std_template")
+        self.std_mode = mode
+
+    def clear_std_template(self):
+        """Back to the iterative template (ic_set_std_template with NULL)."""
+        self._check(self.lib.ic_set_std_template(self.h, None, self.shape[2], 0), "ic_set_std_template")
+        self.std_mode = None
+
+    def std_alignment(self):
+        """The last run's alignment of the standard (ic_get_std_alignment):
+        dict(aligned, lag, shift); all zero with align "none"."""
+        al, lag = C.c_int32(), C.c_int32()
+        sh = C.c_double()
+        self._check(self.lib.ic_get_std_alignment(self.h, C.byref(al), C.byref(lag), C.byref(sh)),
+                    "ic_get_std_alignment")
+        return dict(aligned=int(al.value), lag=int(lag.value), shift=float(sh.value))
 
     def set_detrend(self, chan_order, subint_order, rounds=4, clip=5.0):
         """Detrended scaling for the runs that follow (ic_set_detrend; the
@@ -483,9 +521,12 @@ class GpuSession:
         k = int(n_iter[0])
         bad = np.zeros(m, np.int32)
         self._check(self.lib.ic_get_bad_fits(self.h, _ptr(bad), m), "ic_get_bad_fits")
-        return dict(test=test, weights=weights, loops=int(loops[0]), n_iter=k,
-                    converged=bool(conv[0]), changed=changed[:k].copy(), nzero=nzero[:k].copy(),
-                    bad_fits=bad[:k].copy())
+        out = dict(test=test, weights=weights, loops=int(loops[0]), n_iter=k,
+                   converged=bool(conv[0]), changed=changed[:k].copy(), nzero=nzero[:k].copy(),
+                   bad_fits=bad[:k].copy())
+        if self.std_mode is not None and k > 0:
+            out["std_alignment"] = self.std_alignment()
+        return out
 
     def residual(self):
         out = np.empty(self.shape, np.float32)
@@ -594,6 +635,35 @@ class GpuSession:
             name = self.lib.ic_kernel_name(buf[q].kernel).decode()
             out[name] = dict(ms=buf[q].ms, launches=buf[q].launches)
         return out
+
+
+def _std_pair(std_template):
+    """A std_template argument of a session (a profile, or (profile, align)) ->
+    (profile, align)."""
+    if (isinstance(std_template, (tuple, list)) and len(std_template) == 2
+            and isinstance(std_template[1], (str, int, np.integer)) and np.ndim(std_template[0]) == 1):
+        return std_template[0], std_template[1]
+    return std_template, "auto"
+
+
+def align_template(S, A, align="auto", device=0):
+    """The alignment kernels alone (ic_align_template): the standard S against
+    the template A, both (nbin,) -> dict(aligned, lag, shift, template, mode) as
+    std_template.align states it."""
+    from . import std_template as st
+    lib = load_library()
+    S = st.check(S, np.shape(S)[0] if np.ndim(S) == 1 else st.MIN_NBIN)
+    nbin = S.shape[0]
+    mode = st.resolve_align(align, nbin)
+    A = np.ascontiguousarray(A, dtype=np.float32).reshape(nbin)
+    out = np.empty(nbin, np.float32)
+    al, lag = C.c_int32(), C.c_int32()
+    sh = C.c_double()
+    rc = lib.ic_align_template(int(device), nbin, _ptr(S), _ptr(A), mode, _ptr(out), C.byref(al), C.byref(lag),
+                               C.byref(sh))
+    if rc != 0:
+        raise NativeError("ic_align_template: %s (rc=%d)" % (_err(lib), rc))
+    return dict(aligned=int(al.value), lag=int(lag.value), shift=float(sh.value), template=out, mode=mode)
 
 
 def fit_profiles(profiles, template, fit_mode=FIT_EXACT, device=0):

@@ -105,7 +105,8 @@ class _ResidualQueue:
         return out, j
 
 
-def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, detrend_pieces=None):
+def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, detrend_pieces=None,
+             std_template=None):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -133,7 +134,15 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, d
     detrend = (chan_order, subint_order[, rounds, clip]): set on the session
     before the first run (GpuSession.set_detrend); None leaves the session as
     it is.  detrend_pieces = (chan, subint): likewise
-    (GpuSession.set_detrend_pieces)."""
+    (GpuSession.set_detrend_pieces).  std_template: the standard profile every
+    archive is cleaned against (GpuSession.set_std_template; a profile, a path,
+    or a pair with the align mode), set once before the first run and aligned
+    against each archive; every dict then holds out["std_alignment"].  None
+    leaves the session as it is (clean_batch and run_loop are where the
+    IC_STD_TEMPLATE switch is read)."""
+    if std_template is not None:
+        from .std_template import normalise
+        session.set_std_template(*normalise(std_template, session.shape[2]))
     if detrend is not None:
         session.set_detrend(*detrend)
     if detrend_pieces is not None:
@@ -169,7 +178,8 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, d
 _EXITED = -2   # a worker's last message (run_lanes)
 
 
-def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1, residuals=None):
+def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1, residuals=None,
+              std_template=None):
     """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
     each with or without trailing delays, as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
@@ -181,6 +191,8 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
     `pipeline`'s: every dict comes with out["residual_q"], a triple of its
     lane, valid until the generator is advanced past it - a lane takes a slot
     again only after the consumer has moved on from the result that held it.
+
+    std_template: `pipeline`'s, set on every session before the first run.
 
     On a worker error, or when the consumer stops early (generator closed), the
     lanes stop: the `stop` event (created here if not given) is set, queued work
@@ -194,6 +206,10 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
     if residuals is not None and len(residuals) != len(sessions):
         raise ValueError("residuals needs one sequence of (q, scl, offs) triples per session (%d), not %d"
                          % (len(sessions), len(residuals)))
+    if std_template is not None:
+        from .std_template import normalise
+        for sess in sessions:
+            sess.set_std_template(*normalise(std_template, sess.shape[2]))
     if len(sessions) == 1:
         yield from pipeline(sessions[0], items, fetch, nsum, None if residuals is None else residuals[0])
         return
@@ -406,7 +422,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
                 any_length=None, residuals=False, residual_big_endian=True, detrend=None,
-                detrend_pieces=None):
+                detrend_pieces=None, std_template=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -449,7 +465,13 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     detrend = (chan_order, subint_order[, rounds, clip]): the opt-in detrended
     scaling (detrend.py) on every lane's session; None reads the IC_DETREND
     switch (unset, empty or 0: off).  detrend_pieces = (chan, subint): piecewise
-    detrending (cleaner.run_loop's); None reads the IC_DETREND_PIECES switch."""
+    detrending (cleaner.run_loop's); None reads the IC_DETREND_PIECES switch.
+    std_template (cleaner.run_loop's: a profile (nbin,), a path, or a pair with
+    the align mode): every archive is cleaned against this standard profile
+    (std_template.py), set once on every lane's session and aligned against
+    each archive; out["std_alignment"] is per archive, and a failed alignment
+    warns on stderr.  None reads the IC_STD_TEMPLATE switch."""
+    from . import std_template as stdt
     from .detrend import normalise, normalise_pieces
     detrend = normalise(detrend)
     detrend_pieces = normalise_pieces(detrend_pieces, int(shape[0]), int(shape[1]), detrend)
@@ -460,6 +482,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     if quantised and nsum not in (1, 2):
         raise ValueError("nsum must be 1 or 2")
     nsub, nchan, nbin = (int(x) for x in shape)
+    std = stdt.normalise(std_template, nbin)
     lanes = int(lanes)
     if lanes < 1:
         raise ValueError("lanes must be >= 1")
@@ -569,11 +592,13 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
                                                dedisp_fft=fft, any_length=any_length, detrend=detrend,
-                                               detrend_pieces=detrend_pieces))
+                                               detrend_pieces=detrend_pieces, std_template=std))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
                               residuals=[rr.triples() for rr in result_rings] if residuals else None)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
+            if std is not None:
+                stdt.warn_failed(out.get("std_alignment"), std[1], "archive %d of the batch" % k)
             yield out
         if error:
             raise error[0]

@@ -208,7 +208,7 @@ def _device() -> int:
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
              data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
-             detrend=None, detrend_pieces=None, detrend_shards=None):
+             detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -233,7 +233,14 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     (chan, subint): piecewise detrending (detrend.py), each side None, a piece
     count, "wN" (a piece every N entries) or the pieces' starts; None reads the
     switch IC_DETREND_PIECES="<chan>;<subint>".  Without a detrend order in a
-    direction its pieces are ignored."""
+    direction its pieces are ignored.  ``std_template``: the opt-in cleaning
+    against a supplied standard profile (std_template.py): a profile (nbin,), a
+    path (``.npy`` or an archive), or a pair (profile or path, align) with align
+    one of "auto", "none", "int", "frac"; None reads the switch
+    IC_STD_TEMPLATE="<path>[,<align>]" (unset or empty: off).  The result then
+    holds ``std_alignment`` = dict(aligned, lag, shift); a failed alignment
+    warns once on stderr."""
+    from . import std_template as stdt
     from .detrend import normalise, normalise_pieces, shards_enabled
     from .dist import channel_sharding
     detrend = normalise(detrend)
@@ -249,6 +256,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     pols = cube.ndim == 4
     nsub, nchan, nbin = (cube.shape[0], cube.shape[2], cube.shape[3]) if pols else cube.shape
     sharding = channel_sharding()
+    std = stdt.normalise(std_template, nbin)
     # a shard's pieces are those of the archive's whole lines, the same on every rank
     detrend_pieces = normalise_pieces(detrend_pieces, nsub, nchan_total if sharding and nchan_total else nchan,
                                       detrend)
@@ -266,20 +274,23 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
             w0, shift = np.asarray(w0)[:, c0:c1], np.asarray(shift)[c0:c1]
             delay = None if delay is None else np.asarray(delay)[..., c0:c1]
             nchan_total = nchan
-        return sharded.clean_cube_dist(
+        out = sharded.clean_cube_dist(
             np.ascontiguousarray(cube), np.ascontiguousarray(w0), np.asarray(shift), (nsub, nchan_total, nbin),
             dev, want_residual=want_residual,
             max_iter=args.max_iter, chanthresh=args.chanthresh, subintthresh=args.subintthresh,
             pulse_region=args.pulse_region, baseline_duty=baseline_duty, data_f64=data_f64, delay=delay,
-            input_dedispersed=input_dedispersed,
+            input_dedispersed=input_dedispersed, **({} if std is None else dict(std_template=std)),
             **(dict(detrend=detrend, detrend_pieces=detrend_pieces, shard_detrend=True) if detrend is not None else {}))
+        if rank == 0 and std is not None:
+            stdt.warn_failed(out.get("std_alignment"), std[1])
+        return out
     if nchan_total is not None and nchan_total != nchan:
         raise ValueError("a channel slice of an archive needs channel sharding")
     with _native.GpuSession(nsub, nchan, nbin, args.max_iter, args.chanthresh, args.subintthresh,
                             args.pulse_region, baseline_duty,
                             device=_device() if device is None else device, data_f64=data_f64, delay=delay,
                             input_dedispersed=input_dedispersed, detrend=detrend,
-                            detrend_pieces=detrend_pieces) as s:
+                            detrend_pieces=detrend_pieces, std_template=std) as s:
         if quantised is not None:
             s.upload_quantised(quantised[0], quantised[1], quantised[2], w0, shift, quantised[3])
         elif pols:
@@ -292,6 +303,8 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
                 out["residual_q"] = s.residual_quantised(big_endian=True)
             else:
                 out["residual"] = s.residual()
+    if std is not None:
+        stdt.warn_failed(out.get("std_alignment"), std[1])
     return out
 
 
@@ -341,10 +354,11 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None):
+def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None):
     """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend,
-    detrend_pieces, detrend_shards: run_loop's (None = the IC_DETREND /
-    IC_DETREND_PIECES / IC_DETREND_SHARDS switches; there is no CLI flag).  Under
+    detrend_pieces, detrend_shards, std_template: run_loop's (None = the
+    IC_DETREND / IC_DETREND_PIECES / IC_DETREND_SHARDS / IC_STD_TEMPLATE
+    switches; there is no CLI flag).  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -393,7 +407,7 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
                    residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces,
-                   detrend_shards=detrend_shards)
+                   detrend_shards=detrend_shards, std_template=std_template)
     del cube
 
     x = 0

@@ -1,7 +1,7 @@
 // ic_internal.h — shared declarations between the host session (ic_session.hip)
 // and the gfx950 kernel units (ic_template.hip, ic_codec.hip, ic_fit.hip,
-// ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip).  Not part of the
-// public C-ABI.
+// ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip, ic_stdtemplate.hip).
+// Not part of the public C-ABI.
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -111,6 +111,8 @@ enum KernelId {
     K_TNORM,          // fit_mode 1: sum(T*T)
     K_ROTATE,         // fractional dedispersion (FFT phase rotation)
     K_RESIDUAL_Q,     // the residual formed and encoded to int16 in one pass
+    K_STD_ALIGN,      // standard template: k_std_ccf and k_std_peak
+    K_STD_INSTALL,    // standard template: k_std_install
     K_COUNT
 };
 
@@ -675,5 +677,28 @@ struct ResidualQArgs {
     int grid_cap;               // > 0: at most this many blocks (IC_OPT_GRID_CAP)
 };
 hipError_t launch_residual_q(hipStream_t st, const ResidualQArgs &a);
+
+// Standard template (ic_set_std_template; std_template.py): the alignment modes
+// (the public IC_ALIGN_*), the record k_std_peak writes - its shift is also the
+// device-resident delay the `frac` rotation reads (RotateArgs.delay2) - and the
+// launchers of ic_stdtemplate.hip.
+constexpr int kAlignNone = 0, kAlignInt = 1, kAlignFrac = 2;
+struct StdAlignRec {
+    double shift;       // lag + the parabola's sub-bin part; 0.0 after a failed alignment
+    int32_t aligned;    // 1: a positive finite peak was found
+    int32_t lag;        // first argmax of the cross-correlation; 0 after a failed alignment
+};
+// dynamic LDS of k_std_ccf: S and A as f32
+size_t std_ccf_lds_bytes(int nbin);
+// c[k] = sum_i f64(A[i]) * (f64(S[(i - k) mod nbin]) - m), ascending i; m: the
+// mean of f64(S) summed in ascending index (host)
+hipError_t launch_std_ccf(hipStream_t st, const float *S, const float *A, int nbin, double m, double *c,
+                          int grid_cap = 0);
+hipError_t launch_std_peak(hipStream_t st, const double *c, int nbin, StdAlignRec *rec);
+// T [nbin], T64 [ldD] (zero tail), T2 [2 nbin] (optional) from S as given
+// (kAlignNone; rec and R unused), S gathered by rec->lag (kAlignInt) or R, the
+// rotated standard, when rec->aligned, else S (kAlignFrac)
+hipError_t launch_std_install(hipStream_t st, const float *S, const float *R, const StdAlignRec *rec, int mode,
+                              int nbin, int ldD, float *T, double *T64, double *T2, int grid_cap = 0);
 
 }  // namespace icgpu

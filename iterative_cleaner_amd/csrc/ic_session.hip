@@ -142,7 +142,8 @@ const char *kKernelNames[K_COUNT] = {"k_chan_partials", "k_window",    "k_base",
                                      "k_fscrunch",      "k_tscrunch",  "k_fit_pass", "k_fit_state",
                                      "k_diag",          "k_linestats", "k_combine",  "k_residual",
                                      "k_fit_tail",      "k_sb_tree",   "k_shard_pack", "exchange",
-                                     "k_tnorm",         "k_rotate",    "k_residual_q"};
+                                     "k_tnorm",         "k_rotate",    "k_residual_q", "k_std_align",
+                                     "k_std_install"};
 
 constexpr long kTailProfiles = 8192;  // default: hand the remaining profiles to k_fit_tail below this
 constexpr long kTailProfilesLarge = 4096;   // the same for sessions of >= 2^20 profiles
@@ -268,6 +269,20 @@ struct Session {
     bool sh_dt = false;
     double *xt_send = nullptr, *xt_recv = nullptr;
     size_t xt_ms = 0;
+    // standard template (ic_set_std_template; std_template.py): std_on selects the
+    // one-pass loop that fits against the supplied profile.  std_S: the standard
+    // as given [nbin]; std_rot: its rotated copy (frac); std_c: the
+    // cross-correlation [nbin]; std_rec: k_std_peak's record.  All from `mem` at
+    // the first set, kept across uploads; std_mean: the mean of f64(S), summed in
+    // ascending index when it is set; std_hash: 30 bits of the standard's samples
+    // and mode (a shard's ranks compare them); std_ran: the last run aligned
+    bool std_on = false, std_ran = false;
+    int std_mode = IC_ALIGN_NONE;
+    double std_mean = 0.0;
+    uint32_t std_hash = 0;
+    float *std_S = nullptr, *std_rot = nullptr;
+    double *std_c = nullptr;
+    StdAlignRec *std_rec = nullptr;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -1009,6 +1024,73 @@ int iteration_template(Session *s, int iter)
     return scrunch_stage(s);
 }
 
+// The rules of std_template.py check(): 0 or the message
+const char *std_check(const float *S, int nbin)
+{
+    if (nbin < 4) return "fewer than 4 bins";
+    bool constant = true;
+    for (int i = 0; i < nbin; ++i) {
+        if (!std::isfinite(S[i])) return "a non-finite value";
+        if (S[i] != S[0]) constant = false;
+    }
+    return constant ? "a constant profile" : nullptr;
+}
+
+// m of std_template.py ccf(): the sum of f64(S) in ascending index, over nbin
+// (host code under -ffp-contract=off: one IEEE addition per sample)
+double std_mean_of(const float *S, int nbin)
+{
+    double acc = 0.0;
+    for (int i = 0; i < nbin; ++i) acc = acc + (double)S[i];
+    return acc / (double)nbin;
+}
+
+// the one-profile rotation of the `frac` alignment: S by -shift, the delay read
+// from the record on the device (k_rotate's per-profile-delay path)
+RotateArgs std_rotate_args(const float *S, const StdAlignRec *rec, int nbin, const double2 *tw, const double2 *tw_p2,
+                           float *out, int grid_cap)
+{
+    RotateArgs a{};
+    a.in = S;
+    a.ld_in = nbin;
+    a.delay2 = &rec->shift;
+    a.sign = -1;
+    a.tw = tw;
+    a.tw_p2 = tw_p2;
+    a.nsub = 1;
+    a.nchan = 1;
+    a.nbin = nbin;
+    a.out = out;
+    a.ldo = nbin;
+    a.grid_cap = grid_cap;
+    return a;
+}
+
+// The standard template (ic_set_std_template) takes the place of iteration 1's
+// own: s->T holds A, the archive's first template (iteration_template(s, 1));
+// the standard is aligned against it and installed as T, T64 and T2, all on the
+// session's stream with no host read (std_template.py; DESIGN.md "Standard
+// template").  On a shard every rank holds the same A after scrunch_stage and
+// aligns for itself: the same bits on every rank, no exchange.
+int std_stage(Session *s)
+{
+    const int nbin = s->p.nbin;
+    if (s->std_mode == IC_ALIGN_NONE) {
+        CK(hipMemsetAsync(s->std_rec, 0, sizeof(StdAlignRec), s->stream));
+    } else {
+        LAUNCH(s, K_STD_ALIGN,
+               launch_std_ccf(s->stream, s->std_S, s->T, nbin, s->std_mean, s->std_c, s->grid_cap));
+        LAUNCH(s, K_STD_ALIGN, launch_std_peak(s->stream, s->std_c, nbin, s->std_rec));
+    }
+    if (s->std_mode == IC_ALIGN_FRAC)
+        LAUNCH(s, K_ROTATE, launch_rotate(s->stream, std_rotate_args(s->std_S, s->std_rec, nbin, s->tw, s->tw_p2,
+                                                                     s->std_rot, s->grid_cap)));
+    LAUNCH(s, K_STD_INSTALL,
+           launch_std_install(s->stream, s->std_S, s->std_rot, s->std_rec, s->std_mode, nbin, s->ldD, s->T, s->T64,
+                              s->T2, s->grid_cap));
+    return 0;
+}
+
 // Row medians/MADs of a shard: the diagnostics rows go to their owners
 // (all-to-all), each owner runs the row selections over whole rows, and the
 // results are all-gathered into row_med/row_mad [4][nsub].
@@ -1507,7 +1589,8 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
                   {(void **)&s->xd_recv, drecv, "diagnostics receive"},
                   {(void **)&s->xr_send, sizeof(double) * 8 * s->rows_pad, "row statistics"},
                   {(void **)&s->xr_recv, sizeof(double) * 8 * s->rows_pad * world, "gathered row statistics"},
-                  {(void **)&s->counters, sizeof(int32_t) * (p.max_iter + 5), "counters"}};
+                  // + 2: the standard template's hash words (run_impl), summed with the counters
+                  {(void **)&s->counters, sizeof(int32_t) * (p.max_iter + 7), "counters"}};
         for (auto &b : xb)
             if (s->comm->alloc(b.ptr, b.bytes + 16) != 0 || !*b.ptr)
                 return bail(fail(IC_ENOMEM, "exchange buffer (%s, %zu bytes) failed", b.name, b.bytes));
@@ -1521,7 +1604,7 @@ int create_session(const ic_params *params, int device, int rank, int world, boo
         return bail(fail(IC_ENOMEM, "hipHostMalloc(round counts) failed"));
     if (hipEventCreateWithFlags(&s->sev, hipEventDisableTiming) != hipSuccess)
         return bail(fail(IC_EHIP, "hipEventCreate failed"));
-    if (hipHostMalloc((void **)&s->h_small, sizeof(int32_t) * ((size_t)p.max_iter + 20)) != hipSuccess)
+    if (hipHostMalloc((void **)&s->h_small, sizeof(int32_t) * ((size_t)p.max_iter + 24)) != hipSuccess)
         return bail(fail(IC_ENOMEM, "hipHostMalloc(readback) failed"));
     if (exact) {
         // fit state: 21 double arrays + 5 four-byte arrays, each padded to 256 B
@@ -2099,6 +2182,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     la.row_mad = s->lstat + 8 * nchan + 4 * nsub;
     const bool detrend = s->dt_chan > 0 || s->dt_sub > 0;
     s->trends_ran = false;
+    s->std_ran = false;
     if (detrend && !s->pw_on && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
         return fail(IC_ENOMEM, "hipMalloc(trend coefficients: %zu doubles) failed", (size_t)16 * (nchan + nsub));
     TrendArgs ta{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
@@ -2154,6 +2238,8 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
         x += 1;
         ++n_iter;
         if (int rc = iteration_template(s, n_iter)) return rc;
+        if (s->std_on)
+            if (int rc = std_stage(s)) return rc;
         DiagArgs da = diag_args(s, pr_start, pr_end);
         // the statistics pass: FFT dedispersion measures the residual rows
         // rotated back to the dispersed frame (R), written by k_rotate
@@ -2242,7 +2328,8 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
             if (s->comm)
                 if (int rc = shard_rowstats(s, la)) return rc;
         }
-        CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + 5), s->stream));
+        // (a shard's counters end in the two words of the standard template's hash, below)
+        CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + (s->comm ? 7 : 5)), s->stream));
         if (detrend && s->comm) {
             if (pieces)
                 LAUNCH(s, K_COMBINE,
@@ -2272,11 +2359,29 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
                                   la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
                                   p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, s->grid_cap));
         }
+        // a shard: two words of the standard template's hash (zero, as the
+        // memset left them, when none is set; the first at least 1 otherwise)
+        // ride behind the counters in the same all-reduce on every rank, so
+        // that ranks which set different standards or modes, or of which only
+        // some set one, are detected: each rank compares the sums with world
+        // times its own words
+        const int nhash = s->comm ? 2 : 0;
+        int32_t *hw = s->h_small + p.max_iter + 14;   // pinned
+        hw[0] = hw[1] = 0;
+        if (nhash && s->std_on) {
+            hw[0] = (int32_t)(s->std_hash & 0x7fffu) + 1;
+            hw[1] = (int32_t)((s->std_hash >> 15) & 0x7fffu);
+            CK(hipMemcpyAsync(s->counters + n_iter + 4, hw, sizeof(int32_t) * 2, hipMemcpyHostToDevice, s->stream));
+        }
         if (s->comm)
-            CM(s, s->comm->allreduce_sum_i32(s->counters, (size_t)(n_iter + 4), s->stream), "convergence counters");
-        CK(hipMemcpyAsync(cnt, s->counters, sizeof(int32_t) * (n_iter + 4), hipMemcpyDeviceToHost,
+            CM(s, s->comm->allreduce_sum_i32(s->counters, (size_t)(n_iter + 4 + nhash), s->stream),
+               "convergence counters");
+        CK(hipMemcpyAsync(cnt, s->counters, sizeof(int32_t) * (n_iter + 4 + nhash), hipMemcpyDeviceToHost,
                           s->stream));
         CK(spin_sync(s));
+        if (nhash && (cnt[n_iter + 4] != s->world * hw[0] || cnt[n_iter + 5] != s->world * hw[1]))
+            return fail(IC_EINVAL, "the ranks of this shard group set different standard templates or alignment "
+                                   "modes, or only some set one (ic_set_std_template): every rank must set the same");
         if (changed_out) changed_out[n_iter - 1] = cnt[0];
         if (nzero_out) nzero_out[n_iter - 1] = cnt[1];
         s->bad_fits.push_back(cnt[2]);
@@ -2287,6 +2392,21 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
                 converged = 1;
                 x = 1000000;
             }
+        if (s->std_on && !converged && p.max_iter >= 2) {
+            // One pass: with a fixed template iteration 2 reads what iteration 1
+            // read (D, w0, valid, T), so it would write the same diagnostics,
+            // test values and weights, change nothing and end the loop.  It is
+            // reported, not launched: its records repeat iteration 1's.
+            CK(hipMemcpyAsync(s->hist + 2 * s->P, s->hist + s->P, sizeof(float) * s->P, hipMemcpyDeviceToDevice,
+                              s->stream));
+            ++n_iter;
+            if (changed_out) changed_out[n_iter - 1] = 0;
+            if (nzero_out) nzero_out[n_iter - 1] = cnt[1];
+            s->bad_fits.push_back(cnt[2]);
+            loops = 2;
+            converged = 1;
+            x = 1000000;
+        }
     }
     if (x == p.max_iter) loops = p.max_iter;
     s->last_iter = n_iter;
@@ -2310,6 +2430,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     if (converged_out) *converged_out = converged;
     s->ran = n_iter > 0;
     s->trends_ran = detrend && n_iter > 0;
+    s->std_ran = s->std_on && n_iter > 0;
     return IC_OK;
 }
 
@@ -2876,6 +2997,130 @@ int ic_get_template(void *session, float *T)
     if (!s->ran) return fail(IC_ESTATE, "no completed iteration");
     CK(hipMemcpyAsync(T, s->T, sizeof(float) * s->p.nbin, hipMemcpyDeviceToHost, s->stream));
     CK(hipStreamSynchronize(s->stream));
+    return IC_OK;
+}
+
+static_assert(IC_ALIGN_NONE == kAlignNone && IC_ALIGN_INT == kAlignInt && IC_ALIGN_FRAC == kAlignFrac,
+              "the public alignment modes are the kernels'");
+
+// the argument rules ic_set_std_template and ic_align_template share; 0 or the
+// failed call's return code
+static int std_args(const char *name, const float *S, int nbin, int align)
+{
+    if (align != IC_ALIGN_NONE && align != IC_ALIGN_INT && align != IC_ALIGN_FRAC)
+        return fail(IC_EINVAL, "%s: align=%d (IC_ALIGN_NONE, IC_ALIGN_INT or IC_ALIGN_FRAC)", name, align);
+    if (const char *e = std_check(S, nbin)) return fail(IC_EINVAL, "%s: the standard has %s", name, e);
+    if (align == IC_ALIGN_FRAC && !rotate_supported(nbin))
+        return fail(IC_EINVAL, "%s: IC_ALIGN_FRAC needs " IC_ROT_NBIN_FMT " (nbin=%d); use IC_ALIGN_INT", name,
+                    IC_ROT_NBIN_ARGS, nbin);
+    if (std_ccf_lds_bytes(nbin) > kLdsBlockMax)
+        return fail(IC_EINVAL, "%s: nbin=%d needs %zu bytes of LDS for the cross-correlation (> 160 KiB)", name, nbin,
+                    std_ccf_lds_bytes(nbin));
+    return IC_OK;
+}
+
+int ic_set_std_template(void *session, const float *T, int nbin, int align)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!T) {   // back to the iterative template
+        s->std_on = false;
+        s->std_ran = false;
+        return IC_OK;
+    }
+    if (nbin != s->p.nbin)
+        return fail(IC_EINVAL, "ic_set_std_template: the standard has %d bins, the session %d (a standard of another "
+                               "length is not rebinned)", nbin, s->p.nbin);
+    if (int rc = std_args("ic_set_std_template", T, nbin, align)) return rc;
+    CK(hipSetDevice(s->device));
+    if (s->mem.ensure(&s->std_S, (size_t)nbin) != hipSuccess || s->mem.ensure(&s->std_rot, (size_t)nbin) != hipSuccess ||
+        s->mem.ensure(&s->std_c, (size_t)nbin) != hipSuccess || s->mem.ensure(&s->std_rec, 1) != hipSuccess)
+        return fail(IC_ENOMEM, "hipMalloc(standard template, %d bins) failed", nbin);
+    // a run ends synchronised, so nothing reads the standard set before
+    s->std_on = false;
+    CK(hipMemcpyAsync(s->std_S, T, sizeof(float) * nbin, hipMemcpyHostToDevice, s->stream));
+    CK(hipMemsetAsync(s->std_rec, 0, sizeof(StdAlignRec), s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    s->std_mean = std_mean_of(T, nbin);
+    uint32_t h = 2166136261u;   // FNV-1a over the samples' bytes, then the mode
+    const unsigned char *b = (const unsigned char *)T;
+    for (size_t q = 0; q < sizeof(float) * (size_t)nbin; ++q) h = (h ^ b[q]) * 16777619u;
+    h = (h ^ (uint32_t)align) * 16777619u;
+    s->std_hash = (h ^ (h >> 30)) & 0x3fffffffu;
+    s->std_mode = align;
+    s->std_on = true;
+    s->std_ran = false;
+    return IC_OK;
+}
+
+int ic_get_std_alignment(void *session, int32_t *aligned, int32_t *lag, double *shift)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!s->std_on) return fail(IC_ESTATE, "no standard template is set (ic_set_std_template)");
+    if (!s->ran || !s->std_ran) return fail(IC_ESTATE, "no completed run with the standard template");
+    CK(hipSetDevice(s->device));
+    StdAlignRec r;
+    CK(hipMemcpyAsync(&r, s->std_rec, sizeof r, hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    if (aligned) *aligned = r.aligned;
+    if (lag) *lag = r.lag;
+    if (shift) *shift = r.shift;
+    return IC_OK;
+}
+
+int ic_align_template(int device, int nbin, const float *S, const float *A, int align, float *out, int32_t *aligned,
+                      int32_t *lag, double *shift)
+{
+    if (!S || !A || !out) return fail(IC_EINVAL, "null argument");
+    if (int rc = std_args("ic_align_template", S, nbin, align)) return rc;
+    if (int rc = select_device(device)) return rc;
+    const auto bad = [](hipError_t e) { return named_fail("ic_align_template", e, true); };
+    const int ldD = ((nbin + kFitTile - 1) / kFitTile) * kFitTile;
+    Scratch sc;
+    float *dS = nullptr, *dA = nullptr, *dR = nullptr, *dT = nullptr;
+    double *dc = nullptr, *dT64 = nullptr, *dT2 = nullptr;
+    double2 *dtw = nullptr, *dtw2 = nullptr;
+    StdAlignRec *drec = nullptr;
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    CKF(sc.mem.alloc(&dS, (size_t)nbin), bad);
+    CKF(sc.mem.alloc(&dA, (size_t)nbin), bad);
+    CKF(sc.mem.alloc(&dR, (size_t)nbin), bad);
+    CKF(sc.mem.alloc(&dT, (size_t)nbin), bad);
+    CKF(sc.mem.alloc(&dc, (size_t)nbin), bad);
+    CKF(sc.mem.alloc(&dT64, (size_t)ldD), bad);
+    CKF(sc.mem.alloc(&dT2, (size_t)2 * nbin), bad);
+    CKF(sc.mem.alloc(&drec, 1), bad);
+    CKF(hipMemcpyAsync(dS, S, sizeof(float) * nbin, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dA, A, sizeof(float) * nbin, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemsetAsync(drec, 0, sizeof(StdAlignRec), st), bad);
+    if (align != IC_ALIGN_NONE) {
+        CKF(launch_std_ccf(st, dS, dA, nbin, std_mean_of(S, nbin), dc), bad);
+        CKF(launch_std_peak(st, dc, nbin, drec), bad);
+    }
+    std::vector<double2> tw, tw2;   // alive until the stream is synchronised
+    if (align == IC_ALIGN_FRAC) {
+        tw = host_twiddles(nbin);
+        tw2 = p2_twiddles(nbin);   // empty at a mixed-radix nbin: k_rotate_mr reads tw alone
+        CKF(sc.mem.alloc_exact(&dtw, tw.size()), bad);
+        CKF(hipMemcpyAsync(dtw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice, st), bad);
+        if (!tw2.empty()) {
+            CKF(sc.mem.alloc_exact(&dtw2, tw2.size()), bad);
+            CKF(hipMemcpyAsync(dtw2, tw2.data(), sizeof(double2) * tw2.size(), hipMemcpyHostToDevice, st), bad);
+        }
+        CKF(launch_rotate(st, std_rotate_args(dS, drec, nbin, dtw, dtw2, dR, 0)), bad);
+    }
+    CKF(launch_std_install(st, dS, dR, drec, align, nbin, ldD, dT, dT64, dT2), bad);
+    StdAlignRec r;
+    CKF(hipMemcpyAsync(out, dT, sizeof(float) * nbin, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipMemcpyAsync(&r, drec, sizeof r, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
+    if (aligned) *aligned = r.aligned;
+    if (lag) *lag = r.lag;
+    if (shift) *shift = r.shift;
     return IC_OK;
 }
 

@@ -29,15 +29,18 @@ def _gather_cols(parts, ranges, shape, dtype):
 # the keywords of **args: the session's (_loop_kwargs), and `delay`, which the
 # callers slice per rank themselves
 _LOOP_KEYS = ("max_iter", "chanthresh", "subintthresh", "pulse_region", "baseline_duty", "fit_mode", "data_f64",
-              "options", "input_dedispersed", "any_length", "detrend", "detrend_pieces", "shard_detrend")
+              "options", "input_dedispersed", "any_length", "detrend", "detrend_pieces", "shard_detrend",
+              "std_template")
 
 
-def _loop_kwargs(args, global_shape=None):
+def _loop_kwargs(args, global_shape=None, nbin=None):
     """The ShardSession keywords of a clean_cube_* call's **args.  An unknown
     keyword is an error, not dropped.  detrend (detrend.normalise's forms) needs
     shard_detrend=True, the opt-in every rank must give (ic_shard_enable_detrend);
     detrend_pieces are resolved once against the global (nsub, nchan), so every
-    rank gets the same starts."""
+    rank gets the same starts.  std_template (std_template.normalise's forms
+    but None, which is off: run_loop is where the IC_STD_TEMPLATE switch is
+    read) is loaded and checked once per call, for the archive's nbin."""
     unknown = sorted(set(args) - set(_LOOP_KEYS) - {"delay"})
     if unknown:
         raise TypeError("unknown keyword(s) for a sharded clean: %s" % ", ".join(unknown))
@@ -47,6 +50,9 @@ def _loop_kwargs(args, global_shape=None):
               baseline_duty=args.get("baseline_duty", 0.15), fit_mode=args.get("fit_mode", 0),
               data_f64=args.get("data_f64", False), options=args.get("options"),
               input_dedispersed=args.get("input_dedispersed", False), any_length=args.get("any_length"))
+    if args.get("std_template") is not None:
+        from .std_template import normalise as std_normalise
+        kw["std_template"] = std_normalise(args["std_template"], int(nbin))
     shard_detrend = bool(args.get("shard_detrend", False))
     detrend, pieces = args.get("detrend"), args.get("detrend_pieces")
     if detrend is not None and not shard_detrend:
@@ -76,13 +82,17 @@ def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, f
     ``detrend`` / ``detrend_pieces`` (GpuSession's) with ``shard_detrend=True``:
     the detrended scaling on shards; want_details then adds ``trend_chan``
     (every shard's channel coefficients, joined along the channels) and
-    ``trend_subint`` (all rows', checked equal across the shards)."""
+    ``trend_subint`` (all rows', checked equal across the shards).
+    ``std_template`` (a profile, a path, or a pair with the align mode; None:
+    off): the opt-in cleaning against a standard
+    profile (std_template.py), the same on every shard; ``std_alignment`` is
+    every shard's (checked equal)."""
     nsub, nchan, nbin = cube.shape
     devices = list(devices) if devices is not None else [0] * world
     if len(devices) != world:
         raise ValueError("need one device per shard")
     chans, _ = _native.shard_layout(nsub, nchan, world)
-    kw = _loop_kwargs(args, (nsub, nchan))
+    kw = _loop_kwargs(args, (nsub, nchan), nbin)
     delay = args.get("delay")
     results = [None] * world
     errors = []
@@ -136,6 +146,8 @@ def _merge(results, chans, shape2, want_details):
         if not (np.array_equal(out["changed"], first["changed"])
                 and np.array_equal(out["nzero"], first["nzero"])):
             raise _native.NativeError("shard %d disagrees on the convergence counters" % r)
+        if out.get("std_alignment") != first.get("std_alignment"):
+            raise _native.NativeError("shard %d aligned the standard template differently" % r)
     merged = dict(first)
     merged["test"] = _gather_cols([o["test"] for o in results], chans, shape2, np.float64)
     merged["weights"] = _gather_cols([o["weights"] for o in results], chans, shape2, np.float32)
@@ -162,7 +174,8 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     full residual cube on rank 0 only).  ``delay`` (in args): the slice's
     fractional delays (FFT-rotation dedispersion; (nchan_r,) or (nsub, nchan_r)).
     ``detrend`` / ``detrend_pieces`` with ``shard_detrend=True``: as
-    clean_cube_local; the pieces are resolved against `global_shape`."""
+    clean_cube_local; the pieces are resolved against `global_shape`.
+    ``std_template``: as clean_cube_local; every rank must pass the same."""
     import torch.distributed as dist
 
     from .dist import TorchComm
@@ -172,7 +185,7 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     chans, _ = _native.shard_layout(nsub, nchan, world)
     try:
         with _native.ShardSession(nsub, nchan, nbin, rank, world, comm=comm, device=_device_index(device),
-                                  delay=args.get("delay"), **_loop_kwargs(args, (nsub, nchan))) as s:
+                                  delay=args.get("delay"), **_loop_kwargs(args, (nsub, nchan), nbin)) as s:
             if np.ndim(cube_slice) == 4:   # full-pol: pscrunched on the GPU
                 s.upload_pols(cube_slice, w0_slice, shift_slice)
             else:
@@ -200,6 +213,8 @@ def _merge_dist(out, res, chans, shape, comm, group, want_residual):
     scalars = {k: out[k] for k in ("loops", "n_iter", "converged")}
     scalars.update(changed=list(map(int, out["changed"])), nzero=list(map(int, out["nzero"])),
                    bad_fits=list(map(int, out.get("bad_fits", []))))
+    if "std_alignment" in out:
+        scalars["std_alignment"] = out["std_alignment"]
     every = [None] * world
     dist.all_gather_object(every, scalars, group=group)
     for r, sc in enumerate(every[1:], 1):

@@ -667,6 +667,50 @@ int ic_get_std_alignment(void *session, int32_t *aligned, int32_t *lag, double *
 int ic_align_template(int device, int nbin, const float *S, const float *A, int align, float *out, int32_t *aligned,
                       int32_t *lag, double *shift);
 
+/* Opt-in hot-bin repair (iterative_cleaner_amd/hotbins.py is the written
+ * definition; k_hotbins follows it bit for bit).  Before the loop reads an
+ * uploaded cube, every profile's off-pulse bins are clipped against their
+ * median and MAD (up to `rounds` rounds) and the few bins that stand out are
+ * set to the median of the bins that stay, so that an impulsive interferer in
+ * two or three bins no longer costs the whole profile.  The on-pulse window
+ * [on_start, on_end) is given in the dedispersed frame (0 <= on_start < nbin,
+ * 0 <= on_end <= nbin; on_end <= on_start wraps; its length is (on_end -
+ * on_start) mod nbin, so equal ends, and also (0, nbin), mean no window, never
+ * the whole profile); a
+ * stored bin j of channel c is on-pulse iff (j - o) mod nbin lies in it, o =
+ * shift[c], 0 with input_dedispersed, or rint(delay) mod nbin with fractional
+ * delays (the window then one bin wider on each side).  Fewer than 8 off-pulse
+ * bins are refused.  Profiles with w0 == 0 or a non-finite off-pulse sample are
+ * left alone (count 0); a profile with more than |O| / 4 hot bins is left to
+ * the surgical cleaner (count -1).  On-pulse bins are neither read nor written.
+ * ic_set_hotbins: threshold (finite, > 0; in scaled MADs) switches it on for
+ * the uploads consumed from here on, threshold <= 0 switches it off (the other
+ * arguments are then ignored); rounds 1..8.  Switched on after a run has
+ * already read the current upload, it leaves that upload alone and starts with
+ * the next one.  It changes arithmetic, so it is
+ * no ic_set_option option.  Off, a session launches and computes exactly what
+ * it did without it.  The pass runs once per upload, on the session stream at
+ * the start of the first ic_run that consumes it; a later ic_run of the same
+ * upload reads the repaired cube and keeps the counts and the list.  Channel
+ * shards treat their own slices; nothing is exchanged.
+ * ic_get_hotbins: count [P] (bins repaired, 0, or -1 = over the cap) and / or
+ * total (the sum of the positive counts); either may be NULL.
+ * ic_get_hotbin_list: the repaired bins in CSR layout: the positive counts are
+ * the row lengths, profiles ascending, bins ascending within a profile.
+ * Both: IC_ESTATE while the feature is off or before a run consumed an upload
+ * with it on; the list: IC_EINVAL if cap < total.
+ * ic_hotbins_profiles: a one-shot of the same kernels on nprof profiles: in
+ * [nprof][nbin], w [nprof], offsets [nprof] (o of each profile, any integer;
+ * NULL = 0), widen 0 / 1; out [nprof][nbin] (may be NULL), count [nprof], bins
+ * [cap] (may be NULL with cap 0), *total always written; IC_EINVAL if bins is
+ * given and cap < total (out and count are then still valid). */
+int ic_set_hotbins(void *session, double threshold, int on_start, int on_end, int rounds);
+int ic_get_hotbins(void *session, int32_t *count, int64_t *total);
+int ic_get_hotbin_list(void *session, int32_t *bins, int64_t cap);
+int ic_hotbins_profiles(int device, int nprof, int nbin, const float *in, const float *w, const int32_t *offsets,
+                        int widen, double threshold, int on_start, int on_end, int rounds, float *out,
+                        int32_t *count, int32_t *bins, int64_t cap, int64_t *total);
+
 /* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
  * SURVEY.md §8(e)).  The reference cleans an archive in one process

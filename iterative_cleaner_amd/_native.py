@@ -31,7 +31,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_rotate_profiles_any", "ic_get_residual_quantised_async", "ic_residual_wait",
            "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend",
            "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces",
-           "ic_shard_enable_detrend", "ic_set_std_template", "ic_get_std_alignment", "ic_align_template")
+           "ic_shard_enable_detrend", "ic_set_std_template", "ic_get_std_alignment", "ic_align_template",
+           "ic_set_hotbins", "ic_get_hotbins", "ic_get_hotbin_list", "ic_hotbins_profiles")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -192,6 +193,11 @@ def load_library(path: str = LIB_PATH):
     lib.ic_set_std_template.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.ic_get_std_alignment.argtypes = [vp, vp, vp, vp]
     lib.ic_align_template.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ic_set_hotbins.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.ic_get_hotbins.argtypes = [vp, vp, C.POINTER(C.c_int64)]
+    lib.ic_get_hotbin_list.argtypes = [vp, vp, C.c_int64]
+    lib.ic_hotbins_profiles.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int,
+                                        C.c_int, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.ic_comprehensive_stats_detrend_pieces.argtypes = (list(lib.ic_comprehensive_stats_detrend.argtypes)
                                                           + [C.c_int, vp, C.c_int, vp])
     if lib.ic_abi_version() != ABI_VERSION:
@@ -242,7 +248,7 @@ class GpuSession:
     def __init__(self, nsub, nchan, nbin, max_iter=5, chanthresh=5.0, subintthresh=5.0,
                  pulse_region=(0, 0, 1), baseline_duty=0.15, device=0, fit_mode=FIT_EXACT, data_f64=False,
                  delay=None, options=None, input_dedispersed=False, dedisp_fft=False, any_length=None,
-                 detrend=None, detrend_pieces=None, std_template=None):
+                 detrend=None, detrend_pieces=None, std_template=None, hotbins=None):
         """delay: the session dedisperses by the FFT phase rotation (IC_DEDISP_FFT)
         with these delays (set_delays).  dedisp_fft=True: the same mode without
         delays yet: they come with set_delays, or with each archive
@@ -256,7 +262,10 @@ class GpuSession:
         (set_detrend_pieces); None: ic_set_detrend_pieces is never called.
         std_template = the standard profile (nbin,) or (profile, align): the
         opt-in cleaning against a supplied template (set_std_template;
-        std_template.py); None: ic_set_std_template is never called."""
+        std_template.py); None: ic_set_std_template is never called.
+        hotbins = (threshold, on_start, on_end[, rounds]): the opt-in hot-bin
+        repair (set_hotbins; hotbins.py); None: ic_set_hotbins is never called
+        (a session reads no environment switch: run_loop and clean_batch do)."""
         from .phase_rotation import any_length_enabled
         fft_mode = DEDISP_FFT_ANY if (any_length_enabled() if any_length is None else any_length) else DEDISP_FFT
         self.lib = load_library()
@@ -276,6 +285,7 @@ class GpuSession:
         self.h = h
         self.pieces = None   # (mc, ms) while pieces are set
         self.std_mode = None   # IC_ALIGN_* while a standard template is set
+        self.hotbins_on = False   # while the hot-bin repair is set
         try:
             for name, value in (options or {}).items():
                 self.set_option(name, value)
@@ -287,6 +297,8 @@ class GpuSession:
                 self.set_detrend_pieces(*detrend_pieces)
             if std_template is not None:
                 self.set_std_template(*_std_pair(std_template))
+            if hotbins is not None:
+                self.set_hotbins(*hotbins)
         except Exception:
             self.close()   # no half-made session is left for the collector (a shard's must go before its group)
             raise
@@ -334,6 +346,37 @@ class GpuSession:
         self._check(self.lib.ic_get_std_alignment(self.h, C.byref(al), C.byref(lag), C.byref(sh)),
                     "ic_get_std_alignment")
         return dict(aligned=int(al.value), lag=int(lag.value), shift=float(sh.value))
+
+    def set_hotbins(self, threshold, on_start=0, on_end=0, rounds=4):
+        """Hot-bin repair for the uploads consumed from here on (ic_set_hotbins;
+        the definition is hotbins.py): the off-pulse bins of every profile more
+        than `threshold` scaled MADs from their median are set to the median of
+        the rest, once per upload, before the loop reads the cube.  The on-pulse
+        window [on_start, on_end) is in the dedispersed frame (on_end <=
+        on_start wraps; equal: none).  threshold <= 0 switches it off.  run()
+        then carries ``hotbins`` = dict(count, total, offsets, bins)."""
+        self._check(self.lib.ic_set_hotbins(self.h, float(threshold), int(on_start), int(on_end), int(rounds)),
+                    "ic_set_hotbins")
+        self.hotbins_on = float(threshold) > 0
+
+    def clear_hotbins(self):
+        """Switch the hot-bin repair off (ic_set_hotbins with threshold 0)."""
+        self.set_hotbins(0.0)
+
+    def hotbins(self):
+        """The repair of the upload the last run() consumed (ic_get_hotbins,
+        ic_get_hotbin_list): dict(count int32 (nsub, nchan): bins repaired, 0, or
+        -1 = more than a quarter of the off-pulse bins stood out and the profile
+        was left alone; total; offsets int64 [P + 1] and bins int32 [total]: the
+        repaired bins in CSR layout, profiles in (s, c) order, bins ascending)."""
+        from .hotbins import result_dict
+        nsub, nchan, _ = self.shape
+        count = np.empty((nsub, nchan), np.int32)
+        total = C.c_int64()
+        self._check(self.lib.ic_get_hotbins(self.h, _ptr(count), C.byref(total)), "ic_get_hotbins")
+        bins = np.empty(int(total.value), np.int32)
+        self._check(self.lib.ic_get_hotbin_list(self.h, _ptr(bins), int(total.value)), "ic_get_hotbin_list")
+        return result_dict(count, bins)
 
     def set_detrend(self, chan_order, subint_order, rounds=4, clip=5.0):
         """Detrended scaling for the runs that follow (ic_set_detrend; the
@@ -526,6 +569,13 @@ class GpuSession:
                    bad_fits=bad[:k].copy())
         if self.std_mode is not None and k > 0:
             out["std_alignment"] = self.std_alignment()
+        if self.hotbins_on:
+            # (IC_ESTATE: switched on after a run had read this upload, which is
+            # then left alone; the next upload gets the pass)
+            rc = self.lib.ic_get_hotbins(self.h, None, None)
+            if rc != -4:
+                self._check(rc, "ic_get_hotbins")
+                out["hotbins"] = self.hotbins()
         return out
 
     def residual(self):
@@ -664,6 +714,33 @@ def align_template(S, A, align="auto", device=0):
     if rc != 0:
         raise NativeError("ic_align_template: %s (rc=%d)" % (_err(lib), rc))
     return dict(aligned=int(al.value), lag=int(lag.value), shift=float(sh.value), template=out, mode=mode)
+
+
+def hotbins_profiles(profiles, w, offsets, widen, threshold, on_start, on_end, rounds=4, device=0):
+    """The hot-bin kernels alone (ic_hotbins_profiles) on (nprof, nbin) f32
+    profiles with weights w (nprof,) and offsets (nprof,) int32 (None: 0), as
+    hotbins.repair_profiles states them: (out, count int32, bins int32 CSR)."""
+    lib = load_library()
+    p = np.ascontiguousarray(profiles, dtype=np.float32)
+    if p.ndim != 2:
+        raise ValueError("hotbins_profiles: profiles must be (nprof, nbin)")
+    nprof, nbin = p.shape
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(nprof)
+    off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int32).reshape(nprof)
+    out = np.empty_like(p)
+    count = np.empty(nprof, np.int32)
+    total = C.c_int64()
+    args = [int(device), nprof, nbin, _ptr(p), _ptr(w), _ptr(off), 1 if widen else 0, float(threshold),
+            int(on_start), int(on_end), int(rounds), _ptr(out), _ptr(count)]
+    rc = lib.ic_hotbins_profiles(*args, None, 0, C.byref(total))
+    if rc != 0:
+        raise NativeError("ic_hotbins_profiles: %s (rc=%d)" % (_err(lib), rc))
+    bins = np.empty(int(total.value), np.int32)
+    if total.value:
+        rc = lib.ic_hotbins_profiles(*args, _ptr(bins), int(total.value), C.byref(total))
+        if rc != 0:
+            raise NativeError("ic_hotbins_profiles: %s (rc=%d)" % (_err(lib), rc))
+    return out, count, bins
 
 
 def fit_profiles(profiles, template, fit_mode=FIT_EXACT, device=0):

@@ -106,7 +106,7 @@ class _ResidualQueue:
 
 
 def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, detrend_pieces=None,
-             std_template=None):
+             std_template=None, hotbins=None):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -139,7 +139,13 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, d
     or a pair with the align mode), set once before the first run and aligned
     against each archive; every dict then holds out["std_alignment"].  None
     leaves the session as it is (clean_batch and run_loop are where the
-    IC_STD_TEMPLATE switch is read)."""
+    IC_STD_TEMPLATE switch is read).  hotbins = (threshold, on_start, on_end[,
+    rounds]): the hot-bin repair (GpuSession.set_hotbins; hotbins.py), set
+    before the first run; every archive gets its own pass when its upload is
+    consumed, and every dict then holds out["hotbins"].  None leaves the
+    session as it is (clean_batch and run_loop read the IC_HOTBINS switch)."""
+    if hotbins is not None:
+        session.set_hotbins(*hotbins)
     if std_template is not None:
         from .std_template import normalise
         session.set_std_template(*normalise(std_template, session.shape[2]))
@@ -179,7 +185,7 @@ _EXITED = -2   # a worker's last message (run_lanes)
 
 
 def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1, residuals=None,
-              std_template=None):
+              std_template=None, hotbins=None):
     """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
     each with or without trailing delays, as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
@@ -192,7 +198,7 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
     lane, valid until the generator is advanced past it - a lane takes a slot
     again only after the consumer has moved on from the result that held it.
 
-    std_template: `pipeline`'s, set on every session before the first run.
+    std_template, hotbins: `pipeline`'s, set on every session before the first run.
 
     On a worker error, or when the consumer stops early (generator closed), the
     lanes stop: the `stop` event (created here if not given) is set, queued work
@@ -210,6 +216,9 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
         from .std_template import normalise
         for sess in sessions:
             sess.set_std_template(*normalise(std_template, sess.shape[2]))
+    if hotbins is not None:
+        for sess in sessions:
+            sess.set_hotbins(*hotbins)
     if len(sessions) == 1:
         yield from pipeline(sessions[0], items, fetch, nsum, None if residuals is None else residuals[0])
         return
@@ -422,7 +431,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
                 any_length=None, residuals=False, residual_big_endian=True, detrend=None,
-                detrend_pieces=None, std_template=None):
+                detrend_pieces=None, std_template=None, hotbins=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -470,8 +479,15 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     the align mode): every archive is cleaned against this standard profile
     (std_template.py), set once on every lane's session and aligned against
     each archive; out["std_alignment"] is per archive, and a failed alignment
-    warns on stderr.  None reads the IC_STD_TEMPLATE switch."""
+    warns on stderr.  None reads the IC_STD_TEMPLATE switch.
+    hotbins = (threshold, on_start, on_end[, rounds]): the opt-in hot-bin
+    repair (hotbins.py) on every lane's session: each archive's off-pulse hot
+    bins are repaired before it is cleaned, and out["hotbins"] = dict(count,
+    total, offsets, bins) is per archive.  None reads the IC_HOTBINS switch
+    ("thr,start,end[,rounds]"; unset, empty or 0: off)."""
+    from . import hotbins as hbm
     from . import std_template as stdt
+    hot = hbm.normalise(hotbins)
     from .detrend import normalise, normalise_pieces
     detrend = normalise(detrend)
     detrend_pieces = normalise_pieces(detrend_pieces, int(shape[0]), int(shape[1]), detrend)
@@ -592,7 +608,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                                                pulse_region, baseline_duty, device=device, fit_mode=fit_mode,
                                                options=options, input_dedispersed=input_dedispersed,
                                                dedisp_fft=fft, any_length=any_length, detrend=detrend,
-                                               detrend_pieces=detrend_pieces, std_template=std))
+                                               detrend_pieces=detrend_pieces, std_template=std, hotbins=hot))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
                               residuals=[rr.triples() for rr in result_rings] if residuals else None)
         for k, out in enumerate(lanes_gen):

@@ -208,7 +208,7 @@ def _device() -> int:
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
              data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
-             detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None):
+             detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -239,8 +239,18 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     one of "auto", "none", "int", "frac"; None reads the switch
     IC_STD_TEMPLATE="<path>[,<align>]" (unset or empty: off).  The result then
     holds ``std_alignment`` = dict(aligned, lag, shift); a failed alignment
-    warns once on stderr."""
+    warns once on stderr.  ``hotbins`` = (threshold, on_start, on_end[,
+    rounds]): the opt-in hot-bin repair (hotbins.py): the off-pulse bins of a
+    profile that stand out by more than ``threshold`` scaled MADs are set to the
+    median of the rest before the loop reads the cube; the on-pulse window is in
+    the dedispersed frame.  None reads the switch
+    IC_HOTBINS="thr,start,end[,rounds]" (unset, empty or 0: off).  The result
+    then holds ``hotbins`` = dict(count, total, offsets, bins); under channel
+    sharding every rank repairs its own channels and the dict is the whole
+    archive's."""
+    from . import hotbins as hbm
     from . import std_template as stdt
+    hot = hbm.normalise(hotbins)
     from .detrend import normalise, normalise_pieces, shards_enabled
     from .dist import channel_sharding
     detrend = normalise(detrend)
@@ -280,6 +290,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
             max_iter=args.max_iter, chanthresh=args.chanthresh, subintthresh=args.subintthresh,
             pulse_region=args.pulse_region, baseline_duty=baseline_duty, data_f64=data_f64, delay=delay,
             input_dedispersed=input_dedispersed, **({} if std is None else dict(std_template=std)),
+            **({} if hot is None else dict(hotbins=hot)),
             **(dict(detrend=detrend, detrend_pieces=detrend_pieces, shard_detrend=True) if detrend is not None else {}))
         if rank == 0 and std is not None:
             stdt.warn_failed(out.get("std_alignment"), std[1])
@@ -290,7 +301,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
                             args.pulse_region, baseline_duty,
                             device=_device() if device is None else device, data_f64=data_f64, delay=delay,
                             input_dedispersed=input_dedispersed, detrend=detrend,
-                            detrend_pieces=detrend_pieces, std_template=std) as s:
+                            detrend_pieces=detrend_pieces, std_template=std, hotbins=hot) as s:
         if quantised is not None:
             s.upload_quantised(quantised[0], quantised[1], quantised[2], w0, shift, quantised[3])
         elif pols:
@@ -354,11 +365,12 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None):
+def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None):
     """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend,
-    detrend_pieces, detrend_shards, std_template: run_loop's (None = the
-    IC_DETREND / IC_DETREND_PIECES / IC_DETREND_SHARDS / IC_STD_TEMPLATE
-    switches; there is no CLI flag).  Under
+    detrend_pieces, detrend_shards, std_template, hotbins: run_loop's (None = the
+    IC_DETREND / IC_DETREND_PIECES / IC_DETREND_SHARDS / IC_STD_TEMPLATE /
+    IC_HOTBINS switches; there is no CLI flag).  With hotbins the output archive
+    is patched at the repaired bins (_patch_hotbins).  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -407,7 +419,7 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
                    residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces,
-                   detrend_shards=detrend_shards, std_template=std_template)
+                   detrend_shards=detrend_shards, std_template=std_template, hotbins=hotbins)
     del cube
 
     x = 0
@@ -450,6 +462,8 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
         shift, delay = _dedispersion(ar)
     elif not args.pscrunch and not args.memory:
         ar = backend.Archive_load(arch)
+    if out.get("hotbins") is not None and out["hotbins"]["total"] > 0:
+        _patch_hotbins(ar, out["hotbins"], hotbins, shift, delay, stored_ded)
     set_weights_archive(ar, avg_test_results)
     if args.bad_chan != 1 or args.bad_subint != 1:
         ar = find_bad_parts(ar, args)
@@ -466,6 +480,34 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
             fh.write("\n %s: Cleaned %s with %s, required loops=%s"
                      % (datetime.datetime.now(), ar_name, args, loops))
     return ar
+
+
+def _patch_hotbins(ar, result, hotbins, shift, delay, stored_ded):
+    """The output archive gets the repair the loop's cube got: every profile of
+    the hit list is patched on the host, sparsely, through the writable
+    amplitudes of its Profile objects.  For each polarisation the listed bins
+    take that polarisation's own median over the profile's surviving off-pulse
+    bins (hotbins.patch_amps), so a pscrunched archive (-p) equals what the GPU
+    repaired and a full-polarisation one is repaired polarisation by
+    polarisation at the same bins.  The list is in the frame the loop saw: the
+    stored frame, or, for an archive stored dedispersed with integer shifts,
+    the dispersed frame the host rolled it to (raw[j] = stored[(j - shift) %
+    nbin]: its bins are moved back here).  Handing out the amplitudes marks the
+    archive changed, so PSRFITS re-quantises the patched profiles on unload."""
+    from . import hotbins as hbm
+    thr, a, b, _ = hbm.normalise(hotbins)
+    nsub, nchan, nbin, npol = ar.get_nsubint(), ar.get_nchan(), ar.get_nbin(), ar.get_npol()
+    rolled = stored_ded and delay is None
+    offs, widen = hbm.profile_offsets(nsub, nchan, nbin, shift, delay, stored_ded and delay is not None)
+    start, length = hbm.check_window(nbin, a, b, widen)
+    count, rows, bins = np.asarray(result["count"]), np.asarray(result["offsets"]), np.asarray(result["bins"])
+    for s_, c_ in np.argwhere(count > 0):
+        k = int(s_) * nchan + int(c_)
+        hot, o = bins[rows[k]:rows[k + 1]].astype(np.int64), int(offs[s_, c_])
+        if rolled:
+            hot, o = (hot - o) % nbin, 0
+        for p_ in range(npol):
+            hbm.patch_amps(ar.get_Profile(int(s_), p_, int(c_)).get_amps(), hot, o, start, length)
 
 
 def _residual_archive(ar, residual, weights, shift, backend, delay=None):

@@ -1,6 +1,7 @@
 // ic_internal.h — shared declarations between the host session (ic_session.hip)
 // and the gfx950 kernel units (ic_template.hip, ic_codec.hip, ic_fit.hip,
-// ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip, ic_stdtemplate.hip).
+// ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip, ic_stdtemplate.hip,
+// ic_hotbins.hip).
 // Not part of the public C-ABI.
 #pragma once
 #include <hip/hip_ext.h>
@@ -113,6 +114,8 @@ enum KernelId {
     K_RESIDUAL_Q,     // the residual formed and encoded to int16 in one pass
     K_STD_ALIGN,      // standard template: k_std_ccf and k_std_peak
     K_STD_INSTALL,    // standard template: k_std_install
+    K_HOTBINS,        // hot-bin repair: k_hotbins
+    K_HOTBIN_SCAN,    // ... and the row starts of its hit list: k_hotbin_scan
     K_COUNT
 };
 
@@ -700,5 +703,43 @@ hipError_t launch_std_peak(hipStream_t st, const double *c, int nbin, StdAlignRe
 // rotated standard, when rec->aligned, else S (kAlignFrac)
 hipError_t launch_std_install(hipStream_t st, const float *S, const float *R, const StdAlignRec *rec, int mode,
                               int nbin, int ldD, float *T, double *T64, double *T2, int grid_cap = 0);
+
+// Hot-bin repair (ic_set_hotbins; hotbins.py): the off-pulse bins of every
+// profile are clipped against their median and MAD and the few that stand out
+// are set to the survivors' median, in place (ic_hotbins.hip).  A stored bin j
+// of profile k is on-pulse iff ((j - o_k) mod nbin - win_start) mod nbin <
+// win_len, win_* the window already widened and clamped (win_len 0: none).
+// o_k comes from one of: off32 (int32, any value), offd (f64, rint'ed), or 0;
+// per_profile 0: indexed by the channel k % nchan, 1: by k.
+constexpr int kHotMaxBin = 8192;      // one block of 8 waves holds 16 samples per lane
+constexpr int kHotMinOff = 8;         // fewer off-pulse bins are refused
+constexpr int kHotMaxRounds = 8;
+struct HotBinArgs {
+    float *cube;                // [P][nbin], repaired in place
+    const float *w0;            // [P]
+    const int32_t *off32;
+    const double *offd;
+    int per_profile;
+    long P;
+    int nchan, nbin;
+    int win_start, win_len;
+    double threshold;
+    int rounds;
+    int32_t *count;             // [P]: bins repaired, 0, or -1 (over the cap)
+    uint32_t *mask;             // [P][mask_words(nbin)]: bit j of a profile's words = bin j repaired
+    int grid_cap;
+};
+inline int hot_mask_words(int nbin) { return (nbin + 31) / 32; }
+// detect and repair: count and mask written for every profile
+hipError_t launch_hotbins(hipStream_t st, const HotBinArgs &a);
+// the hit list from count and mask (a mask row is defined only where count >
+// 0): offs[k] = the sum of the positive counts before k, *total their sum (part:
+// hotbin_scan_parts(P) words of scratch, a block's sum each); then
+// bins[offs[k] ..) = the set bits of profile k, ascending, the entries below cap
+size_t hotbin_scan_parts(long P);
+hipError_t launch_hotbin_scan(hipStream_t st, const int32_t *count, long P, int64_t *part, int64_t *offs,
+                              int64_t *total);
+hipError_t launch_hotbin_fill(hipStream_t st, const int32_t *count, const uint32_t *mask, const int64_t *offs, long P,
+                              int nbin, int32_t *bins, int64_t cap, int grid_cap = 0);
 
 }  // namespace icgpu

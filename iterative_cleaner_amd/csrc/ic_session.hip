@@ -143,7 +143,7 @@ const char *kKernelNames[K_COUNT] = {"k_chan_partials", "k_window",    "k_base",
                                      "k_diag",          "k_linestats", "k_combine",  "k_residual",
                                      "k_fit_tail",      "k_sb_tree",   "k_shard_pack", "exchange",
                                      "k_tnorm",         "k_rotate",    "k_residual_q", "k_std_align",
-                                     "k_std_install"};
+                                     "k_std_install",   "k_hotbins",   "k_hotbin_scan"};
 
 constexpr long kTailProfiles = 8192;  // default: hand the remaining profiles to k_fit_tail below this
 constexpr long kTailProfilesLarge = 4096;   // the same for sessions of >= 2^20 profiles
@@ -283,6 +283,19 @@ struct Session {
     float *std_S = nullptr, *std_rot = nullptr;
     double *std_c = nullptr;
     StdAlignRec *std_rec = nullptr;
+    // hot-bin repair (ic_set_hotbins; hotbins.py): hb_on queues k_hotbins at the
+    // start of the first ic_run after an upload, before anything reads the cube
+    // (hb_done: this upload has had its pass; hb_have: the counts, masks and row
+    // starts below are this upload's).  hb_count [P], hb_mask [P][words], hb_offs
+    // [P], hb_total [1], then the scan's block sums: from `mem` at the first pass, kept.
+    // The profiles' offsets come from shift, or from the session's own delays:
+    // delay2, or the channel row in dly while delay2 is null
+    bool hb_on = false, hb_done = false, hb_have = false;
+    double hb_thr = 0.0;
+    int hb_start = 0, hb_end = 0, hb_rounds = 4;
+    int32_t *hb_count = nullptr;
+    uint32_t *hb_mask = nullptr;
+    int64_t *hb_offs = nullptr, *hb_total = nullptr;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -345,7 +358,7 @@ struct Session {
     // from them on the copy stream (slot_ph; slot_dmode 1) or nothing more
     // (per profile; 2).  0: the slot's upload carries no delays.  Buffers at
     // first need.  The ic_run that consumes the upload exchanges the slot's
-    // buffer with the session's (ph or dly): the delays stay the session's own
+    // buffers with the session's (ph and dly, or dly): the delays stay the session's own
     // when a later upload, attached or not, reuses the slot.
     float *slot_ph[2] = {nullptr, nullptr};
     double *slot_dly[2] = {nullptr, nullptr};
@@ -1755,6 +1768,7 @@ static int finish_upload(Session *s)
     CK(hipStreamSynchronize(s->stream));
     s->uploaded = true;
     s->ran = false;
+    s->hb_done = s->hb_have = false;
     return IC_OK;
 }
 
@@ -2120,6 +2134,72 @@ PieceArgs piece_args(const std::vector<int32_t> &cs, const std::vector<int32_t> 
     return PieceArgs{(int)cs.size(), (int)ss.size(), starts, starts + cs.size() + 1, piece, piece + nsub};
 }
 
+// ---- hot-bin repair (ic_set_hotbins; hotbins.py) ----
+// the on-pulse window in the kernels' form: (start, length), widened by one bin
+// on each side for fractional delays (never from nothing, never beyond nbin)
+void hot_window(int nbin, int on_start, int on_end, bool widen, int *start, int *len)
+{
+    int L = ((on_end - on_start) % nbin + nbin) % nbin, st = on_start;
+    if (widen && L > 0) {
+        st = (st + nbin - 1) % nbin;
+        L = L + 2 < nbin ? L + 2 : nbin;
+    }
+    *start = st;
+    *len = L;
+}
+// the ranges of ic_set_hotbins / ic_hotbins_profiles; 0 or the message
+const char *hotbins_range(int nbin, double threshold, int on_start, int on_end, int rounds, bool widen)
+{
+    if (!(std::isfinite(threshold) && threshold > 0.0)) return "threshold must be finite and > 0";
+    if (rounds < 1 || rounds > kHotMaxRounds) return "rounds outside 1..8";
+    if (nbin > kHotMaxBin) return "nbin above 8192";
+    if (on_start < 0 || on_start >= nbin) return "on_start outside [0, nbin)";
+    if (on_end < 0 || on_end > nbin) return "on_end outside [0, nbin]";
+    int ws = 0, wl = 0;
+    hot_window(nbin, on_start, on_end, widen, &ws, &wl);
+    if (nbin - wl < kHotMinOff) return "fewer than 8 off-pulse bins";
+    return nullptr;
+}
+// fractional delays move the pulse by their rounded value and widen the window
+bool hot_widen(const Session *s) { return s->fftded && !s->p.input_dedispersed; }
+
+// the upload's one pass: detect and repair in place, then the rows' starts
+int hotbins_stage(Session *s)
+{
+    const int nbin = s->p.nbin;
+    const size_t words = (size_t)hot_mask_words(nbin);
+    if (s->mem.ensure(&s->hb_count, s->P) != hipSuccess || s->mem.ensure(&s->hb_mask, s->P * words) != hipSuccess ||
+        s->mem.ensure(&s->hb_offs, s->P) != hipSuccess ||
+        s->mem.ensure(&s->hb_total, 1 + hotbin_scan_parts((long)s->P)) != hipSuccess)
+        return fail(IC_ENOMEM, "hipMalloc(hot-bin counts and masks: %zu bytes) failed",
+                    s->P * (12 + 4 * words));
+    HotBinArgs a{};
+    a.cube = s->raw;
+    a.w0 = s->w0;
+    const bool frac = hot_widen(s);
+    if (frac) {
+        a.offd = s->delay2 ? s->delay2 : s->dly;
+        a.per_profile = s->delay2 ? 1 : 0;
+        if (!a.offd) return fail(IC_ESTATE, "hot-bin repair: the session has no delays");
+    } else if (!s->fftded) {
+        a.off32 = s->shift;
+    }
+    a.P = (long)s->P;
+    a.nchan = s->nchan;
+    a.nbin = nbin;
+    hot_window(nbin, s->hb_start, s->hb_end, frac, &a.win_start, &a.win_len);
+    a.threshold = s->hb_thr;
+    a.rounds = s->hb_rounds;
+    a.count = s->hb_count;
+    a.mask = s->hb_mask;
+    a.grid_cap = s->grid_cap;
+    LAUNCH(s, K_HOTBINS, launch_hotbins(s->stream, a));
+    LAUNCH(s, K_HOTBIN_SCAN, launch_hotbin_scan(s->stream, s->hb_count, (long)s->P, s->hb_total + 1, s->hb_offs,
+                                                s->hb_total));
+    s->hb_done = s->hb_have = true;
+    return IC_OK;
+}
+
 int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_out, int32_t *changed_out,
              int32_t *nzero_out, int32_t *n_iter_out, int32_t *converged_out)
 {
@@ -2135,10 +2215,16 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
         s->shift = s->slot_shift[slot];
         s->uploaded = true;
         s->ran = false;
+        s->hb_done = s->hb_have = false;
         // delays that came with the upload become the session's (slot_ev
         // follows their copy and the table kernel)
         if (s->slot_dmode[slot] == 1) {
             std::swap(s->ph, s->slot_ph[slot]);
+            // ... and the channel row they were built from (the hot-bin pass
+            // reads it for the profiles' offsets): the slot keeps the session's
+            // old buffer, so a later upload into the slot overwrites nothing
+            // the session still reads
+            std::swap(s->dly, s->slot_dly[slot]);
             s->delay2 = nullptr;   // a per-channel archive after a per-profile one
         } else if (s->slot_dmode[slot] == 2) {
             std::swap(s->dly, s->slot_dly[slot]);
@@ -2164,6 +2250,8 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     int pr_end = p.pr_end < 0 ? 0 : (p.pr_end > nbin ? nbin : p.pr_end);
     // fit cube (ic.py:96-100) + initial weights/history; a session can be re-run
     s->stats = ic_run_stats{};
+    if (s->hb_on && !s->hb_done)
+        if (int rc = hotbins_stage(s)) return rc;
     if (int rc = prepare(s)) return rc;
     LineStatsArgs la;
     la.nsub = nsub;
@@ -3121,6 +3209,134 @@ int ic_align_template(int device, int nbin, const float *S, const float *A, int 
     if (aligned) *aligned = r.aligned;
     if (lag) *lag = r.lag;
     if (shift) *shift = r.shift;
+    return IC_OK;
+}
+
+int ic_set_hotbins(void *session, double threshold, int on_start, int on_end, int rounds)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (threshold <= 0.0) {   // off: the session launches what it did before
+        s->hb_on = false;
+        return IC_OK;
+    }
+    if (const char *e = hotbins_range(s->p.nbin, threshold, on_start, on_end, rounds, hot_widen(s)))
+        return fail(IC_EINVAL, "ic_set_hotbins(%g, %d, %d, %d) at nbin=%d: %s", threshold, on_start, on_end, rounds,
+                    s->p.nbin, e);
+    // "the uploads consumed from here on": an upload that a run has already
+    // read while the option was off keeps its cube as it is
+    if (!s->hb_on && s->ran) s->hb_done = true;
+    s->hb_on = true;
+    s->hb_thr = threshold;
+    s->hb_start = on_start;
+    s->hb_end = on_end;
+    s->hb_rounds = rounds;
+    return IC_OK;
+}
+
+static int hotbins_state(const Session *s, const char *name)
+{
+    if (!s->hb_on) return fail(IC_ESTATE, "%s: hot-bin repair is off (ic_set_hotbins)", name);
+    if (!s->hb_have) return fail(IC_ESTATE, "%s: no run has consumed an upload with hot-bin repair on", name);
+    return IC_OK;
+}
+
+int ic_get_hotbins(void *session, int32_t *count, int64_t *total)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (int rc = hotbins_state(s, "ic_get_hotbins")) return rc;
+    CK(hipSetDevice(s->device));
+    if (count) CK(hipMemcpyAsync(count, s->hb_count, sizeof(int32_t) * s->P, hipMemcpyDeviceToHost, s->stream));
+    if (total) CK(hipMemcpyAsync(total, s->hb_total, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    return IC_OK;
+}
+
+int ic_get_hotbin_list(void *session, int32_t *bins, int64_t cap)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (int rc = hotbins_state(s, "ic_get_hotbin_list")) return rc;
+    CK(hipSetDevice(s->device));
+    int64_t total = 0;
+    CK(hipMemcpyAsync(&total, s->hb_total, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    if (cap < total) return fail(IC_EINVAL, "ic_get_hotbin_list: cap=%lld below the list's %lld entries",
+                                 (long long)cap, (long long)total);
+    if (total == 0) return IC_OK;
+    if (!bins) return fail(IC_EINVAL, "ic_get_hotbin_list: null bins");
+    const auto bad = [](hipError_t e) { return named_fail("ic_get_hotbin_list", e, true); };
+    Scratch tmp;
+    int32_t *d = nullptr;
+    CKF(tmp.mem.alloc_exact(&d, (size_t)total), bad);
+    CKF(launch_hotbin_fill(s->stream, s->hb_count, s->hb_mask, s->hb_offs, (long)s->P, s->p.nbin, d, total,
+                           s->grid_cap), bad);
+    CKF(hipMemcpyAsync(bins, d, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s->stream), bad);
+    CKF(hipStreamSynchronize(s->stream), bad);   // before tmp frees d
+    return IC_OK;
+}
+
+int ic_hotbins_profiles(int device, int nprof, int nbin, const float *in, const float *w, const int32_t *offsets,
+                        int widen, double threshold, int on_start, int on_end, int rounds, float *out,
+                        int32_t *count, int32_t *bins, int64_t cap, int64_t *total)
+{
+    if (!in || !w || !count || !total) return fail(IC_EINVAL, "null argument");
+    if (nprof <= 0 || nbin <= 0) return fail(IC_EINVAL, "bad shape nprof=%d nbin=%d", nprof, nbin);
+    if (widen != 0 && widen != 1) return fail(IC_EINVAL, "widen=%d (0 or 1)", widen);
+    if (cap < 0 || (bins == nullptr && cap != 0)) return fail(IC_EINVAL, "cap=%lld with%s bins", (long long)cap,
+                                                              bins ? "" : " null");
+    if (const char *e = hotbins_range(nbin, threshold, on_start, on_end, rounds, widen != 0))
+        return fail(IC_EINVAL, "ic_hotbins_profiles(%g, %d, %d, %d) at nbin=%d: %s", threshold, on_start, on_end,
+                    rounds, nbin, e);
+    if (int rc = select_device(device)) return rc;
+    const size_t P = (size_t)nprof, N = P * nbin, words = (size_t)hot_mask_words(nbin);
+    const auto bad = [](hipError_t e) { return named_fail("ic_hotbins_profiles", e, true); };
+    Scratch sc;
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    HotBinArgs a{};
+    float *dw = nullptr;
+    int32_t *doff = nullptr, *dbins = nullptr;
+    int64_t *doffs = nullptr, *dtotal = nullptr;
+    CKF(sc.mem.alloc_exact(&a.cube, N), bad);
+    CKF(sc.mem.alloc_exact(&dw, P), bad);
+    CKF(sc.mem.alloc_exact(&a.count, P), bad);
+    CKF(sc.mem.alloc_exact(&a.mask, P * words), bad);
+    CKF(sc.mem.alloc_exact(&doffs, P), bad);
+    CKF(sc.mem.alloc_exact(&dtotal, 1 + hotbin_scan_parts((long)P)), bad);
+    CKF(hipMemcpyAsync(a.cube, in, sizeof(float) * N, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dw, w, sizeof(float) * P, hipMemcpyHostToDevice, st), bad);
+    if (offsets) {
+        CKF(sc.mem.alloc_exact(&doff, P), bad);
+        CKF(hipMemcpyAsync(doff, offsets, sizeof(int32_t) * P, hipMemcpyHostToDevice, st), bad);
+    }
+    a.w0 = dw;
+    a.off32 = doff;
+    a.per_profile = 1;
+    a.P = (long)P;
+    a.nchan = 1;
+    a.nbin = nbin;
+    hot_window(nbin, on_start, on_end, widen != 0, &a.win_start, &a.win_len);
+    a.threshold = threshold;
+    a.rounds = rounds;
+    CKF(launch_hotbins(st, a), bad);
+    CKF(launch_hotbin_scan(st, a.count, (long)P, dtotal + 1, doffs, dtotal), bad);
+    if (out) CKF(hipMemcpyAsync(out, a.cube, sizeof(float) * N, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipMemcpyAsync(count, a.count, sizeof(int32_t) * P, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipMemcpyAsync(total, dtotal, sizeof(int64_t), hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
+    if (!bins) return IC_OK;
+    if (cap < *total) return fail(IC_EINVAL, "ic_hotbins_profiles: cap=%lld below the list's %lld entries",
+                                  (long long)cap, (long long)*total);
+    if (*total == 0) return IC_OK;
+    CKF(sc.mem.alloc_exact(&dbins, (size_t)*total), bad);
+    CKF(launch_hotbin_fill(st, a.count, a.mask, doffs, (long)P, nbin, dbins, *total), bad);
+    CKF(hipMemcpyAsync(bins, dbins, sizeof(int32_t) * (size_t)*total, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
     return IC_OK;
 }
 

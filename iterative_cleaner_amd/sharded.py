@@ -30,7 +30,7 @@ def _gather_cols(parts, ranges, shape, dtype):
 # callers slice per rank themselves
 _LOOP_KEYS = ("max_iter", "chanthresh", "subintthresh", "pulse_region", "baseline_duty", "fit_mode", "data_f64",
               "options", "input_dedispersed", "any_length", "detrend", "detrend_pieces", "shard_detrend",
-              "std_template")
+              "std_template", "hotbins")
 
 
 def _loop_kwargs(args, global_shape=None, nbin=None):
@@ -40,7 +40,9 @@ def _loop_kwargs(args, global_shape=None, nbin=None):
     detrend_pieces are resolved once against the global (nsub, nchan), so every
     rank gets the same starts.  std_template (std_template.normalise's forms
     but None, which is off: run_loop is where the IC_STD_TEMPLATE switch is
-    read) is loaded and checked once per call, for the archive's nbin."""
+    read) is loaded and checked once per call, for the archive's nbin.
+    hotbins (hotbins.normalise's forms but None, which is off: run_loop reads
+    the IC_HOTBINS switch): the hot-bin repair, each rank on its own slice."""
     unknown = sorted(set(args) - set(_LOOP_KEYS) - {"delay"})
     if unknown:
         raise TypeError("unknown keyword(s) for a sharded clean: %s" % ", ".join(unknown))
@@ -53,6 +55,11 @@ def _loop_kwargs(args, global_shape=None, nbin=None):
     if args.get("std_template") is not None:
         from .std_template import normalise as std_normalise
         kw["std_template"] = std_normalise(args["std_template"], int(nbin))
+    if args.get("hotbins") is not None:
+        from .hotbins import normalise as hot_normalise
+        hot = hot_normalise(args["hotbins"])
+        if hot is not None:
+            kw["hotbins"] = hot
     shard_detrend = bool(args.get("shard_detrend", False))
     detrend, pieces = args.get("detrend"), args.get("detrend_pieces")
     if detrend is not None and not shard_detrend:
@@ -86,7 +93,10 @@ def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, f
     ``std_template`` (a profile, a path, or a pair with the align mode; None:
     off): the opt-in cleaning against a standard
     profile (std_template.py), the same on every shard; ``std_alignment`` is
-    every shard's (checked equal)."""
+    every shard's (checked equal).  ``hotbins`` = (threshold, on_start,
+    on_end[, rounds]) (None: off): the opt-in hot-bin repair (hotbins.py);
+    every shard repairs its own channels and ``hotbins`` is the whole
+    archive's dict(count, total, offsets, bins)."""
     nsub, nchan, nbin = cube.shape
     devices = list(devices) if devices is not None else [0] * world
     if len(devices) != world:
@@ -151,6 +161,9 @@ def _merge(results, chans, shape2, want_details):
     merged = dict(first)
     merged["test"] = _gather_cols([o["test"] for o in results], chans, shape2, np.float64)
     merged["weights"] = _gather_cols([o["weights"] for o in results], chans, shape2, np.float32)
+    if "hotbins" in first:
+        from .hotbins import merge_shards
+        merged["hotbins"] = merge_shards([o["hotbins"] for o in results])
     if want_details and "amp" in first:
         for key, dt in (("amp", np.float64), ("info", np.int32), ("std", np.float64),
                         ("mean", np.float64), ("ptp", first["ptp"].dtype), ("fft", np.float64)):
@@ -175,7 +188,7 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     fractional delays (FFT-rotation dedispersion; (nchan_r,) or (nsub, nchan_r)).
     ``detrend`` / ``detrend_pieces`` with ``shard_detrend=True``: as
     clean_cube_local; the pieces are resolved against `global_shape`.
-    ``std_template``: as clean_cube_local; every rank must pass the same."""
+    ``std_template``, ``hotbins``: as clean_cube_local; every rank must pass the same."""
     import torch.distributed as dist
 
     from .dist import TorchComm
@@ -240,6 +253,12 @@ def _merge_dist(out, res, chans, shape, comm, group, want_residual):
 
     merged["test"] = gather_cols(out["test"], torch.float64)
     merged["weights"] = gather_cols(out["weights"], torch.float32)
+    if "hotbins" in out:
+        # sparse: the ranks' counts and lists as objects, merged on every rank
+        from .hotbins import merge_shards
+        parts = [None] * world
+        dist.all_gather_object(parts, {k: out["hotbins"][k] for k in ("count", "offsets", "bins")}, group=group)
+        merged["hotbins"] = merge_shards(parts)
     if want_residual:
         R = gather_cols(res if res is not None else np.zeros((nsub, nc, nbin), np.float32), torch.float32,
                         to_all=False)

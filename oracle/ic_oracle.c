@@ -437,7 +437,7 @@ void orc_fit_cube(int nsub, int nchan, int n, const float *raw, const float *w0,
 
 /* template (iterative_cleaner.py:88-94): remove_baseline(W), dedisperse,
  * fscrunch, tscrunch, amps * 10000 (f32). */
-static void orc_scrunch(int nsub, int nchan, int n, const float *raw, const float *W,
+void orc_scrunch(int nsub, int nchan, int n, const float *raw, const float *W,
                         const int32_t *shift, const float *base, float *T);
 
 void orc_template(int nsub, int nchan, int n, const float *raw, const float *W,
@@ -450,7 +450,7 @@ void orc_template(int nsub, int nchan, int n, const float *raw, const float *W,
 }
 
 /* dedisperse (integer shifts), fscrunch, tscrunch of f32(raw - base), amps * 10000 */
-static void orc_scrunch(int nsub, int nchan, int n, const float *raw, const float *W,
+void orc_scrunch(int nsub, int nchan, int n, const float *raw, const float *W,
                         const int32_t *shift, const float *base, float *T)
 {
     const int nsb = (nchan + SUPER_BLOCK - 1) / SUPER_BLOCK;

@@ -48,6 +48,7 @@ def lib():
         _lib.orc_baseline.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p, C.c_void_p]
         _lib.orc_fit_cube.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p]
         _lib.orc_template.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_double, C.c_void_p]
+        _lib.orc_scrunch.argtypes = [C.c_int] * 3 + [C.c_void_p] * 5
         _lib.orc_diagnostics.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
         _lib.orc_test.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_void_p]
         _lib.orc_test_f64.argtypes = _lib.orc_test.argtypes
@@ -133,6 +134,18 @@ def template(raw, W, shift, duty=0.15):
     return T
 
 
+def scrunch(cube, W, shift, base=None):
+    """orc_scrunch: dedisperse (integer shifts), fscrunch, tscrunch of
+    f32(cube - base), amps * 10000; base (nsub, nchan) f32 (None: zeros)."""
+    cube = f32(cube)
+    nsub, nchan, n = cube.shape
+    base = np.zeros((nsub, nchan), np.float32) if base is None else f32(base)
+    T = np.empty(n, np.float32)
+    lib().orc_scrunch(nsub, nchan, n, _p(cube), _p(f32(W)), _p(np.ascontiguousarray(shift, np.int32)),
+                      _p(base), _p(T))
+    return T
+
+
 def twiddles(n):
     """(2, n) f64 twiddle table of the FFT rotation (orc_twiddles)."""
     tw = np.empty((n, 2), np.float64)
@@ -148,6 +161,13 @@ def phasors(n, delay):
     return np.ascontiguousarray(np.moveaxis(ph, -1, 0))
 
 
+def _power_of_two(n):
+    """orc_rotate_ex is written for a power-of-two nbin >= 4 and checks nothing:
+    at any other length its output is not a rotation."""
+    if n < 4 or n & (n - 1):
+        raise ValueError("the C oracle's FFT rotation needs a power-of-two nbin >= 4, not %d" % n)
+
+
 def rotate(cube, delay, sign=1, base=None, identity=False):
     """FFT phase rotation (fractional dedispersion) of a (nsub, nchan, n) cube:
     rot(f32(cube - base)) by +delay (sign 1) or -delay (sign -1); delay (nchan,)
@@ -155,6 +175,7 @@ def rotate(cube, delay, sign=1, base=None, identity=False):
     no-op dedisperse of an archive stored dedispersed (f32(cube - base))."""
     cube = f32(cube)
     nsub, nchan, n = cube.shape
+    _power_of_two(n)
     out = np.empty_like(cube)
     d = np.ascontiguousarray(delay, np.float64)
     per_profile = d.size == nsub * nchan and d.ndim == 2
@@ -218,6 +239,7 @@ def clean_loop(raw, w0, shift, chanthresh=5.0, subintthresh=5.0, max_iter=5, pul
                     int(fit_mode), 1 if data_f64 else 0, 0 if delay is None else 1,
                     1 if input_dedispersed else 0, 1 if per_profile else 0)
     if delay is not None:
+        _power_of_two(n)
         delay = np.ascontiguousarray(delay, np.float64).reshape((nsub, nchan) if per_profile else (nchan,))
     test = np.empty((nsub, nchan), np.float64)
     weights = np.empty((nsub, nchan), np.float32)

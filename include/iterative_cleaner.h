@@ -711,6 +711,38 @@ int ic_hotbins_profiles(int device, int nprof, int nbin, const float *in, const 
                         int widen, double threshold, int on_start, int on_end, int rounds, float *out,
                         int32_t *count, int32_t *bins, int64_t cap, int64_t *total);
 
+/* Opt-in dynamic spectrum (iterative_cleaner_amd/dynspec.py is the written
+ * definition; k_dynspec follows it bit for bit): the pulsar's flux and its
+ * uncertainty per (subint, channel) by a template fit with a free baseline, as
+ * psrchive's psrflux takes it from a cleaned archive (that parity is not
+ * pinned).  Per profile the inputs are the dedispersed f32 samples x of the
+ * cube the last ic_run consumed (raw gathered by the integer shifts; rot(raw)
+ * with the FFT dedispersion modes; an input stored dedispersed as it is;
+ * hot-bin-repaired where that mode is on), the template T as ic_get_template
+ * returns it and the last iteration's weight w.  No baseline is removed first
+ * and the pulse region plays no part.  With t = f64(T) - mean(T) and Stt = sum
+ * t^2:  amp = sum(t x) / Stt,  base = mean(x) - amp mean(T),  err = sqrt(sum(((x
+ * - mean(x)) - amp t)^2) / (nbin - 2)) / sqrt(Stt); every sum in f64 in the one
+ * order dynspec.py writes down (64 chains, then a halving tree), no fused
+ * operations.  A profile with w == 0 gets amp = err = base = +0.0 and its
+ * samples are never read; non-finite samples and a constant template are not
+ * special-cased.
+ * ic_get_dynspec: synchronous; amp / err / base [nsub * nchan] each, any may be
+ * NULL.  IC_ESTATE before a completed iteration and on a failed session;
+ * IC_EINVAL for nbin < 4.  It serves every mode ic_run serves, may be called
+ * repeatedly, and launches nothing during ic_run: a session that never calls it
+ * launches and computes exactly what it did without it.  Its scratch (3
+ * doubles per profile and nbin + 2) is allocated at the first call and kept
+ * until ic_session_destroy.  On a channel shard it returns the shard's [nsub]
+ * [nchan_loc] slice; nothing is exchanged (the template is the same on every
+ * rank).  Its kernel is timed as "k_dynspec" (ic_get_kernel_times).
+ * ic_dynspec_profiles: a one-shot of the same kernels on nprof dedispersed
+ * profiles [nprof][nbin] with the template T [nbin] and weights w [nprof];
+ * 4 <= nbin <= 32768. */
+int ic_get_dynspec(void *session, double *amp, double *err, double *base);
+int ic_dynspec_profiles(int device, int nprof, int nbin, const float *T, const float *profiles, const float *w,
+                        double *amp, double *err, double *base);
+
 /* ------------------------------------------------------------------------
  * Channel-sharded cleaning of ONE archive across `world` shards (config C3,
  * SURVEY.md §8(e)).  The reference cleans an archive in one process

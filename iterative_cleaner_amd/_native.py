@@ -32,7 +32,8 @@ EXPORTS = ("ic_abi_version", "ic_device_count", "ic_session_create", "ic_session
            "ic_set_detrend", "ic_get_trends", "ic_comprehensive_stats_detrend",
            "ic_set_detrend_pieces", "ic_get_trends_pieces", "ic_comprehensive_stats_detrend_pieces",
            "ic_shard_enable_detrend", "ic_set_std_template", "ic_get_std_alignment", "ic_align_template",
-           "ic_set_hotbins", "ic_get_hotbins", "ic_get_hotbin_list", "ic_hotbins_profiles")
+           "ic_set_hotbins", "ic_get_hotbins", "ic_get_hotbin_list", "ic_hotbins_profiles",
+           "ic_get_dynspec", "ic_dynspec_profiles")
 
 # session schedule options (ic_set_option; include/iterative_cleaner.h): they
 # choose how the loop is scheduled, never its arithmetic
@@ -198,6 +199,8 @@ def load_library(path: str = LIB_PATH):
     lib.ic_get_hotbin_list.argtypes = [vp, vp, C.c_int64]
     lib.ic_hotbins_profiles.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                         C.c_int, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.ic_get_dynspec.argtypes = [vp, vp, vp, vp]
+    lib.ic_dynspec_profiles.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.ic_comprehensive_stats_detrend_pieces.argtypes = (list(lib.ic_comprehensive_stats_detrend.argtypes)
                                                           + [C.c_int, vp, C.c_int, vp])
     if lib.ic_abi_version() != ABI_VERSION:
@@ -620,6 +623,18 @@ class GpuSession:
         self._check(self.lib.ic_get_template(self.h, _ptr(out)), "ic_get_template")
         return out
 
+    def dynspec(self):
+        """The dynamic spectrum of the cube the last run() consumed
+        (ic_get_dynspec; the definition is dynspec.py): dict(amp, err, base),
+        f64 (nsub, nchan) (a shard: its channel slice): the amplitude of the
+        run's template in every dedispersed profile by a fit with a free
+        baseline, its error, and that baseline; profiles the run left with
+        weight 0 hold zeros.  Launched here, never by run()."""
+        nsub, nchan, _ = self.shape
+        amp, err, base = (np.empty((nsub, nchan), np.float64) for _ in range(3))
+        self._check(self.lib.ic_get_dynspec(self.h, _ptr(amp), _ptr(err), _ptr(base)), "ic_get_dynspec")
+        return dict(amp=amp, err=err, base=base)
+
     def fit(self):
         nsub, nchan, _ = self.shape
         amp = np.empty((nsub, nchan), np.float64)
@@ -741,6 +756,29 @@ def hotbins_profiles(profiles, w, offsets, widen, threshold, on_start, on_end, r
         if rc != 0:
             raise NativeError("ic_hotbins_profiles: %s (rc=%d)" % (_err(lib), rc))
     return out, count, bins
+
+
+def dynspec_profiles(template, profiles, w, device=0):
+    """The dynamic-spectrum kernels alone (ic_dynspec_profiles) on (nprof, nbin)
+    f32 dedispersed profiles with the template (nbin,) and weights w (nprof,),
+    as dynspec.profiles states them: dict(amp, err, base), f64 (nprof,)."""
+    lib = load_library()
+    p = np.ascontiguousarray(profiles, dtype=np.float32)
+    if p.ndim != 2:
+        raise ValueError("dynspec_profiles: profiles must be (nprof, nbin)")
+    nprof, nbin = p.shape
+    T = np.ascontiguousarray(template, dtype=np.float32)
+    if T.shape != (nbin,):
+        raise ValueError("dynspec_profiles: the template must be (%d,), got %s" % (nbin, T.shape))
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.size != nprof:
+        raise ValueError("dynspec_profiles: %d weights for %d profiles" % (w.size, nprof))
+    amp, err, base = (np.empty(nprof, np.float64) for _ in range(3))
+    rc = lib.ic_dynspec_profiles(int(device), nprof, nbin, _ptr(T), _ptr(p), _ptr(w), _ptr(amp), _ptr(err),
+                                 _ptr(base))
+    if rc != 0:
+        raise NativeError("ic_dynspec_profiles: %s (rc=%d)" % (_err(lib), rc))
+    return dict(amp=amp, err=err, base=base)
 
 
 def fit_profiles(profiles, template, fit_mode=FIT_EXACT, device=0):

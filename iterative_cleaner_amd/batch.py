@@ -106,7 +106,7 @@ class _ResidualQueue:
 
 
 def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, detrend_pieces=None,
-             std_template=None, hotbins=None):
+             std_template=None, hotbins=None, dynspec=False):
     """Clean every item of `items` on `session`, overlapping each archive's
     upload with the previous archive's cleaning.  An item is (cube, w0, shift),
     or (q, scl, offs, w0, shift): int16 PSRFITS samples with their scales and
@@ -143,7 +143,10 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, d
     rounds]): the hot-bin repair (GpuSession.set_hotbins; hotbins.py), set
     before the first run; every archive gets its own pass when its upload is
     consumed, and every dict then holds out["hotbins"].  None leaves the
-    session as it is (clean_batch and run_loop read the IC_HOTBINS switch)."""
+    session as it is (clean_batch and run_loop read the IC_HOTBINS switch).
+    dynspec=True: every dict holds out["dynspec"] = dict(amp, err, base), the
+    dynamic spectrum of its archive (GpuSession.dynspec; dynspec.py), taken
+    right after the archive's run."""
     if hotbins is not None:
         session.set_hotbins(*hotbins)
     if std_template is not None:
@@ -173,19 +176,28 @@ def pipeline(session, items, fetch=True, nsum=1, residuals=None, detrend=None, d
     _queue_upload(session, first, nsum)
     for nxt in it:
         _queue_upload(session, nxt, nsum)
-        yield from after_run(session.run(fetch))
-    yield from after_run(session.run(fetch))
+        yield from after_run(_run(session, fetch, dynspec))
+    yield from after_run(_run(session, fetch, dynspec))
     if rq is not None:
         landed, _ = rq.land()
         if landed is not None:
             yield landed
 
 
+def _run(session, fetch, dynspec):
+    """session.run(fetch), with the archive's dynamic spectrum when asked for
+    (the session still holds the cube, template and weights of that run)."""
+    out = session.run(fetch)
+    if dynspec and out.get("n_iter", 0) > 0:
+        out["dynspec"] = session.dynspec()
+    return out
+
+
 _EXITED = -2   # a worker's last message (run_lanes)
 
 
 def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1, residuals=None,
-              std_template=None, hotbins=None):
+              std_template=None, hotbins=None, dynspec=False):
     """Clean every item of `items` ((cube, w0, shift) or (q, scl, offs, w0, shift),
     each with or without trailing delays, as `pipeline`) on `len(sessions)` sessions of one
     shape concurrently (one host thread per session, shared work queue; each
@@ -199,6 +211,7 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
     again only after the consumer has moved on from the result that held it.
 
     std_template, hotbins: `pipeline`'s, set on every session before the first run.
+    dynspec: `pipeline`'s.
 
     On a worker error, or when the consumer stops early (generator closed), the
     lanes stop: the `stop` event (created here if not given) is set, queued work
@@ -220,7 +233,8 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
         for sess in sessions:
             sess.set_hotbins(*hotbins)
     if len(sessions) == 1:
-        yield from pipeline(sessions[0], items, fetch, nsum, None if residuals is None else residuals[0])
+        yield from pipeline(sessions[0], items, fetch, nsum, None if residuals is None else residuals[0],
+                            dynspec=dynspec)
         return
     rqs = None
     if residuals is not None:
@@ -270,7 +284,7 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
                     item = work.get_nowait()
                 except queue.Empty:
                     if pending is not None:   # nothing queued: run what we hold
-                        finish(pending, sess.run(fetch))
+                        finish(pending, _run(sess, fetch, dynspec))
                         pending = None
                         continue
                     if flying is not None:    # nothing to overlap it with: hand it over
@@ -284,10 +298,10 @@ def run_lanes(sessions, items, fetch=True, stop=None, join_timeout=None, nsum=1,
                 del held[lane][:-3]             # an upload is consumed by the second run after it
                 _queue_upload(sess, arrays, nsum)
                 if pending is not None:
-                    finish(pending, sess.run(fetch))
+                    finish(pending, _run(sess, fetch, dynspec))
                 pending = idx
             if pending is not None and not stop.is_set():
-                finish(pending, sess.run(fetch))
+                finish(pending, _run(sess, fetch, dynspec))
             if flying is not None and not stop.is_set():
                 land()
         except BaseException as e:  # noqa: BLE001 - re-raised by the consumer
@@ -431,7 +445,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                 pulse_region=(0, 0, 1), baseline_duty=0.15, lanes=1, join_timeout=None, quantised=False, nsum=1,
                 dedisp="shift", input_dedispersed=False, fit_mode=_native.FIT_EXACT, options=None,
                 any_length=None, residuals=False, residual_big_endian=True, detrend=None,
-                detrend_pieces=None, std_template=None, hotbins=None):
+                detrend_pieces=None, std_template=None, hotbins=None, dynspec=None):
     """Clean the archives produced by `loader` (an iterable of (cube, w0, shift)
     host arrays of one (nsub, nchan, nbin) shape; shift is reduced mod nbin).
     A loader thread copies them into a ring of page-locked slots; the GPU
@@ -484,8 +498,13 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
     repair (hotbins.py) on every lane's session: each archive's off-pulse hot
     bins are repaired before it is cleaned, and out["hotbins"] = dict(count,
     total, offsets, bins) is per archive.  None reads the IC_HOTBINS switch
-    ("thr,start,end[,rounds]"; unset, empty or 0: off)."""
+    ("thr,start,end[,rounds]"; unset, empty or 0: off).
+    dynspec=True: out["dynspec"] = dict(amp, err, base) per archive, its dynamic
+    spectrum (dynspec.py).  None reads the IC_DYNSPEC switch (unset, empty or
+    0: off; no file is written here)."""
+    from . import dynspec as dsm
     from . import hotbins as hbm
+    dyn = dsm.normalise(dynspec) is not None
     from . import std_template as stdt
     hot = hbm.normalise(hotbins)
     from .detrend import normalise, normalise_pieces
@@ -610,7 +629,7 @@ def clean_batch(loader, shape, device=0, ring=None, max_iter=5, chanthresh=5.0, 
                                                dedisp_fft=fft, any_length=any_length, detrend=detrend,
                                                detrend_pieces=detrend_pieces, std_template=std, hotbins=hot))
         lanes_gen = run_lanes(sessions, staged(), stop=stop, join_timeout=join_timeout, nsum=nsum,
-                              residuals=[rr.triples() for rr in result_rings] if residuals else None)
+                              residuals=[rr.triples() for rr in result_rings] if residuals else None, dynspec=dyn)
         for k, out in enumerate(lanes_gen):
             free.put(order[k])          # archive k's slot is free once its result is yielded
             if std is not None:

@@ -208,7 +208,8 @@ def _device() -> int:
 
 def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_duty=0.15, nchan_total=None,
              data_f64=False, delay=None, input_dedispersed=False, quantised=None, residual_quantised=False,
-             detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None):
+             detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None,
+             dynspec=None):
     """Run the GPU loop on a (nsub, nchan, nbin) f32 cube, or on full-polarisation
     data (nsub, npol, nchan, nbin) that the GPU pscrunches; returns the ic_run dict
     (+ ``residual`` when requested).  ``quantised`` = (q, scl, offs, nsum) with
@@ -247,8 +248,13 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
     IC_HOTBINS="thr,start,end[,rounds]" (unset, empty or 0: off).  The result
     then holds ``hotbins`` = dict(count, total, offsets, bins); under channel
     sharding every rank repairs its own channels and the dict is the whole
-    archive's."""
+    archive's.  ``dynspec``=True: the result holds ``dynspec`` = dict(amp, err,
+    base), the dynamic spectrum (dynspec.py) of the cube the loop consumed, each
+    f64 (nsub, nchan) (under channel sharding the whole archive's); None reads
+    the switch IC_DYNSPEC (unset, empty or 0: off)."""
+    from . import dynspec as dsm
     from . import hotbins as hbm
+    dyn = dsm.normalise(dynspec) is not None
     from . import std_template as stdt
     hot = hbm.normalise(hotbins)
     from .detrend import normalise, normalise_pieces, shards_enabled
@@ -290,7 +296,7 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
             max_iter=args.max_iter, chanthresh=args.chanthresh, subintthresh=args.subintthresh,
             pulse_region=args.pulse_region, baseline_duty=baseline_duty, data_f64=data_f64, delay=delay,
             input_dedispersed=input_dedispersed, **({} if std is None else dict(std_template=std)),
-            **({} if hot is None else dict(hotbins=hot)),
+            **({} if hot is None else dict(hotbins=hot)), **(dict(dynspec=True) if dyn else {}),
             **(dict(detrend=detrend, detrend_pieces=detrend_pieces, shard_detrend=True) if detrend is not None else {}))
         if rank == 0 and std is not None:
             stdt.warn_failed(out.get("std_alignment"), std[1])
@@ -309,6 +315,8 @@ def run_loop(cube, w0, shift, args, device=None, want_residual=False, baseline_d
         else:
             s.upload(cube, w0, shift)
         out = s.run()
+        if dyn and out["n_iter"] > 0:
+            out["dynspec"] = s.dynspec()
         if want_residual and out["n_iter"] > 0:
             if residual_quantised:
                 out["residual_q"] = s.residual_quantised(big_endian=True)
@@ -365,12 +373,17 @@ def _plot_zap(test, ar_name, args):
 BAD_STATUS = "Bad status for least squares fit when removing profile."
 
 
-def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None):
+def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None, std_template=None, hotbins=None,
+          dynspec=None):
     """Surgical cleaning of one archive (iterative_cleaner.py:65-178).  detrend,
     detrend_pieces, detrend_shards, std_template, hotbins: run_loop's (None = the
     IC_DETREND / IC_DETREND_PIECES / IC_DETREND_SHARDS / IC_STD_TEMPLATE /
     IC_HOTBINS switches; there is no CLI flag).  With hotbins the output archive
-    is patched at the repaired bins (_patch_hotbins).  Under
+    is patched at the repaired bins (_patch_hotbins).  dynspec: True writes the
+    dynamic spectrum (dynspec.py) to "<ar_name>.dynspec", a path writes it
+    there; None reads the switch IC_DYNSPEC (unset, empty or 0: off; 1: the
+    default name; anything else: the path).  The file is masked with the output
+    archive's final weights, after set_weights_archive and find_bad_parts.  Under
     channel sharding only rank 0 prints and writes files; `ar` may then be this
     rank's channel slice (main() reads slice-only) and rank 0 loads the whole
     archive for the output."""
@@ -381,6 +394,8 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
         _side_effects = False
     else:
         _side_effects = True
+    from . import dynspec as dsm
+    dyn = dsm.normalise(dynspec)
     backend = archive_backend()
     chan_slice = getattr(ar, "_chan_range", None) is not None
     nchan_total = ar._nchan_total if chan_slice else None
@@ -419,7 +434,8 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
                    nchan_total=nchan_total, data_f64=f64, delay=delay,
                    input_dedispersed=stored_ded and delay is not None, quantised=quant,
                    residual_quantised=psrfits_res, detrend=detrend, detrend_pieces=detrend_pieces,
-                   detrend_shards=detrend_shards, std_template=std_template, hotbins=hotbins)
+                   detrend_shards=detrend_shards, std_template=std_template, hotbins=hotbins,
+                   dynspec=dyn is not None)
     del cube
 
     x = 0
@@ -467,6 +483,9 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
     set_weights_archive(ar, avg_test_results)
     if args.bad_chan != 1 or args.bad_subint != 1:
         ar = find_bad_parts(ar, args)
+    if dyn is not None and _side_effects and out.get("dynspec") is not None:
+        _write_dynspec(ar, out["dynspec"], "%s.dynspec" % ar_name if dyn is True else dyn, ar_name,
+                       "standard" if out.get("std_alignment") is not None else "cleaner")
     if args.unload_res and _side_effects:
         res_name = "%s_residual_%s.ar" % (ar_name, loops)
         if psrfits_res:
@@ -480,6 +499,19 @@ def clean(ar, args, arch, detrend=None, detrend_pieces=None, detrend_shards=None
             fh.write("\n %s: Cleaned %s with %s, required loops=%s"
                      % (datetime.datetime.now(), ar_name, args, loops))
     return ar
+
+
+def _write_dynspec(ar, result, path, ar_name, source):
+    """The dynamic spectrum of the cleaned archive as text (dynspec.save): masked
+    with the output archive's weights as they stand (after set_weights_archive
+    and find_bad_parts, so a channel --bad_chan removed is zero here too), with
+    the channels' frequencies and the subints' times where the archive object
+    offers them.  source: where the template came from ("cleaner": the last
+    iteration's; "standard": the supplied profile)."""
+    from . import dynspec as dsm
+    freq, tmin = dsm.archive_axes(ar)
+    dsm.save(path, result, dsm.final_weights(ar),
+             dict(archive=ar_name, nbin=ar.get_nbin(), template=source, freq_MHz=freq, time_min=tmin))
 
 
 def _patch_hotbins(ar, result, hotbins, shift, delay, stored_ded):

@@ -1,7 +1,7 @@
 // ic_internal.h — shared declarations between the host session (ic_session.hip)
 // and the gfx950 kernel units (ic_template.hip, ic_codec.hip, ic_fit.hip,
 // ic_diag.hip, ic_rotate.hip, ic_linestats.hip, ic_shards.hip, ic_stdtemplate.hip,
-// ic_hotbins.hip).
+// ic_hotbins.hip, ic_dynspec.hip).
 // Not part of the public C-ABI.
 #pragma once
 #include <hip/hip_ext.h>
@@ -116,6 +116,7 @@ enum KernelId {
     K_STD_INSTALL,    // standard template: k_std_install
     K_HOTBINS,        // hot-bin repair: k_hotbins
     K_HOTBIN_SCAN,    // ... and the row starts of its hit list: k_hotbin_scan
+    K_DYNSPEC,        // dynamic spectrum (ic_get_dynspec): k_dynspec
     K_COUNT
 };
 
@@ -741,5 +742,27 @@ hipError_t launch_hotbin_scan(hipStream_t st, const int32_t *count, long P, int6
                               int64_t *total);
 hipError_t launch_hotbin_fill(hipStream_t st, const int32_t *count, const uint32_t *mask, const int64_t *offs, long P,
                               int nbin, int32_t *bins, int64_t cap, int grid_cap = 0);
+
+// Dynamic spectrum (ic_get_dynspec; dynspec.py): the free-baseline template fit
+// of every dedispersed profile, after a run (ic_dynspec.hip).  x: the raw cube
+// [P][nbin] with shift [nchan] (profile k reads channel k % nchan's; bin i of
+// the dedispersed profile is x[(i + shift) % nbin]), or rows already
+// dedispersed (shift == nullptr).  tt: launch_dynspec_prep's [2 + nbin] doubles
+// (mT, Stt, then t).  Profiles with w == 0 get zeros and their rows are not
+// read.  amp / err / base [P]: any may be null.
+constexpr int kDynMinBin = 4;          // fewer bins are refused
+constexpr int kDynRegMaxBin = 8192;    // up to here a row stays in one wave's registers between the passes
+struct DynspecArgs {
+    const float *x;
+    const int32_t *shift;
+    const float *w;
+    const double *tt;
+    long P;
+    int nchan, nbin;
+    double *amp, *err, *base;
+    int grid_cap;
+};
+hipError_t launch_dynspec_prep(hipStream_t st, const float *T, int nbin, double *tt);
+hipError_t launch_dynspec(hipStream_t st, const DynspecArgs &a);
 
 }  // namespace icgpu

@@ -143,7 +143,7 @@ const char *kKernelNames[K_COUNT] = {"k_chan_partials", "k_window",    "k_base",
                                      "k_diag",          "k_linestats", "k_combine",  "k_residual",
                                      "k_fit_tail",      "k_sb_tree",   "k_shard_pack", "exchange",
                                      "k_tnorm",         "k_rotate",    "k_residual_q", "k_std_align",
-                                     "k_std_install",   "k_hotbins",   "k_hotbin_scan"};
+                                     "k_std_install",   "k_hotbins",   "k_hotbin_scan", "k_dynspec"};
 
 constexpr long kTailProfiles = 8192;  // default: hand the remaining profiles to k_fit_tail below this
 constexpr long kTailProfilesLarge = 4096;   // the same for sessions of >= 2^20 profiles
@@ -296,6 +296,10 @@ struct Session {
     int32_t *hb_count = nullptr;
     uint32_t *hb_mask = nullptr;
     int64_t *hb_offs = nullptr, *hb_total = nullptr;
+    // dynamic spectrum (ic_get_dynspec; dynspec.py): nothing of it runs in
+    // ic_run.  ds_tt [2 + nbin]: mT, Stt and the table t of the template;
+    // ds_out [3 P]: amp, err, base.  From `mem` at the first call, kept
+    double *ds_tt = nullptr, *ds_out = nullptr;
     long tail_threshold = kTailProfiles;   // IC_OPT_FIT_TAIL
     bool diag_chain = true;     // IC_OPT_DIAG_CHAIN: k_diag_cl at nbin 1024/2048/4096
     int grid_cap = 0;           // IC_OPT_GRID_CAP: > 0 caps the grids of the grid-stride kernels
@@ -3336,6 +3340,85 @@ int ic_hotbins_profiles(int device, int nprof, int nbin, const float *in, const 
     CKF(sc.mem.alloc_exact(&dbins, (size_t)*total), bad);
     CKF(launch_hotbin_fill(st, a.count, a.mask, doffs, (long)P, nbin, dbins, *total), bad);
     CKF(hipMemcpyAsync(bins, dbins, sizeof(int32_t) * (size_t)*total, hipMemcpyDeviceToHost, st), bad);
+    CKF(hipStreamSynchronize(st), bad);
+    return IC_OK;
+}
+
+int ic_get_dynspec(void *session, double *amp, double *err, double *base)
+{
+    Session *s = (Session *)session;
+    if (!s) return fail(IC_EINVAL, "null session");
+    if (s->failed) return failed_session();
+    if (!s->ran) return fail(IC_ESTATE, "ic_get_dynspec: no completed iteration");
+    const int nbin = s->p.nbin;
+    if (nbin < kDynMinBin) return fail(IC_EINVAL, "ic_get_dynspec: nbin=%d below %d", nbin, kDynMinBin);
+    CK(hipSetDevice(s->device));
+    if (s->mem.ensure(&s->ds_tt, (size_t)nbin + 2) != hipSuccess || s->mem.ensure(&s->ds_out, 3 * s->P) != hipSuccess)
+        return fail(IC_ENOMEM, "hipMalloc(dynamic spectrum: %zu bytes) failed", 8 * ((size_t)nbin + 2 + 3 * s->P));
+    // the cube the last run consumed, dedispersed: the rotated view rot(raw)
+    // that prepare() left (an input stored dedispersed: its copy), or raw
+    // gathered by the integer shifts
+    DynspecArgs a{};
+    a.x = s->fftded ? s->dr : s->raw;
+    a.shift = s->fftded ? nullptr : s->shift;
+    a.w = s->W;
+    a.tt = s->ds_tt;
+    a.P = (long)s->P;
+    a.nchan = s->nchan;
+    a.nbin = nbin;
+    a.amp = s->ds_out;
+    a.err = s->ds_out + s->P;
+    a.base = s->ds_out + 2 * s->P;
+    a.grid_cap = s->grid_cap;
+    CK(launch_dynspec_prep(s->stream, s->T, nbin, s->ds_tt));
+    LAUNCH(s, K_DYNSPEC, launch_dynspec(s->stream, a));
+    double *const host[3] = {amp, err, base};
+    for (int q = 0; q < 3; ++q)
+        if (host[q])
+            CK(hipMemcpyAsync(host[q], s->ds_out + (size_t)q * s->P, sizeof(double) * s->P, hipMemcpyDeviceToHost,
+                              s->stream));
+    CK(hipStreamSynchronize(s->stream));
+    return IC_OK;
+}
+
+int ic_dynspec_profiles(int device, int nprof, int nbin, const float *T, const float *profiles, const float *w,
+                        double *amp, double *err, double *base)
+{
+    if (!T || !profiles || !w) return fail(IC_EINVAL, "null argument");
+    if (nprof <= 0) return fail(IC_EINVAL, "bad shape nprof=%d nbin=%d", nprof, nbin);
+    if (nbin < kDynMinBin || nbin > 32768)
+        return fail(IC_EINVAL, "ic_dynspec_profiles: nbin=%d outside %d..32768", nbin, kDynMinBin);
+    if (int rc = select_device(device)) return rc;
+    const size_t P = (size_t)nprof, N = P * nbin;
+    const auto bad = [](hipError_t e) { return named_fail("ic_dynspec_profiles", e, true); };
+    Scratch sc;
+    CKF(sc.open_stream(), bad);
+    hipStream_t st = sc.stream;
+    float *dT = nullptr, *dx = nullptr, *dw = nullptr;
+    double *dtt = nullptr, *dout = nullptr;
+    CKF(sc.mem.alloc(&dT, (size_t)nbin), bad);
+    CKF(sc.mem.alloc_exact(&dx, N), bad);
+    CKF(sc.mem.alloc_exact(&dw, P), bad);
+    CKF(sc.mem.alloc(&dtt, (size_t)nbin + 2), bad);
+    CKF(sc.mem.alloc(&dout, 3 * P), bad);
+    CKF(hipMemcpyAsync(dT, T, sizeof(float) * nbin, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dx, profiles, sizeof(float) * N, hipMemcpyHostToDevice, st), bad);
+    CKF(hipMemcpyAsync(dw, w, sizeof(float) * P, hipMemcpyHostToDevice, st), bad);
+    DynspecArgs a{};
+    a.x = dx;
+    a.w = dw;
+    a.tt = dtt;
+    a.P = (long)P;
+    a.nchan = 1;
+    a.nbin = nbin;
+    a.amp = dout;
+    a.err = dout + P;
+    a.base = dout + 2 * P;
+    CKF(launch_dynspec_prep(st, dT, nbin, dtt), bad);
+    CKF(launch_dynspec(st, a), bad);
+    double *const host[3] = {amp, err, base};
+    for (int q = 0; q < 3; ++q)
+        if (host[q]) CKF(hipMemcpyAsync(host[q], dout + (size_t)q * P, sizeof(double) * P, hipMemcpyDeviceToHost, st), bad);
     CKF(hipStreamSynchronize(st), bad);
     return IC_OK;
 }

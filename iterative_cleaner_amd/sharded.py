@@ -26,8 +26,8 @@ def _gather_cols(parts, ranges, shape, dtype):
     return out
 
 
-# the keywords of **args: the session's (_loop_kwargs), and `delay`, which the
-# callers slice per rank themselves
+# the keywords of **args: the session's (_loop_kwargs), `delay`, which the
+# callers slice per rank themselves, and `dynspec`, which they act on after the run
 _LOOP_KEYS = ("max_iter", "chanthresh", "subintthresh", "pulse_region", "baseline_duty", "fit_mode", "data_f64",
               "options", "input_dedispersed", "any_length", "detrend", "detrend_pieces", "shard_detrend",
               "std_template", "hotbins")
@@ -43,7 +43,7 @@ def _loop_kwargs(args, global_shape=None, nbin=None):
     read) is loaded and checked once per call, for the archive's nbin.
     hotbins (hotbins.normalise's forms but None, which is off: run_loop reads
     the IC_HOTBINS switch): the hot-bin repair, each rank on its own slice."""
-    unknown = sorted(set(args) - set(_LOOP_KEYS) - {"delay"})
+    unknown = sorted(set(args) - set(_LOOP_KEYS) - {"delay", "dynspec"})
     if unknown:
         raise TypeError("unknown keyword(s) for a sharded clean: %s" % ", ".join(unknown))
     kw = dict(max_iter=args.get("max_iter", 5), chanthresh=args.get("chanthresh", 5.0),
@@ -96,7 +96,9 @@ def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, f
     every shard's (checked equal).  ``hotbins`` = (threshold, on_start,
     on_end[, rounds]) (None: off): the opt-in hot-bin repair (hotbins.py);
     every shard repairs its own channels and ``hotbins`` is the whole
-    archive's dict(count, total, offsets, bins)."""
+    archive's dict(count, total, offsets, bins).  ``dynspec=True``: ``dynspec``
+    = dict(amp, err, base), the archive's dynamic spectrum (dynspec.py), every
+    shard's slice joined in rank order."""
     nsub, nchan, nbin = cube.shape
     devices = list(devices) if devices is not None else [0] * world
     if len(devices) != world:
@@ -123,6 +125,8 @@ def clean_cube_local(cube, w0, shift, world, devices=None, want_details=False, f
                 try:
                     s = sessions[r]
                     out = s.run()
+                    if args.get("dynspec") and out["n_iter"] > 0:
+                        out["dynspec"] = s.dynspec()
                     if want_details and out["n_iter"] > 0:
                         out["amp"], out["info"] = s.fit()
                         out["std"], out["mean"], out["ptp"], out["fft"] = s.diagnostics()
@@ -164,6 +168,9 @@ def _merge(results, chans, shape2, want_details):
     if "hotbins" in first:
         from .hotbins import merge_shards
         merged["hotbins"] = merge_shards([o["hotbins"] for o in results])
+    if "dynspec" in first:
+        from .dynspec import merge_shards as merge_dynspec
+        merged["dynspec"] = merge_dynspec([o["dynspec"] for o in results])
     if want_details and "amp" in first:
         for key, dt in (("amp", np.float64), ("info", np.int32), ("std", np.float64),
                         ("mean", np.float64), ("ptp", first["ptp"].dtype), ("fft", np.float64)):
@@ -188,7 +195,7 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
     fractional delays (FFT-rotation dedispersion; (nchan_r,) or (nsub, nchan_r)).
     ``detrend`` / ``detrend_pieces`` with ``shard_detrend=True``: as
     clean_cube_local; the pieces are resolved against `global_shape`.
-    ``std_template``, ``hotbins``: as clean_cube_local; every rank must pass the same."""
+    ``std_template``, ``hotbins``, ``dynspec``: as clean_cube_local; every rank must pass the same."""
     import torch.distributed as dist
 
     from .dist import TorchComm
@@ -204,6 +211,8 @@ def clean_cube_dist(cube_slice, w0_slice, shift_slice, global_shape, device, gro
             else:
                 s.upload(cube_slice, w0_slice, shift_slice)
             out = s.run()
+            if args.get("dynspec") and out["n_iter"] > 0:
+                out["dynspec"] = s.dynspec()
             res = s.residual() if want_residual and out["n_iter"] > 0 else None
     except _native.NativeError:
         comm.abort()          # peers waiting in a collective with this rank must not block
@@ -259,6 +268,9 @@ def _merge_dist(out, res, chans, shape, comm, group, want_residual):
         parts = [None] * world
         dist.all_gather_object(parts, {k: out["hotbins"][k] for k in ("count", "offsets", "bins")}, group=group)
         merged["hotbins"] = merge_shards(parts)
+    if "dynspec" in out:
+        # the ranks' slices joined in rank order (dynspec.merge_shards), on every rank
+        merged["dynspec"] = {k: gather_cols(out["dynspec"][k], torch.float64) for k in ("amp", "err", "base")}
     if want_residual:
         R = gather_cols(res if res is not None else np.zeros((nsub, nc, nbin), np.float32), torch.float32,
                         to_all=False)

@@ -469,52 +469,38 @@ bool diag_list_supported(const DiagArgs &a);
 size_t diag_lds_bytes(int nbin);
 // *TT = numpy pairwise sum of T64[i]^2 over nbin (plan), nleaf_ub >= plan leaves/ops
 hipError_t launch_tnorm(hipStream_t st, const double *T64, const PwPlan *plan, int nleaf_ub, double *TT);
-// which: bit 0 = column lines (length nsub), bit 1 = row lines (length nchan)
-hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which = 3);
+// The line stage: medians / MADs of the four diagnostics along channel lines
+// and subint lines into a's col_* / row_*.  which: bit 0 = column lines (length
+// nsub), bit 1 = row lines (length nchan).  trend != nullptr: the detrended form
+// (k_linetrend), which also writes the lines' coefficients into *trend and
+// takes the medians / MADs of the detrended lines; pieces != nullptr (only with
+// trend): the piecewise form (k_linetrend_pw)
+hipError_t launch_lines(hipStream_t st, const LineStatsArgs &a, const TrendArgs *trend, const PieceArgs *pieces,
+                        int which);
+// combine scales the entries (detrended with *trend, if given) with the stage's
+// medians / MADs: test values, weights and the convergence counters.
 // counters: [0] changed, [1] zero weights, [2] fit statuses outside 1-4 (info
 // may be null), [3] test values within 1e-9 of 1.0, [4+h] new weights !=
 // history h (iterative_cleaner.py:127-141)
-hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                          const float *w0,
-                          const double *std_d, const double *mean_d, const double *ptp_d, int ptp_f32,
-                          const double *fft_d, const double *col_med, const double *col_mad,
-                          const double *row_med, const double *row_mad, double chanthresh,
-                          double subintthresh, double *test, float *W, float *hist, int iter,
-                          int32_t *counters, int grid_cap = 0);
-// the detrended forms (k_linetrend, k_combine_dt): launch_linetrend writes the
-// coefficients of t and the medians / MADs of the detrended lines into a's
-// col_* / row_*; launch_combine_dt scales the detrended entries with them
-hipError_t launch_linetrend(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int which = 3);
-hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                             int grid_cap = 0);
-// the piecewise forms (k_linetrend_pw, k_combine_pw), as the two above
-hipError_t launch_linetrend_pw(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pc,
-                               int which = 3);
-hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                             const PieceArgs &pc, int grid_cap = 0);
-// the two combines on a channel shard (k_combine_dt_sh, k_combine_pw_sh): nchan
-// is the shard's, its channels chan0 .. chan0 + nchan of nchan_g; t.row_coef (and
-// pc's row tables) are whole subint lines', t.col_coef the shard's channels'
-hipError_t launch_combine_dt_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                                int chan0, int nchan_g, int grid_cap = 0);
-hipError_t launch_combine_pw_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                                const PieceArgs &pc, int chan0, int nchan_g, int grid_cap = 0);
+struct CombineArgs {
+    LineStatsArgs ls;                       // the stage's diagnostics and line statistics
+    const int32_t *info;
+    const float *w0;
+    double chanthresh, subintthresh;
+    double *test;
+    float *W, *hist;
+    int iter;
+    int32_t *counters;
+    int grid_cap;
+    const TrendArgs *trend = nullptr;       // nullptr: plain (k_combine)
+    const PieceArgs *pieces = nullptr;      // nullptr: whole lines; only with trend
+    // a channel shard (only with trend; nchan_g == 0: not a shard): ls.nchan is
+    // the shard's, its channels chan0 .. chan0 + nchan of nchan_g; trend->row_coef
+    // (and the pieces' row tables) are whole subint lines', col_coef the shard's
+    // channels'
+    int chan0 = 0, nchan_g = 0;
+};
+hipError_t launch_combine(hipStream_t st, const CombineArgs &c);
 // Phasor exp(+2 pi i k d / n) of harmonic k (0 <= k <= n/2) for a delay of d
 // bins, n even (<= 8192; 1/n and 4/n are rounded factors unless n is a power
 // of two): the phase rotation's multiplier

@@ -1219,199 +1219,109 @@ __global__ __launch_bounds__(256) void k_combine_pw_sh(
 
 // ============================================================ launchers
 
-hipError_t launch_linestats(hipStream_t st, const LineStatsArgs &a, int which)
+// one direction's plain lines; wave-private LDS: 256-bin histogram + the line's keys
+static hipError_t launch_linestats_dir(hipStream_t st, const LineStatsArgs &a, int rows, int len, int lines)
 {
-    // columns (length nsub), then rows (length nchan); wave-private LDS:
-    // 256-bin histogram + the line's keys
-    for (int rows = 0; rows < 2; ++rows) {
-        if (!((which >> rows) & 1)) continue;
-        const int len = rows ? a.nchan : a.nsub;
-        const int lines = 4 * (rows ? a.nsub : a.nchan);
-        if (lines == 0 || len == 0) continue;
-        // few long lines (the rows): W waves per line (a.grp_waves = W in {0, 4, 8},
-        // 0 = one wave per line; a.grp_minlen = the shortest line it takes)
-        if (lines < 8192 && len >= a.grp_minlen) {
-            const int W = a.grp_waves;
-            if (W == 4 || W == 8) {
-                const int seg = (((len + W - 1) / W) + 63) & ~63;
-                const size_t gshm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8;
-                if (gshm <= kLdsBlockMax) {
-                    if (W == 4)
-                        IC_GGL(k_linestats_grp<4>, dim3(lines), dim3(256), gshm, st, a, rows, len);
-                    else
-                        IC_GGL(k_linestats_grp<8>, dim3(lines), dim3(512), gshm, st, a, rows, len);
-                    const hipError_t e = hipGetLastError();
-                    if (e != hipSuccess) return e;
-                    continue;
-                }
+    // few long lines (the rows): W waves per line (a.grp_waves = W in {0, 4, 8},
+    // 0 = one wave per line; a.grp_minlen = the shortest line it takes)
+    if (lines < 8192 && len >= a.grp_minlen) {
+        const int W = a.grp_waves;
+        if (W == 4 || W == 8) {
+            const int seg = (((len + W - 1) / W) + 63) & ~63;
+            const size_t gshm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8;
+            if (gshm <= kLdsBlockMax) {
+                if (W == 4)
+                    IC_GGL(k_linestats_grp<4>, dim3(lines), dim3(256), gshm, st, a, rows, len);
+                else
+                    IC_GGL(k_linestats_grp<8>, dim3(lines), dim3(512), gshm, st, a, rows, len);
+                return hipGetLastError();
             }
         }
-        const int per_wave = 1024 + ((len * 8 + 15) / 16) * 16;
-        int wpb = 4;
-        while (wpb > 1 && (size_t)wpb * per_wave > 64 * 1024) --wpb;
-        const size_t shm = (size_t)wpb * per_wave;
-        if (shm > kLdsBlockMax) return hipErrorInvalidValue;
-        IC_GGL(k_linestats, dim3(cdiv(lines, wpb)), dim3(64 * wpb), shm, st, a, rows, len, wpb,
-                           per_wave);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
     }
-    return hipSuccess;
-}
-
-// the detrended line stage: coefficients, and the medians / MADs of d' into
-// a's col_* / row_* (which: as launch_linestats).  Rows of >= grp_minlen values
-// take grp_waves waves per line, as launch_linestats' do; the bits do not
-// depend on it.
-template <int W>
-static hipError_t launch_linetrend_w(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int rows, int len,
-                                     int lines, bool *done)
-{
-    const int seg = (((len + W - 1) / W) + 63) & ~63;
-    const size_t shm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8 + (size_t)((len + 63) / 64) * 8;
-    *done = shm <= kLdsBlockMax;
-    if (!*done) return hipSuccess;
-    IC_GGL(k_linetrend<W>, dim3(lines), dim3(64 * W), shm, st, a, t, rows, len);
+    const int per_wave = 1024 + ((len * 8 + 15) / 16) * 16;
+    int wpb = 4;
+    while (wpb > 1 && (size_t)wpb * per_wave > 64 * 1024) --wpb;
+    const size_t shm = (size_t)wpb * per_wave;
+    if (shm > kLdsBlockMax) return hipErrorInvalidValue;
+    IC_GGL(k_linestats, dim3(cdiv(lines, wpb)), dim3(64 * wpb), shm, st, a, rows, len, wpb, per_wave);
     return hipGetLastError();
 }
 
-hipError_t launch_linetrend(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, int which)
-{
-    for (int rows = 0; rows < 2; ++rows) {
-        if (!((which >> rows) & 1)) continue;
-        const int len = rows ? a.nchan : a.nsub;
-        const int lines = 4 * (rows ? a.nsub : a.nchan);
-        if (lines == 0 || len == 0) continue;
-        bool done = false;
-        hipError_t e = hipSuccess;
-        if (lines < 8192 && len >= a.grp_minlen) {
-            if (a.grp_waves == 4) e = launch_linetrend_w<4>(st, a, t, rows, len, lines, &done);
-            if (a.grp_waves == 8) e = launch_linetrend_w<8>(st, a, t, rows, len, lines, &done);
-        }
-        if (!done) {
-            e = launch_linetrend_w<1>(st, a, t, rows, len, lines, &done);
-            if (!done) return hipErrorInvalidValue;
-        }
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// the piecewise line stage: launch_linetrend's shapes; LDS also holds a line's
-// piece coefficients (32 B each) and retired flags
+// one direction's detrended lines with W waves per line, if LDS holds them
+// (*done).  With pieces LDS also holds a line's piece coefficients (32 B each)
+// and retired flags
 template <int W>
-static hipError_t launch_linetrend_pw_w(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pa,
-                                        int rows, int len, int lines, bool *done)
+static hipError_t launch_linetrend_w(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs *pa,
+                                     int rows, int len, int lines, bool *done)
 {
     const int seg = (((len + W - 1) / W) + 63) & ~63;
-    const size_t m = (size_t)(rows ? pa.row_np : pa.col_np);
-    const size_t shm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8 + (size_t)((len + 63) / 64) * 8 + m * 32 +
-                       ((m + 15) & ~(size_t)15);
+    size_t shm = 1024 + 16 * (size_t)W + (size_t)W * seg * 8 + (size_t)((len + 63) / 64) * 8;
+    if (pa) {
+        const size_t m = (size_t)(rows ? pa->row_np : pa->col_np);
+        shm += m * 32 + ((m + 15) & ~(size_t)15);
+    }
     *done = shm <= kLdsBlockMax;
     if (!*done) return hipSuccess;
-    IC_GGL(k_linetrend_pw<W>, dim3(lines), dim3(64 * W), shm, st, a, t, pa, rows, len);
+    if (pa)
+        IC_GGL(k_linetrend_pw<W>, dim3(lines), dim3(64 * W), shm, st, a, t, *pa, rows, len);
+    else
+        IC_GGL(k_linetrend<W>, dim3(lines), dim3(64 * W), shm, st, a, t, rows, len);
     return hipGetLastError();
 }
 
-hipError_t launch_linetrend_pw(hipStream_t st, const LineStatsArgs &a, const TrendArgs &t, const PieceArgs &pa,
-                               int which)
+// columns (length nsub), then rows (length nchan).  The detrended forms' rows of
+// >= grp_minlen values take grp_waves waves per line, as the plain ones do; the
+// bits do not depend on it.
+hipError_t launch_lines(hipStream_t st, const LineStatsArgs &a, const TrendArgs *trend, const PieceArgs *pa, int which)
 {
-    if (pa.col_np < 1 || pa.col_np > kMaxPieces || pa.row_np < 1 || pa.row_np > kMaxPieces)
+    if (pa && (!trend || pa->col_np < 1 || pa->col_np > kMaxPieces || pa->row_np < 1 || pa->row_np > kMaxPieces))
         return hipErrorInvalidValue;
     for (int rows = 0; rows < 2; ++rows) {
         if (!((which >> rows) & 1)) continue;
         const int len = rows ? a.nchan : a.nsub;
         const int lines = 4 * (rows ? a.nsub : a.nchan);
         if (lines == 0 || len == 0) continue;
-        bool done = false;
         hipError_t e = hipSuccess;
-        if (lines < 8192 && len >= a.grp_minlen) {
-            if (a.grp_waves == 4) e = launch_linetrend_pw_w<4>(st, a, t, pa, rows, len, lines, &done);
-            if (a.grp_waves == 8) e = launch_linetrend_pw_w<8>(st, a, t, pa, rows, len, lines, &done);
-        }
-        if (!done) {
-            e = launch_linetrend_pw_w<1>(st, a, t, pa, rows, len, lines, &done);
-            if (!done) return hipErrorInvalidValue;
+        if (!trend) {
+            e = launch_linestats_dir(st, a, rows, len, lines);
+        } else {
+            bool done = false;
+            if (lines < 8192 && len >= a.grp_minlen) {
+                if (a.grp_waves == 4) e = launch_linetrend_w<4>(st, a, *trend, pa, rows, len, lines, &done);
+                if (a.grp_waves == 8) e = launch_linetrend_w<8>(st, a, *trend, pa, rows, len, lines, &done);
+            }
+            if (!done) {
+                e = launch_linetrend_w<1>(st, a, *trend, pa, rows, len, lines, &done);
+                if (!done) return hipErrorInvalidValue;
+            }
         }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_combine_pw(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                             const PieceArgs &pa, int grid_cap)
+hipError_t launch_combine(hipStream_t st, const CombineArgs &c)
 {
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine_pw, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
-           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t, pa);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine_pw_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                                const PieceArgs &pa, int chan0, int nchan_g, int grid_cap)
-{
-    if (chan0 < 0 || nchan < 0 || chan0 + nchan > nchan_g) return hipErrorInvalidValue;
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine_pw_sh, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
-           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t, pa,
-           chan0, nchan_g);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine_dt_sh(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                                const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                                int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                                const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                                double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                                int chan0, int nchan_g, int grid_cap)
-{
-    if (chan0 < 0 || nchan < 0 || chan0 + nchan > nchan_g) return hipErrorInvalidValue;
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine_dt_sh, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
-           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t,
-           chan0, nchan_g);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine_dt(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                             const float *w0, const double *std_d, const double *mean_d, const double *ptp_d,
-                             int ptp_f32, const double *fft_d, const double *col_med, const double *col_mad,
-                             const double *row_med, const double *row_mad, double chanthresh, double subintthresh,
-                             double *test, float *W, float *hist, int iter, int32_t *counters, const TrendArgs &t,
-                             int grid_cap)
-{
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine_dt, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d, mean_d, ptp_d, ptp_f32,
-           fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh, test, W, hist, iter, counters, t);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine(hipStream_t st, int nsub, int nchan, const uint8_t *valid, const int32_t *info,
-                          const float *w0,
-                          const double *std_d, const double *mean_d, const double *ptp_d, int ptp_f32,
-                          const double *fft_d, const double *col_med, const double *col_mad,
-                          const double *row_med, const double *row_mad, double chanthresh,
-                          double subintthresh, double *test, float *W, float *hist, int iter,
-                          int32_t *counters, int grid_cap)
-{
-    const size_t P = (size_t)nsub * nchan;
-    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), grid_cap);
-    IC_GGL(k_combine, dim3(grid), dim3(256), 0, st, nsub, nchan, valid, info, w0, std_d,
-                       mean_d, ptp_d, ptp_f32, fft_d, col_med, col_mad, row_med, row_mad, chanthresh, subintthresh,
-                       test, W, hist, iter, counters);
-    return hipGetLastError();
+    const LineStatsArgs &a = c.ls;
+    const bool shard = c.trend && c.nchan_g != 0;
+    if (c.pieces && !c.trend) return hipErrorInvalidValue;
+    if (shard && (c.chan0 < 0 || a.nchan < 0 || c.chan0 + a.nchan > c.nchan_g)) return hipErrorInvalidValue;
+    const size_t P = (size_t)a.nsub * a.nchan;
+    const unsigned grid = cap_grid(std::min<size_t>(cdiv(P, 256), 1024), c.grid_cap);
+    // the arguments every form takes, then the form's own
+    auto go = [&](auto kernel, auto... form) {
+        IC_GGL(kernel, dim3(grid), dim3(256), 0, st, a.nsub, a.nchan, a.valid, c.info, c.w0, a.std_d, a.mean_d, a.ptp_d,
+               a.ptp_f32, a.fft_d, a.col_med, a.col_mad, a.row_med, a.row_mad, c.chanthresh, c.subintthresh, c.test,
+               c.W, c.hist, c.iter, c.counters, form...);
+        return hipGetLastError();
+    };
+    if (!c.trend) return go(k_combine);
+    if (shard) {
+        if (c.pieces) return go(k_combine_pw_sh, *c.trend, *c.pieces, c.chan0, c.nchan_g);
+        return go(k_combine_dt_sh, *c.trend, c.chan0, c.nchan_g);
+    }
+    if (c.pieces) return go(k_combine_pw, *c.trend, *c.pieces);
+    return go(k_combine_dt, *c.trend);
 }
 
 }  // namespace icgpu

@@ -1146,7 +1146,7 @@ int shard_rowstats(Session *s, const LineStatsArgs &la)
 {
     if (int rc = shard_rows_to_owners(s)) return rc;
     const LineStatsArgs lr = owned_rows_args(s, la, s->xr_send);
-    LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, lr, 2));
+    LAUNCH(s, K_LINESTATS, launch_lines(s->stream, lr, nullptr, nullptr, 2));
     CM(s, s->comm->allgather(s->xr_send, s->xr_recv, sizeof(double) * 8 * s->rows_pad, s->stream), "row statistics");
     LAUNCH(s, K_SHARD_PACK, launch_unpack_rowstats(s->stream, s->geom, s->rows_pad, s->xr_recv, la.row_med, la.row_mad));
     return 0;
@@ -1170,10 +1170,7 @@ int shard_rowtrends(Session *s, const LineStatsArgs &la, const TrendArgs &ta, co
         TrendArgs tr = ta;
         tr.col_coef = nullptr;
         tr.row_coef = s->xt_send + 8 * (size_t)s->rows_own;
-        if (pa)
-            LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, lr, tr, *pa, 2));
-        else
-            LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, lr, tr, 2));
+        LAUNCH(s, K_LINESTATS, launch_lines(s->stream, lr, &tr, pa, 2));
     }
     CM(s, s->comm->allgather(s->xt_send, s->xt_recv, sizeof(double) * slot, s->stream), "row trends");
     LAUNCH(s, K_SHARD_PACK,
@@ -2204,6 +2201,128 @@ int hotbins_stage(Session *s)
     return IC_OK;
 }
 
+// ---- the line stage: medians / MADs along the lines, then combine ----
+// a's line statistics over one lstat block of 8 (nsub + nchan) doubles
+void lay_lstat(LineStatsArgs *a, int nsub, int nchan, double *lstat)
+{
+    a->nsub = nsub;
+    a->nchan = nchan;
+    a->col_med = lstat;
+    a->col_mad = lstat + 4 * nchan;
+    a->row_med = lstat + 8 * nchan;
+    a->row_mad = lstat + 8 * nchan + 4 * nsub;
+}
+
+// a run's line stage: ta is read when detrend, pa when pieces
+struct LineStage {
+    LineStatsArgs la;
+    TrendArgs ta;
+    PieceArgs pa;
+    bool detrend, pieces;
+};
+
+// once per run: the stage's arguments; what the detrended forms need is
+// allocated (and the piece tables uploaded) at the first run that needs it
+int line_stage_prepare(Session *s, LineStage *g)
+{
+    const ic_params &p = s->p;
+    const int nsub = p.nsub, nchan = s->nchan;
+    LineStatsArgs &la = g->la;
+    lay_lstat(&la, nsub, nchan, s->lstat);
+    la.valid = s->valid;
+    la.std_d = s->std_;
+    la.mean_d = s->mean;
+    la.fft_d = s->fft;
+    la.ptp_d = s->ptp;
+    la.ptp_f32 = !p.data_f64;
+    la.grp_waves = s->ls_knobs.grp_waves;
+    la.grp_minlen = s->ls_knobs.grp_minlen;
+    const bool detrend = g->detrend = s->dt_chan > 0 || s->dt_sub > 0;
+    if (detrend && !s->pw_on && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
+        return fail(IC_ENOMEM, "hipMalloc(trend coefficients: %zu doubles) failed", (size_t)16 * (nchan + nsub));
+    g->ta = TrendArgs{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
+                      s->trend ? s->trend + (size_t)16 * nchan : nullptr};
+    // piecewise (ic_set_detrend_pieces): its own tables and coefficient arrays
+    const bool pieces = g->pieces = detrend && s->pw_on;
+    g->pa = PieceArgs{};
+    if (pieces) {
+        const size_t mc = s->pw_cs.size(), ms = s->pw_ss.size();
+        if (!s->pw_trend) {   // allocated last: set once all three are there
+            // (a shard's subint pieces: those of the whole subint line, on every rank)
+            const PieceTables pt = piece_tables(s->pw_cs, s->pw_ss, nsub, p.nchan);
+            if (s->mem.ensure(&s->pw_starts, pt.starts.size()) != hipSuccess ||
+                s->mem.ensure(&s->pw_piece, pt.piece.size()) != hipSuccess ||
+                s->mem.ensure(&s->pw_trend, 16 * ((size_t)nchan * mc + (size_t)nsub * ms)) != hipSuccess)
+                return fail(IC_ENOMEM, "hipMalloc(piecewise trends: %zu doubles) failed",
+                            16 * ((size_t)nchan * mc + (size_t)nsub * ms));
+            CK(hipMemcpyAsync(s->pw_starts, pt.starts.data(), sizeof(int32_t) * pt.starts.size(),
+                              hipMemcpyHostToDevice, s->stream));
+            CK(hipMemcpyAsync(s->pw_piece, pt.piece.data(), sizeof(int16_t) * pt.piece.size(), hipMemcpyHostToDevice,
+                              s->stream));
+            CK(hipStreamSynchronize(s->stream));   // pt goes out of scope
+        }
+        g->pa = piece_args(s->pw_cs, s->pw_ss, nsub, s->pw_starts, s->pw_piece);
+        g->ta.col_coef = s->pw_trend;
+        g->ta.row_coef = s->pw_trend + 16 * (size_t)nchan * mc;
+    }
+    // a shard's slots of detrended row statistics (shard_rowtrends): the
+    // transport's, sized for this run's subint pieces
+    if (detrend && s->comm) {
+        if (!s->sh_dt) return fail(IC_ESTATE, "detrending on a channel shard without ic_shard_enable_detrend");
+        const size_t ms = pieces ? s->pw_ss.size() : 1;
+        if (s->xt_ms != ms) {
+            s->comm->release(s->xt_send);
+            s->comm->release(s->xt_recv);
+            s->xt_send = s->xt_recv = nullptr;
+            s->xt_ms = 0;
+        }
+        if (!s->xt_send) {
+            const size_t slot = sizeof(double) * (size_t)s->rows_pad * (8 + 16 * ms);
+            if (s->comm->alloc((void **)&s->xt_send, slot + 16) != 0 || !s->xt_send ||
+                s->comm->alloc((void **)&s->xt_recv, slot * s->world + 16) != 0 || !s->xt_recv)
+                return fail(IC_ENOMEM, "exchange buffer (row trends, %zu bytes gathered) failed", slot * s->world);
+            s->xt_ms = ms;
+        }
+    }
+    return 0;
+}
+
+// once per iteration: the lines, a shard's rows, the counters, combine
+int line_stage(Session *s, const LineStage &g, int n_iter)
+{
+    const ic_params &p = s->p;
+    const TrendArgs *ta = g.detrend ? &g.ta : nullptr;
+    const PieceArgs *pa = g.pieces ? &g.pa : nullptr;
+    // channel medians are local to a shard (detrended too: a channel line is
+    // whole on its shard, ic_shard_enable_detrend); row medians need whole rows,
+    // which their row owners take
+    LAUNCH(s, K_LINESTATS, launch_lines(s->stream, g.la, ta, pa, s->comm ? 1 : 3));
+    if (s->comm)
+        if (int rc = ta ? shard_rowtrends(s, g.la, *ta, pa) : shard_rowstats(s, g.la)) return rc;
+    // (a shard's counters end in the two words of the standard template's hash, run_impl)
+    CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + (s->comm ? 7 : 5)), s->stream));
+    CombineArgs c;
+    c.ls = g.la;
+    c.info = s->info;
+    c.w0 = s->w0;
+    c.chanthresh = p.chanthresh;
+    c.subintthresh = p.subintthresh;
+    c.test = s->test;
+    c.W = s->W;
+    c.hist = s->hist;
+    c.iter = n_iter;
+    c.counters = s->counters;
+    c.grid_cap = s->grid_cap;
+    c.trend = ta;
+    c.pieces = pa;
+    if (ta && s->comm) {
+        c.chan0 = s->c0;
+        c.nchan_g = p.nchan;
+    }
+    LAUNCH(s, K_COMBINE, launch_combine(s->stream, c));
+    return 0;
+}
+
 int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_out, int32_t *changed_out,
              int32_t *nzero_out, int32_t *n_iter_out, int32_t *converged_out)
 {
@@ -2249,7 +2368,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     // run that failed in between may have left some set
     if (s->tmark) CK(hipMemsetAsync(s->tmark, 0, s->P, s->stream));
     const ic_params &p = s->p;
-    const int nsub = p.nsub, nchan = s->nchan, nbin = p.nbin;
+    const int nsub = p.nsub, nbin = p.nbin;
     int pr_start = p.pr_start < 0 ? 0 : (p.pr_start > nbin ? nbin : p.pr_start);
     int pr_end = p.pr_end < 0 ? 0 : (p.pr_end > nbin ? nbin : p.pr_end);
     // fit cube (ic.py:96-100) + initial weights/history; a session can be re-run
@@ -2257,70 +2376,10 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     if (s->hb_on && !s->hb_done)
         if (int rc = hotbins_stage(s)) return rc;
     if (int rc = prepare(s)) return rc;
-    LineStatsArgs la;
-    la.nsub = nsub;
-    la.nchan = nchan;
-    la.valid = s->valid;
-    la.std_d = s->std_;
-    la.mean_d = s->mean;
-    la.fft_d = s->fft;
-    la.ptp_d = s->ptp;
-    la.ptp_f32 = !p.data_f64;
-    la.grp_waves = s->ls_knobs.grp_waves;
-    la.grp_minlen = s->ls_knobs.grp_minlen;
-    la.col_med = s->lstat;
-    la.col_mad = s->lstat + 4 * nchan;
-    la.row_med = s->lstat + 8 * nchan;
-    la.row_mad = s->lstat + 8 * nchan + 4 * nsub;
-    const bool detrend = s->dt_chan > 0 || s->dt_sub > 0;
     s->trends_ran = false;
     s->std_ran = false;
-    if (detrend && !s->pw_on && s->mem.ensure(&s->trend, (size_t)16 * (nchan + nsub)) != hipSuccess)
-        return fail(IC_ENOMEM, "hipMalloc(trend coefficients: %zu doubles) failed", (size_t)16 * (nchan + nsub));
-    TrendArgs ta{s->dt_chan, s->dt_sub, s->dt_rounds, s->dt_clip, s->trend,
-                 s->trend ? s->trend + (size_t)16 * nchan : nullptr};
-    // piecewise (ic_set_detrend_pieces): its own tables and coefficient arrays
-    const bool pieces = detrend && s->pw_on;
-    PieceArgs pa{};
-    if (pieces) {
-        const size_t mc = s->pw_cs.size(), ms = s->pw_ss.size();
-        if (!s->pw_trend) {   // allocated last: set once all three are there
-            // (a shard's subint pieces: those of the whole subint line, on every rank)
-            const PieceTables pt = piece_tables(s->pw_cs, s->pw_ss, nsub, p.nchan);
-            if (s->mem.ensure(&s->pw_starts, pt.starts.size()) != hipSuccess ||
-                s->mem.ensure(&s->pw_piece, pt.piece.size()) != hipSuccess ||
-                s->mem.ensure(&s->pw_trend, 16 * ((size_t)nchan * mc + (size_t)nsub * ms)) != hipSuccess)
-                return fail(IC_ENOMEM, "hipMalloc(piecewise trends: %zu doubles) failed",
-                            16 * ((size_t)nchan * mc + (size_t)nsub * ms));
-            CK(hipMemcpyAsync(s->pw_starts, pt.starts.data(), sizeof(int32_t) * pt.starts.size(),
-                              hipMemcpyHostToDevice, s->stream));
-            CK(hipMemcpyAsync(s->pw_piece, pt.piece.data(), sizeof(int16_t) * pt.piece.size(), hipMemcpyHostToDevice,
-                              s->stream));
-            CK(hipStreamSynchronize(s->stream));   // pt goes out of scope
-        }
-        pa = piece_args(s->pw_cs, s->pw_ss, nsub, s->pw_starts, s->pw_piece);
-        ta.col_coef = s->pw_trend;
-        ta.row_coef = s->pw_trend + 16 * (size_t)nchan * mc;
-    }
-    // a shard's slots of detrended row statistics (shard_rowtrends): the
-    // transport's, sized for this run's subint pieces
-    if (detrend && s->comm) {
-        if (!s->sh_dt) return fail(IC_ESTATE, "detrending on a channel shard without ic_shard_enable_detrend");
-        const size_t ms = pieces ? s->pw_ss.size() : 1;
-        if (s->xt_ms != ms) {
-            s->comm->release(s->xt_send);
-            s->comm->release(s->xt_recv);
-            s->xt_send = s->xt_recv = nullptr;
-            s->xt_ms = 0;
-        }
-        if (!s->xt_send) {
-            const size_t slot = sizeof(double) * (size_t)s->rows_pad * (8 + 16 * ms);
-            if (s->comm->alloc((void **)&s->xt_send, slot + 16) != 0 || !s->xt_send ||
-                s->comm->alloc((void **)&s->xt_recv, slot * s->world + 16) != 0 || !s->xt_recv)
-                return fail(IC_ENOMEM, "exchange buffer (row trends, %zu bytes gathered) failed", slot * s->world);
-            s->xt_ms = ms;
-        }
-    }
+    LineStage ls;
+    if (int rc = line_stage_prepare(s, &ls)) return rc;
     int32_t *cnt = s->h_small;   // [max_iter + 5] counters, then the run stats (pinned)
     s->bad_fits.clear();
     int x = 0, loops = -1, n_iter = 0, converged = 0;
@@ -2402,55 +2461,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
         } else {
             LAUNCH(s, K_DIAG, launch_diag(s->stream, da));
         }
-        // channel medians are local to a shard; row medians need whole rows
-        if (detrend && s->comm) {
-            // (ic_shard_enable_detrend) a channel line is whole on its shard; the
-            // subint lines are fitted by their row owners
-            if (pieces)
-                LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, la, ta, pa, 1));
-            else
-                LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 1));
-            if (int rc = shard_rowtrends(s, la, ta, pieces ? &pa : nullptr)) return rc;
-        } else if (pieces) {
-            LAUNCH(s, K_LINESTATS, launch_linetrend_pw(s->stream, la, ta, pa, 3));
-        } else if (detrend) {
-            LAUNCH(s, K_LINESTATS, launch_linetrend(s->stream, la, ta, 3));
-        } else {
-            LAUNCH(s, K_LINESTATS, launch_linestats(s->stream, la, s->comm ? 1 : 3));
-            if (s->comm)
-                if (int rc = shard_rowstats(s, la)) return rc;
-        }
-        // (a shard's counters end in the two words of the standard template's hash, below)
-        CK(hipMemsetAsync(s->counters, 0, sizeof(int32_t) * (p.max_iter + (s->comm ? 7 : 5)), s->stream));
-        if (detrend && s->comm) {
-            if (pieces)
-                LAUNCH(s, K_COMBINE,
-                       launch_combine_pw_sh(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
-                                            la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad,
-                                            p.chanthresh, p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters,
-                                            ta, pa, s->c0, p.nchan, s->grid_cap));
-            else
-                LAUNCH(s, K_COMBINE,
-                       launch_combine_dt_sh(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
-                                            la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad,
-                                            p.chanthresh, p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters,
-                                            ta, s->c0, p.nchan, s->grid_cap));
-        } else if (pieces) {
-            LAUNCH(s, K_COMBINE,
-                   launch_combine_pw(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
-                                     la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
-                                     p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, ta, pa, s->grid_cap));
-        } else if (detrend) {
-            LAUNCH(s, K_COMBINE,
-                   launch_combine_dt(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
-                                     la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
-                                     p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, ta, s->grid_cap));
-        } else {
-            LAUNCH(s, K_COMBINE,
-                   launch_combine(s->stream, nsub, nchan, s->valid, s->info, s->w0, s->std_, s->mean, s->ptp,
-                                  la.ptp_f32, s->fft, la.col_med, la.col_mad, la.row_med, la.row_mad, p.chanthresh,
-                                  p.subintthresh, s->test, s->W, s->hist, n_iter, s->counters, s->grid_cap));
-        }
+        if (int rc = line_stage(s, ls, n_iter)) return rc;
         // a shard: two words of the standard template's hash (zero, as the
         // memset left them, when none is set; the first at least 1 otherwise)
         // ride behind the counters in the same all-reduce on every rank, so
@@ -2521,7 +2532,7 @@ int run_impl(Session *s, double *test_out, float *weights_out, int32_t *loops_ou
     s->stats.iterations = n_iter;
     if (converged_out) *converged_out = converged;
     s->ran = n_iter > 0;
-    s->trends_ran = detrend && n_iter > 0;
+    s->trends_ran = ls.detrend && n_iter > 0;
     s->std_ran = s->std_on && n_iter > 0;
     return IC_OK;
 }
@@ -3596,9 +3607,9 @@ static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float 
     a.ptp_o = pt;
     a.data_f64 = data_f64;
     CK(launch_diag(st, a));
-    LineStatsArgs la;
-    la.nsub = nsub;
-    la.nchan = nchan;
+    CombineArgs c;
+    LineStatsArgs &la = c.ls;
+    lay_lstat(&la, nsub, nchan, lstat);
     la.valid = valid;
     la.std_d = sd;
     la.mean_d = mn;
@@ -3607,37 +3618,36 @@ static int stats_oneshot(int device, int nsub, int nchan, int nbin, const float 
     la.ptp_f32 = !data_f64;
     la.grp_waves = rowstat_waves;
     la.grp_minlen = rowstat_minlen;
-    la.col_med = lstat;
-    la.col_mad = lstat + 4 * nchan;
-    la.row_med = lstat + 8 * nchan;
-    la.row_mad = lstat + 8 * nchan + 4 * nsub;
+    c.info = nullptr;
+    c.w0 = w0;
+    c.chanthresh = chanthresh;
+    c.subintthresh = subintthresh;
+    c.test = test;
+    c.W = W;
+    c.hist = hist;
+    c.iter = 1;
+    c.counters = cnt;
+    c.grid_cap = 0;
+    TrendArgs ta{};
+    PieceArgs pa{};
     if (trend) {
-        TrendArgs ta = *trend;
+        ta = *trend;
         ta.col_coef = coef;
         ta.row_coef = coef + (size_t)16 * nchan * mc;
-        if (pieces) {
-            CK(hipMemcpyAsync(pstarts, ptab.starts.data(), 4 * ptab.starts.size(), hipMemcpyHostToDevice, st));
-            CK(hipMemcpyAsync(ppiece, ptab.piece.data(), 2 * ptab.piece.size(), hipMemcpyHostToDevice, st));
-            const PieceArgs pa = piece_args(pieces->cs, pieces->ss, nsub, pstarts, ppiece);
-            CK(launch_linetrend_pw(st, la, ta, pa, 3));
-            CK(launch_combine_pw(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med,
-                                 la.col_mad, la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt,
-                                 ta, pa));
-        } else {
-            CK(launch_linetrend(st, la, ta, 3));
-            CK(launch_combine_dt(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, la.ptp_f32, ff, la.col_med,
-                                 la.col_mad, la.row_med, la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt,
-                                 ta));
-        }
-        if (trend->col_coef)
-            CK(hipMemcpyAsync(trend->col_coef, ta.col_coef, 8 * 16 * (size_t)nchan * mc, hipMemcpyDeviceToHost, st));
-        if (trend->row_coef)
-            CK(hipMemcpyAsync(trend->row_coef, ta.row_coef, 8 * 16 * (size_t)nsub * ms, hipMemcpyDeviceToHost, st));
-    } else {
-        CK(launch_linestats(st, la, 3));
-        CK(launch_combine(st, nsub, nchan, valid, nullptr, w0, sd, mn, pt, 1, ff, la.col_med, la.col_mad, la.row_med,
-                          la.row_mad, chanthresh, subintthresh, test, W, hist, 1, cnt));
+        c.trend = &ta;
     }
+    if (trend && pieces) {
+        CK(hipMemcpyAsync(pstarts, ptab.starts.data(), 4 * ptab.starts.size(), hipMemcpyHostToDevice, st));
+        CK(hipMemcpyAsync(ppiece, ptab.piece.data(), 2 * ptab.piece.size(), hipMemcpyHostToDevice, st));
+        pa = piece_args(pieces->cs, pieces->ss, nsub, pstarts, ppiece);
+        c.pieces = &pa;
+    }
+    CK(launch_lines(st, la, c.trend, c.pieces, 3));
+    CK(launch_combine(st, c));
+    if (trend && trend->col_coef)
+        CK(hipMemcpyAsync(trend->col_coef, ta.col_coef, 8 * 16 * (size_t)nchan * mc, hipMemcpyDeviceToHost, st));
+    if (trend && trend->row_coef)
+        CK(hipMemcpyAsync(trend->row_coef, ta.row_coef, 8 * 16 * (size_t)nsub * ms, hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(test_out, test, 8 * P, hipMemcpyDeviceToHost, st));
     if (std_o) CK(hipMemcpyAsync(std_o, sd, 8 * P, hipMemcpyDeviceToHost, st));
     if (mean_o) CK(hipMemcpyAsync(mean_o, mn, 8 * P, hipMemcpyDeviceToHost, st));
